@@ -17,6 +17,7 @@ Prints ONE JSON line on rank 0.
     stage4_b8    configs[4]  4-stage 512x512 extension (Generator4 + Disc64/128/256/512), batch 8, fp16 arithmetic
 """
 import argparse
+import copy
 import ctypes
 import importlib
 import json
@@ -227,6 +228,31 @@ def synthetic_batch(dev, batch, seed, resolutions=(64, 128, 256)):
     lens = [T] * batch
     reals = [(torch.rand(batch, 3, r, r, generator=g) * 2 - 1).to(dev) for r in resolutions]
     return words, sent, lens, reals
+
+
+def dump_outputs(out, dirname, budget=64_000_000):
+    """Write the arrays of one step's result dict to `dirname`/<name>.npy in float32 (lists as <name>0, <name>1, ...).  If they
+    exceed `budget` bytes in all, the largest arrays are cut down to a fixed seeded sample of their elements (flattened, sorted
+    indices from numpy's default_rng(0)) so that the total fits; the returned manifest says which and how."""
+    import numpy as np
+    arrays = {}
+    for k, v in out.items():
+        for i, t in (enumerate(v) if isinstance(v, (list, tuple)) else [(None, v)]):
+            if isinstance(t, torch.Tensor):
+                arrays[k if i is None else f"{k}{i}"] = t.detach().float().cpu().numpy()
+    os.makedirs(dirname, exist_ok=True)
+    left, manifest = budget - 128 * len(arrays), {}                         # (128 bytes: the .npy header of each file)
+    for n, (name, a) in enumerate(sorted(arrays.items(), key=lambda kv: (kv[1].nbytes, kv[0]))):
+        share = left // (len(arrays) - n)
+        entry = {"shape": list(a.shape)}
+        if a.nbytes > share:
+            keep = share // a.itemsize
+            entry["sample"] = f"{keep} of {a.size} elements at flat indices sorted(numpy.random.default_rng(0).choice({a.size}, {keep}, replace=False))"
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+        left -= a.nbytes
+        manifest[name] = entry
+    return {"dir": dirname, "arrays": manifest}
 
 
 def usable_cores():
@@ -440,7 +466,12 @@ def main():
                          "the end-to-end step with the Inception-shaped trunk and the LSTM text encoder, the other two BASELINE configs)")
     ap.add_argument("--cpu-baseline-batch", type=int, default=24)
     ap.add_argument("--layer-table", default=None, help="write the per-layer conv timing table of the instrumented steps to this file")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned (losses, fake images, attention maps, mu / logvar) to DIR/<name>.npy "
+                         "in float32, at most 64 MB in all (larger arrays: a fixed seeded sample), so that two builds can be compared")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     spec = WORKLOADS[args.workload]
     if args.batch is None:
         args.batch = spec["batch"]
@@ -491,6 +522,10 @@ def main():
             raise SystemExit(f"--storage {args.storage} needs --precision {args.storage} (the storage type is the MFMA operand type)")
         HF.set_activation_storage(args.storage)
     step = build(dev, args.batch, HF, args.image_encoder, args.workload)
+    # the launch-mode probe below trains a number of untimed steps that depends on what it measures: an eager timed region starts
+    # from this seeded state again (weights, BatchNorm buffers, optimisers, noise stream), so that with the same arguments it
+    # computes the same numbers whether or not the probe ran
+    initial_state = copy.deepcopy(step.state_dict(all_ranks=False))
     if args.single_stream:
         step.overlap_discriminators = False
     words, sent, lens, reals = synthetic_batch(dev, args.batch, seed=1234 + rank, resolutions=spec["reals"])
@@ -559,6 +594,13 @@ def main():
         use_graph = True
         launch_note = "segments"
     one_step = graphed.replay if use_graph else eager_step
+    if not use_graph:
+        # (in place; the copies bump the weights' versions, so the next eager step re-packs every packed weight.  A captured graph
+        # re-packs a module's weights only after that module's optimiser step: it goes on from where its capture left the state)
+        torch.cuda.synchronize()
+        step.load_state_dict(initial_state)
+        torch.cuda.synchronize()
+    del initial_state
 
     for _ in range(args.warmup):
         one_step()
@@ -579,6 +621,10 @@ def main():
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if rank == 0 and args.dump_outputs:
+        dumped = dump_outputs(out, args.dump_outputs)     # before anything else runs: later steps reuse the graph's output buffers
+        dumped["steps_trained_before_the_dumped_one"] = (f"{args.warmup + args.steps - 1} from the seeded initial state" if not use_graph
+                                                         else "the capture's and probe's untimed steps, then warm-up and timed replays")
     finite = all(bool(torch.isfinite(out[k]).all()) for k in (f"d_loss{len(step.Ds) - 1}", "g_total"))
     if dp:
         # EXPOSED exchange: HIP events around every wait of a compute stream on the exchange (GradBuckets._join), over two more
@@ -649,6 +695,8 @@ def main():
         }
         if dp_info:
             line["data_parallel"] = dp_info
+        if args.dump_outputs:
+            line["dumped_outputs"] = dumped
         if world == 1 and not dp and not args.no_variants and args.workload == "full3":
             line["variants"] = side_measurements(args, dev, HF, LIB, step, words, sent, reals)
         if world == 1 and not args.no_cpu_baseline and args.workload == "full3":

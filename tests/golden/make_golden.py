@@ -171,6 +171,15 @@ def gen_disc(cls, res, B, df, seed):
     save(f"a7_disc{res}", seed=seed, df=df, x=npy(x), y=npy(y), g_x=npy(x.grad), **before, **after, **param_grads(D))
 
 
+# --------------------------------------------------------------------------- h1
+def gen_init_weights(seed=7):
+    """The reference's initial weights after torch.manual_seed(seed): module creation order and initialisers decide them."""
+    torch.manual_seed(seed)
+    G = Generator(4, 16, 10, 10)
+    D = Disc128(4)
+    save("h1_init_seed7", seed=seed, **sd(G, "G/"), **sd(D, "D/"))
+
+
 # --------------------------------------------------------------------------- a8/a9
 def gen_damsm(seed=41):
     g = torch.Generator().manual_seed(seed)
@@ -331,6 +340,8 @@ def main():
     only = sys.argv[sys.argv.index("--only") + 1] if "--only" in sys.argv else None
     if only == "f2_rnn_encoder":
         return gen_rnn_encoder()
+    if only == "h1_init_seed7":
+        return gen_init_weights()
     gen_attention("a1_attention_small", B=4, C=8, E=32, T=10, hw=16, lens=[10, 7, 2, 10], seed=1)
     gen_attention("a1_attention_gen2", B=2, C=32, E=64, T=10, hw=64, lens=[10, 4], seed=2)
     gen_func_attention()
@@ -348,6 +359,7 @@ def main():
     gen_small_losses()
     gen_train_step()
     gen_rnn_encoder()
+    gen_init_weights()
 
 
 if __name__ == "__main__":
