@@ -859,14 +859,16 @@ __global__ __launch_bounds__(256) void bias_grad_kernel(const float* __restrict_
 // main conv kernel (gather or weight gradient), excluding the slab-sum / unpack passes that follow a split launch
 static thread_local hipEvent_t g_timer_start = nullptr, g_timer_stop = nullptr;
 static thread_local const void* g_timed_kernel = nullptr;      // host stub of the main kernel of the last timed call (AGAN_LAUNCH)
+static thread_local int g_timed_split = 0;                      // partial-sum slabs that kernel wrote (1: it wrote the result itself)
 namespace agan { namespace conv { thread_local const void* g_noted_kernel = nullptr; } }
 static inline void timer_begin(hipStream_t st) {
     if (g_timer_start) (void)hipEventRecord(g_timer_start, st);
 }
-static inline void timer_end(hipStream_t st) {
+static inline void timer_end(hipStream_t st, int split) {
     if (g_timer_stop) {
         (void)hipEventRecord(g_timer_stop, st);
         g_timed_kernel = agan::conv::g_noted_kernel;           // the LAST launch inside the bracket is the main kernel (a weight transform precedes it)
+        g_timed_split = split;
     }
     g_timer_start = g_timer_stop = nullptr;
 }
@@ -890,6 +892,8 @@ int agan_timer_last_kernel(char* name, size_t capacity) {
     free(dem);
     return AGAN_OK;
 }
+
+int agan_timer_last_split(void) { return g_timed_kernel ? g_timed_split : 0; }
 
 int agan_timer_create(void** event) {
     AGAN_REQUIRE(event != nullptr, "timer_create: null pointer");
@@ -1097,7 +1101,7 @@ int agan_conv_gather_dt(const void* in_v, const void* wkv, const float* bias, vo
             void* dst = p16.ksplit > 1 ? ws : out_v;
             timer_begin(st);
             launch_p16_gather(in_v, wkv, bias, dst, g, p16, prec, act, lrelu_mask_v, st, in_dtype != AGAN_DT_F32, out_dtype != AGAN_DT_F32);
-            timer_end(st);
+            timer_end(st, p16.ksplit);
             if (int e = check_launch("conv_gather/p16")) return e;
             if (p16.ksplit > 1) {
                 const size_t n = (size_t)g.B * g.Cout * g.OH * g.OW;
@@ -1125,7 +1129,7 @@ int agan_conv_gather_dt(const void* in_v, const void* wkv, const float* bias, vo
         timer_begin(st);
         AGAN_REQUIRE(prec != AGAN_PREC_F16X3 || in_scale != nullptr, "conv_gather: AGAN_PREC_F16X3 needs the operand's agan_absmax_scale pair");
         launch_patch_gather(in, wkv, bias, dst, g, pp, p, prec, act, lrelu_mask, st, in_scale, out_amax);
-        timer_end(st);
+        timer_end(st, p.ksplit);
         if (int e = check_launch("conv_gather/patch")) return e;
         if (p.ksplit > 1) {
             const size_t n = (size_t)g.B * g.Cout * g.OH * g.OW;
@@ -1144,7 +1148,7 @@ int agan_conv_gather_dt(const void* in_v, const void* wkv, const float* bias, vo
             }
             timer_begin(st);
             launch_wino(in, wk, out, g, wp, ws, st);
-            timer_end(st);
+            timer_end(st, wp.ksplit);
             if (int e = check_launch("conv_gather/winograd")) return e;
             if (wp.ksplit > 1) {
                 const size_t n = (size_t)g.B * g.Cout * g.OH * g.OW;
@@ -1158,7 +1162,7 @@ int agan_conv_gather_dt(const void* in_v, const void* wkv, const float* bias, vo
     if (prec == AGAN_PREC_F32 && small_n_gather_supported(g)) {
         timer_begin(st);
         launch_gather_small_n(in_v, wk, bias, out, g, st, in_dtype);
-        timer_end(st);
+        timer_end(st, 1);
         return check_launch("conv_gather/small_n");
     }
     const GatherPlan p = plan_gather(g, prec);
@@ -1171,7 +1175,7 @@ int agan_conv_gather_dt(const void* in_v, const void* wkv, const float* bias, vo
     if (p.bn == 128) launch_gather<128, 2, 2>(in, wk, bias, dst, ktab, g, p, act, lrelu_mask_v, st, out_dtype);
     else if (p.bn == 64) launch_gather<64, 2, 2>(in, wk, bias, dst, ktab, g, p, act, lrelu_mask_v, st, out_dtype);
     else launch_gather<32, 4, 1>(in, wk, bias, dst, ktab, g, p, act, lrelu_mask_v, st, out_dtype);
-    timer_end(st);
+    timer_end(st, p.ksplit);
     if (int e = check_launch("conv_gather")) return e;
     if (p.ksplit > 1) {
         const size_t n = (size_t)g.B * g.Cout * g.OH * g.OW;
@@ -1267,7 +1271,7 @@ int agan_conv_wgrad_dt(const void* x_v, const void* dy_v, float* dw, const agan_
             float* wsf = static_cast<float*>(ws);
             timer_begin(st);
             launch_wino_wgrad(x, dy, wsf, g, wp, st);
-            timer_end(st);
+            timer_end(st, wp.psplit);
             if (int e = check_launch("conv_wgrad/winograd")) return e;
             launch_wino_wgrad_sum(wsf, g, wp, dw, accumulate ? 1 : 0, st);
             return check_launch("conv_wgrad/winograd/sum");
@@ -1287,7 +1291,7 @@ int agan_conv_wgrad_dt(const void* x_v, const void* dy_v, float* dw, const agan_
                          "amax slots of x and dy (x_amax / dy_amax)", prec_asked);
             timer_begin(st);
             launch_rows_wgrad(x_v, dy_v, wsf, g, rp, prec, st, x_scale, dy_scale, x_dtype != AGAN_DT_F32, dy_dtype != AGAN_DT_F32);
-            timer_end(st);
+            timer_end(st, rp.psplit);
             if (int e = check_launch("conv_wgrad/rows")) return e;
             // few slabs: summed inside the unpack pass; many (the small layers, split 100-fold over their pixels): the bandwidth-bound slab sum first
             const float* src = wsf;
@@ -1318,7 +1322,7 @@ int agan_conv_wgrad_dt(const void* x_v, const void* dy_v, float* dw, const agan_
                          "conv_wgrad: precision mode %d runs this weight gradient as AGAN_PREC_F16X3 (agan_conv_wgrad_effective_prec), which needs the "
                          "amax slots of x and dy (x_amax / dy_amax)", prec_asked);
         launch_patch_wgrad(x_v, dy_v, wsf, g, pp, p, prec, st, x_scale, dy_scale, x_dtype != AGAN_DT_F32, dy_dtype != AGAN_DT_F32);
-        timer_end(st);
+        timer_end(st, p.psplit);
         if (int e = check_launch("conv_wgrad/patch")) return e;
         if (!up && p.psplit <= 4) {
             launch_wgrad_sum_unpack(wsf, p.psplit, p.slab, dw, g.Cout, g.Cin, kh, kw, pp.NPH, pp.NT, p.Kp, accumulate, st);
@@ -1342,7 +1346,7 @@ int agan_conv_wgrad_dt(const void* x_v, const void* dy_v, float* dw, const agan_
         float* part = static_cast<float*>(ws);
         timer_begin(st);
         launch_wgrad_small_n(x_v, dy, part, g, sp, st, x_dtype);
-        timer_end(st);
+        timer_end(st, sp.nchunk);
         const size_t n = (size_t)g.Cout * g.K;
         launch_sum_slabs(part, sp.nchunk, n, sp.slab, nullptr, 1, 1, dw, accumulate, AGAN_ACT_NONE, nullptr, nullptr, st);
         return check_launch("conv_wgrad/small_n");
@@ -1368,7 +1372,7 @@ int agan_conv_wgrad_dt(const void* x_v, const void* dy_v, float* dw, const agan_
     else if (p.bi == 128) AGAN_WG(128, 64);
     else if (p.bj == 128) AGAN_WG(64, 128);
     else AGAN_WG(64, 64);
-    timer_end(st);
+    timer_end(st, p.psplit);
 #undef AGAN_WG
     if (int e = check_launch("conv_wgrad")) return e;
     const size_t n = (size_t)p.ncls * g.Cout * g.K;

@@ -327,6 +327,9 @@ int agan_timer_elapsed_ms(void* start, void* stop, float* ms);
  * --kernel-trace --stats` names it (e.g. "void (anonymous namespace)::conv_gather_f32_kernel<128, 128, 2, 2, 0>(float const*, ...)"),
  * copied into name[capacity]; empty if nothing has been timed.  bench.py keys `roofline_by_kernel` with it. */
 int agan_timer_last_kernel(char* name, size_t capacity);
+/* The split factor of that kernel's launch: its plan's K split (gathers) or pixel split (weight gradients), i.e. how many partial
+ * sums per output the pass after it adds up; 1 for an unsplit launch; 0 if nothing has been timed. */
+int agan_timer_last_split(void);
 
 static inline int agan_round_up(int v, int m) { return (v + m - 1) / m * m; }
 
