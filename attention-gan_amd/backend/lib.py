@@ -87,6 +87,7 @@ _SIGNATURES = {
     "agan_act_bwd": (c_int, [_P, _P, _P, c_size_t, c_int, _P]),
     "agan_glu_fwd": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
     "agan_glu_bwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),
+    "agan_bn_last_launch": (c_int, [_P, c_int]),
     "agan_attn_fwd": (c_int, [_P, _P, _P, _P, c_float, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     "agan_attn_bwd_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "agan_attn_bwd": (c_int, [_P] * 7 + [c_float, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_size_t, _P]),

@@ -15,6 +15,23 @@ constexpr float kSlope = 0.2f;   // LeakyReLU slope, utilities/layers.py:124
 
 __device__ __forceinline__ float sigmoidf_(float v) { return 1.f / (1.f + __expf(-v)); }
 
+// Values per thread and loop step of the streaming sweeps: 8 where a 16-bit tensor is involved and rows are whole 8-groups (16-byte
+// accesses on it), else 4, else 1.  The host's choice of template width and the in-kernel loop choice both call this.
+__host__ __device__ __forceinline__ int vec_width(bool any16, int HW) { return (any16 && (HW & 7) == 0) ? 8 : ((HW & 3) == 0 ? 4 : 1); }
+
+// ---- launch log: one integer per kernel launch of the last agan_bn_* / agan_act_* / agan_glu_* call (agan_bn_last_launch) --------
+constexpr int kLogCap = 64;
+thread_local int g_log[kLogCap];
+thread_local int g_log_n = 0;
+// kernel kinds of a log code (include/agan.h: agan_bn_last_launch)
+enum { kLogStatsPartial = 1, kLogStatsFinal, kLogStatsRows, kLogFwdApply, kLogSmallFwd, kLogSmallBwd, kLogBwdPartial, kLogBwdFinal,
+       kLogBwdApply, kLogActFwd, kLogActBwd, kLogGluFwd, kLogGluBwd };
+inline void log_reset() { g_log_n = 0; }
+inline void log_launch(int kind, int act, int xdt, int odt, int width) {
+    if (g_log_n < kLogCap) g_log[g_log_n] = kind * 100000 + act * 10000 + xdt * 1000 + odt * 100 + width;
+    ++g_log_n;
+}
+
 // ---- chunked per-channel reduction driver -----------------------------------------------------------------
 // Calls f(x_index, flat_pixel_index, vec) for every element of channel c inside [beg, end) of the (b, p) space.
 struct Chunk { int beg, end; };
@@ -39,7 +56,8 @@ __global__ __launch_bounds__(256) void bn_stats_partial_kernel(const void* __res
     const int n = B * HW;
     const Chunk ch = chunk_of(n, nchunk, chunk);
     double s = 0.0, q = 0.0;
-    if (XDT != AGAN_DT_F32 && (HW & 7) == 0) {           // 16-bit storage: 8 values = one 16-byte load (chunks are multiples of 8 then)
+    const int w = vec_width(XDT != AGAN_DT_F32, HW);
+    if (w == 8) {                                        // 16-bit storage: 8 values = one 16-byte load (chunks are multiples of 8 then)
         for (int i = ch.beg + threadIdx.x * 8; i < ch.end; i += 2048) {
             const int b = i / HW, p = i - b * HW;
             float v[8];
@@ -51,7 +69,7 @@ __global__ __launch_bounds__(256) void bn_stats_partial_kernel(const void* __res
             s += (double)s4;
             q += q4;
         }
-    } else if ((HW & 3) == 0) {
+    } else if (w == 4) {
         for (int i = ch.beg + threadIdx.x * 4; i < ch.end; i += 1024) {
             const int b = i / HW, p = i - b * HW;
             const float4 v = ld4<XDT>(x, ((size_t)b * C + c) * HW + p);
@@ -68,8 +86,8 @@ __global__ __launch_bounds__(256) void bn_stats_partial_kernel(const void* __res
     }
     s = wave_sum_d(s);
     q = wave_sum_d(q);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { red[0][w] = s; red[1][w] = q; }
+    const int wv = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { red[0][wv] = s; red[1][wv] = q; }
     __syncthreads();
     if (threadIdx.x == 0) {
         part[((size_t)c * nchunk + chunk) * 2 + 0] = red[0][0] + red[0][1] + red[0][2] + red[0][3];
@@ -137,13 +155,24 @@ int stats_chunks(int B, int C, int HW) {
 // ---------------------------------------------------------------------------------------------------------
 // forward apply
 // ---------------------------------------------------------------------------------------------------------
-struct Affine { float s, t; };
-__device__ __forceinline__ Affine affine_of(const float* mean, const float* invstd, const float* gamma, const float* beta, int c) {
+// z = (x - m) * s + b with s = gamma * invstd.  Most channels take the folded form m = 0, b = beta - mean * s (one FMA per value).
+// Where the mean is more than kCentreAt standard deviations from 0 the fold cancels two values of magnitude |mean * s| >> |z| and
+// loses z's own scale: such a channel is centred first, m = mean, b = beta ((x - mean) is exact there).  x - 0 = x exactly, so the
+// folded channels compute exactly what the plain x * s + (beta - mean * s) computes.
+constexpr float kCentreAt = 16.f;
+struct Affine { float s, m, b; };
+__device__ __forceinline__ Affine make_affine(float mean, float invstd, float gamma, float beta) {
     Affine a;
-    a.s = gamma[c] * invstd[c];
-    a.t = beta[c] - mean[c] * a.s;
+    a.s = gamma * invstd;
+    const bool centre = fabsf(mean * invstd) > kCentreAt;
+    a.m = centre ? mean : 0.f;
+    a.b = centre ? beta : beta - mean * a.s;
     return a;
 }
+__device__ __forceinline__ Affine affine_of(const float* mean, const float* invstd, const float* gamma, const float* beta, int c) {
+    return make_affine(mean[c], invstd[c], gamma[c], beta[c]);
+}
+__device__ __forceinline__ float norm_of(const Affine& a, float x) { return (x - a.m) * a.s + a.b; }
 
 // XDT: storage type of x; ODT: of out and the residual
 // V: elements per thread and iteration (1, 4, or 8 where a 16-bit tensor is involved: 16-byte accesses on it)
@@ -169,12 +198,12 @@ __global__ __launch_bounds__(256) void bn_act_fwd_kernel(const void* __restrict_
             float gv[V];
             ldv<XDT, V>(x, xi + (size_t)Co * HW, gv);
 #pragma unroll
-            for (int k = 0; k < V; ++k) yv[k] = (xv[k] * a.s + a.t) * sigmoidf_(gv[k] * g.s + g.t);
+            for (int k = 0; k < V; ++k) yv[k] = norm_of(a, xv[k]) * sigmoidf_(norm_of(g, gv[k]));
         } else {
 #pragma unroll
             for (int k = 0; k < V; ++k) {
-                float z = xv[k] * a.s + a.t;
-                if (ACT == AGAN_ACT_LRELU) z = z >= 0.f ? z : z * kSlope;
+                float z = norm_of(a, xv[k]);
+                if (ACT == AGAN_ACT_LRELU) z = z > 0.f ? z : z * kSlope;
                 yv[k] = z;
             }
             if (res) {
@@ -198,13 +227,13 @@ __global__ __launch_bounds__(256) void bn_act_fwd_kernel(const void* __restrict_
 template <int ACT>
 __device__ __forceinline__ void dz_of(float xa, float xg, float d, const Affine& a, const Affine& g, float& dza, float& dzg) {
     if (ACT == AGAN_ACT_GLU) {
-        const float za = xa * a.s + a.t;
-        const float sg = sigmoidf_(xg * g.s + g.t);
+        const float za = norm_of(a, xa);
+        const float sg = sigmoidf_(norm_of(g, xg));
         dza = d * sg;
         dzg = d * za * sg * (1.f - sg);
     } else if (ACT == AGAN_ACT_LRELU) {
-        const float z = xa * a.s + a.t;
-        dza = z >= 0.f ? d : d * kSlope;
+        const float z = norm_of(a, xa);
+        dza = z > 0.f ? d : d * kSlope;         // torch's leaky_relu_backward: slope 1 only where the input is > 0
         dzg = 0.f;
     } else {
         dza = d;
@@ -256,8 +285,9 @@ __global__ __launch_bounds__(256) void bn_bwd_partial_kernel(const void* __restr
         }
     };
     constexpr bool any16 = XDT != AGAN_DT_F32 || ODT != AGAN_DT_F32;
-    if (any16 && (HW & 7) == 0) sweep(std::integral_constant<int, 8>{});
-    else if ((HW & 3) == 0) sweep(std::integral_constant<int, 4>{});
+    const int nv = vec_width(any16, HW);
+    if (nv == 8) sweep(std::integral_constant<int, 8>{});
+    else if (nv == 4) sweep(std::integral_constant<int, 4>{});
     else sweep(std::integral_constant<int, 1>{});
     s0 = wave_sum_d(s0); s1 = wave_sum_d(s1);
     if (ACT == AGAN_ACT_GLU) { s2 = wave_sum_d(s2); s3 = wave_sum_d(s3); }
@@ -334,7 +364,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const void* __restric
 // ---------------------------------------------------------------------------------------------------------
 template <int ACT>
 __device__ __forceinline__ float act1(float v) {
-    if (ACT == AGAN_ACT_LRELU) return v >= 0.f ? v : v * kSlope;
+    if (ACT == AGAN_ACT_LRELU) return v > 0.f ? v : v * kSlope;
     if (ACT == AGAN_ACT_TANH) return tanhf(v);
     if (ACT == AGAN_ACT_SIGMOID) return 1.f / (1.f + expf(-v));
     return v;
@@ -342,7 +372,7 @@ __device__ __forceinline__ float act1(float v) {
 // derivative expressed from the OUTPUT y (lrelu keeps the sign, so y works there too)
 template <int ACT>
 __device__ __forceinline__ float dact1(float y, float d) {
-    if (ACT == AGAN_ACT_LRELU) return y >= 0.f ? d : d * kSlope;
+    if (ACT == AGAN_ACT_LRELU) return y > 0.f ? d : d * kSlope;      // (y > 0 exactly where the input is > 0)
     if (ACT == AGAN_ACT_TANH) return d * (1.f - y * y);
     if (ACT == AGAN_ACT_SIGMOID) return d * y * (1.f - y);
     return d;
@@ -479,18 +509,18 @@ __global__ __launch_bounds__(256) void bn_small_fwd_kernel(const void* __restric
             }
         }
     }
-    const float sa = gamma[c] * is, ta = beta[c] - (float)m * sa;
-    float sgs = 0.f, tg = 0.f, mx = 0.f;
-    if (GLU) { sgs = gamma[c + Co] * isg; tg = beta[c + Co] - mgf * sgs; }
+    const Affine a = make_affine((float)m, is, gamma[c], beta[c]);
+    const Affine g = GLU ? make_affine(mgf, isg, gamma[c + Co], beta[c + Co]) : a;
+    float mx = 0.f;
 #pragma unroll
     for (int j = 0; j < PER; ++j) {
         const int i = threadIdx.x + j * 256;
         if (i < n) {
             const int b = i / HW, p = i - b * HW;
             const size_t oi = ((size_t)b * Co + c) * HW + p;
-            float z = va[j] * sa + ta;
-            if (GLU) z *= sigmoidf_(vg[j] * sgs + tg);
-            else if (ACT == AGAN_ACT_LRELU) z = z >= 0.f ? z : z * kSlope;
+            float z = norm_of(a, va[j]);
+            if (GLU) z *= sigmoidf_(norm_of(g, vg[j]));
+            else if (ACT == AGAN_ACT_LRELU) z = z > 0.f ? z : z * kSlope;
             if (!GLU && ACT == AGAN_ACT_NONE && res) z += ld1<ODT>(res, oi);
             st1<ODT>(out, oi, z);
             mx = fmaxf(mx, fabsf(z));
@@ -589,21 +619,16 @@ static bool bn_dt_ok(int xd, int od) {
 static const void* off(const void* p, size_t elems, int dt) { return static_cast<const char*>(p) + elems * dt_size(dt); }
 static void* off(void* p, size_t elems, int dt) { return static_cast<char*>(p) + elems * dt_size(dt); }
 
-extern "C" {
-
-size_t agan_bn_stats_ws_bytes(int B, int C, int HW) {
-    if (HW == 1) return 0;
-    return (size_t)C * stats_chunks(B, C, HW) * 2 * sizeof(double);
-}
-
-int agan_bn_stats_dt(const void* x, int B, int C, int HW, float eps, float* mean, float* invstd, float* running_mean,
-                     float* running_var, int64_t* nbt, float momentum, void* ws, size_t ws_bytes, void* stream, int x_dtype) {
+// (bodies of agan_bn_stats_dt / agan_bn_act_fwd_dt without the launch-log reset: agan_bn_train_fwd_dt calls them per group)
+static int bn_stats_impl(const void* x, int B, int C, int HW, float eps, float* mean, float* invstd, float* running_mean,
+                         float* running_var, int64_t* nbt, float momentum, void* ws, size_t ws_bytes, void* stream, int x_dtype) {
     AGAN_REQUIRE(x && mean && invstd && B > 0 && C > 0 && HW > 0, "bn_stats: bad argument");
     AGAN_REQUIRE((running_mean == nullptr) == (running_var == nullptr), "bn_stats: running_mean/var must come together");
     AGAN_REQUIRE(x_dtype == AGAN_DT_F32 || x_dtype == AGAN_DT_BF16 || x_dtype == AGAN_DT_F16, "bn_stats: storage type %d", x_dtype);
     hipStream_t st = as_stream(stream);
     if (HW == 1) {
         AGAN_REQUIRE(x_dtype == AGAN_DT_F32, "bn_stats: [B, C] inputs (BatchNorm1d) are fp32 only");
+        log_launch(kLogStatsRows, 0, x_dtype, x_dtype, 1);
         hipLaunchKernelGGL(bn_stats_rows_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, static_cast<const float*>(x), B, C, eps, mean, invstd,
                            running_mean, running_var, nbt, momentum);
         return check_launch("bn_stats_rows");
@@ -614,21 +639,19 @@ int agan_bn_stats_dt(const void* x, int B, int C, int HW, float eps, float* mean
         return AGAN_EWORKSPACE;
     }
     double* part = static_cast<double*>(ws);
+    log_launch(kLogStatsPartial, 0, x_dtype, x_dtype, vec_width(x_dtype != AGAN_DT_F32, HW));
     if (x_dtype == AGAN_DT_F32) hipLaunchKernelGGL(bn_stats_partial_kernel<AGAN_DT_F32>, dim3(C, nchunk), dim3(256), 0, st, x, B, C, HW, nchunk, part);
     else if (x_dtype == AGAN_DT_BF16) hipLaunchKernelGGL(bn_stats_partial_kernel<AGAN_DT_BF16>, dim3(C, nchunk), dim3(256), 0, st, x, B, C, HW, nchunk, part);
     else hipLaunchKernelGGL(bn_stats_partial_kernel<AGAN_DT_F16>, dim3(C, nchunk), dim3(256), 0, st, x, B, C, HW, nchunk, part);
+    log_launch(kLogStatsFinal, 0, x_dtype, x_dtype, 1);
     hipLaunchKernelGGL(bn_stats_final_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, part, C, nchunk, B * HW, eps, mean, invstd,
                        running_mean, running_var, nbt, momentum);
     return check_launch("bn_stats");
 }
-int agan_bn_stats(const float* x, int B, int C, int HW, float eps, float* mean, float* invstd, float* running_mean,
-                  float* running_var, int64_t* nbt, float momentum, void* ws, size_t ws_bytes, void* stream) {
-    return agan_bn_stats_dt(x, B, C, HW, eps, mean, invstd, running_mean, running_var, nbt, momentum, ws, ws_bytes, stream, AGAN_DT_F32);
-}
 
-int agan_bn_act_fwd_dt(const void* x, const float* mean, const float* invstd, const float* gamma, const float* beta,
-                       const void* residual, void* out, int B, int C, int HW, int act, void* stream, float* out_amax, int x_dtype,
-                       int out_dtype) {
+static int bn_act_fwd_impl(const void* x, const float* mean, const float* invstd, const float* gamma, const float* beta,
+                           const void* residual, void* out, int B, int C, int HW, int act, void* stream, float* out_amax, int x_dtype,
+                           int out_dtype) {
     AGAN_REQUIRE(x && mean && invstd && gamma && beta && out && B > 0 && C > 0 && HW > 0, "bn_act_fwd: bad argument");
     AGAN_REQUIRE(act == AGAN_ACT_NONE || act == AGAN_ACT_GLU || act == AGAN_ACT_LRELU, "bn_act_fwd: activation %d", act);
     AGAN_REQUIRE(act != AGAN_ACT_GLU || (C % 2 == 0), "channels dont divide 2!");
@@ -636,10 +659,10 @@ int agan_bn_act_fwd_dt(const void* x, const float* mean, const float* invstd, co
     AGAN_REQUIRE(bn_dt_ok(x_dtype, out_dtype), "bn_act_fwd: storage types %d -> %d", x_dtype, out_dtype);
     hipStream_t st = as_stream(stream);
     // elements per thread and iteration: 8 where a 16-bit tensor is involved and rows are whole 8-groups (16-byte accesses on it), else 4 / 1
-    const int vw = ((x_dtype != AGAN_DT_F32 || out_dtype != AGAN_DT_F32) && (HW & 7) == 0) ? 8 : ((HW & 3) == 0 ? 4 : 1);
+    const int vw = vec_width(x_dtype != AGAN_DT_F32 || out_dtype != AGAN_DT_F32, HW);
     const int Co = act == AGAN_ACT_GLU ? C / 2 : C;
     const int blocks = ew_blocks((size_t)B * Co * HW / vw);
-#define AGAN_L(A, V, XD, OD) hipLaunchKernelGGL((bn_act_fwd_kernel<A, V, XD, OD>), dim3(blocks), dim3(256), 0, st, x, mean, invstd, gamma, beta, residual, out, B, C, HW, out_amax)
+#define AGAN_L(A, V, XD, OD) do { log_launch(kLogFwdApply, A, XD, OD, V); hipLaunchKernelGGL((bn_act_fwd_kernel<A, V, XD, OD>), dim3(blocks), dim3(256), 0, st, x, mean, invstd, gamma, beta, residual, out, B, C, HW, out_amax); } while (0)
 #define AGAN_V(A, XD, OD)                                                                                           \
     do {                                                                                                            \
         if (vw == 8) { if constexpr ((XD) != AGAN_DT_F32 || (OD) != AGAN_DT_F32) AGAN_L(A, 8, XD, OD); }             \
@@ -656,6 +679,36 @@ int agan_bn_act_fwd_dt(const void* x, const float* mean, const float* invstd, co
 #undef AGAN_L
     return check_launch("bn_act_fwd");
 }
+
+extern "C" {
+
+size_t agan_bn_stats_ws_bytes(int B, int C, int HW) {
+    if (HW == 1) return 0;
+    return (size_t)C * stats_chunks(B, C, HW) * 2 * sizeof(double);
+}
+
+int agan_bn_last_launch(int* codes, int capacity) {
+    const int n = std::min(std::min(g_log_n, kLogCap), capacity);
+    for (int i = 0; i < n; ++i) codes[i] = g_log[i];
+    return g_log_n;
+}
+
+int agan_bn_stats_dt(const void* x, int B, int C, int HW, float eps, float* mean, float* invstd, float* running_mean,
+                     float* running_var, int64_t* nbt, float momentum, void* ws, size_t ws_bytes, void* stream, int x_dtype) {
+    log_reset();
+    return bn_stats_impl(x, B, C, HW, eps, mean, invstd, running_mean, running_var, nbt, momentum, ws, ws_bytes, stream, x_dtype);
+}
+int agan_bn_stats(const float* x, int B, int C, int HW, float eps, float* mean, float* invstd, float* running_mean,
+                  float* running_var, int64_t* nbt, float momentum, void* ws, size_t ws_bytes, void* stream) {
+    return agan_bn_stats_dt(x, B, C, HW, eps, mean, invstd, running_mean, running_var, nbt, momentum, ws, ws_bytes, stream, AGAN_DT_F32);
+}
+
+int agan_bn_act_fwd_dt(const void* x, const float* mean, const float* invstd, const float* gamma, const float* beta,
+                       const void* residual, void* out, int B, int C, int HW, int act, void* stream, float* out_amax, int x_dtype,
+                       int out_dtype) {
+    log_reset();
+    return bn_act_fwd_impl(x, mean, invstd, gamma, beta, residual, out, B, C, HW, act, stream, out_amax, x_dtype, out_dtype);
+}
 int agan_bn_act_fwd(const float* x, const float* mean, const float* invstd, const float* gamma, const float* beta,
                     const float* residual, float* out, int B, int C, int HW, int act, void* stream, float* out_amax) {
     return agan_bn_act_fwd_dt(x, mean, invstd, gamma, beta, residual, out, B, C, HW, act, stream, out_amax, AGAN_DT_F32, AGAN_DT_F32);
@@ -670,6 +723,7 @@ size_t agan_bn_act_bwd_ws_bytes(int B, int C, int HW) {
 int agan_bn_act_bwd_dt(const void* x, const void* dout, const float* mean, const float* invstd, const float* gamma,
                        const float* beta, void* dx, float* dgamma, float* dbeta, int B, int C, int HW, int act, int accumulate,
                        int groups, void* ws, size_t ws_bytes, void* stream, float* dx_amax, int x_dtype, int out_dtype) {
+    log_reset();
     AGAN_REQUIRE(x && dout && mean && invstd && gamma && beta && dx && dgamma && dbeta && ws, "bn_act_bwd: null pointer");
     AGAN_REQUIRE(act == AGAN_ACT_NONE || act == AGAN_ACT_GLU || act == AGAN_ACT_LRELU, "bn_act_bwd: activation %d", act);
     AGAN_REQUIRE(act != AGAN_ACT_GLU || (C % 2 == 0), "channels dont divide 2!");
@@ -689,7 +743,7 @@ int agan_bn_act_bwd_dt(const void* x, const void* dout, const float* mean, const
             const void* dg = off(dout, (size_t)gi * Bg * Co * HW, out_dtype);
             void* dxg = off(dx, (size_t)gi * Bg * C * HW, x_dtype);
             const int acc = gi == 0 ? accumulate : 1;
-#define AGAN_LP(A, XD, OD, P) hipLaunchKernelGGL((bn_small_bwd_kernel<A, XD, OD, P>), dim3(Co), dim3(256), 0, st, xg, dg, mean + (size_t)gi * C, invstd + (size_t)gi * C, gamma, beta, dxg, dgamma, dbeta, Bg, C, HW, acc, dx_amax)
+#define AGAN_LP(A, XD, OD, P) do { log_launch(kLogSmallBwd, A, XD, OD, P); hipLaunchKernelGGL((bn_small_bwd_kernel<A, XD, OD, P>), dim3(Co), dim3(256), 0, st, xg, dg, mean + (size_t)gi * C, invstd + (size_t)gi * C, gamma, beta, dxg, dgamma, dbeta, Bg, C, HW, acc, dx_amax); } while (0)
 #define AGAN_L(A, XD, OD) do { if (Bg * HW <= 512) AGAN_LP(A, XD, OD, 2); else if (Bg * HW <= 2048) AGAN_LP(A, XD, OD, 8); else AGAN_LP(A, XD, OD, kSmallPer); } while (0)
 #define AGAN_C(XD, OD)                                           \
     if (act == AGAN_ACT_GLU) AGAN_L(AGAN_ACT_GLU, XD, OD);       \
@@ -706,7 +760,7 @@ int agan_bn_act_bwd_dt(const void* x, const void* dout, const float* mean, const
     double* part = static_cast<double*>(ws);
     float* coef = reinterpret_cast<float*>(part + (size_t)C * nchunk * 4);
     dim3 grid(Co, nchunk);
-    const int vw = ((x_dtype != AGAN_DT_F32 || out_dtype != AGAN_DT_F32) && (HW & 7) == 0) ? 8 : ((HW & 3) == 0 ? 4 : 1);
+    const int vw = vec_width(x_dtype != AGAN_DT_F32 || out_dtype != AGAN_DT_F32, HW);      // (also the partial kernel's sweep width)
     const int blocks = ew_blocks((size_t)Bg * Co * HW / vw);
     for (int gi = 0; gi < groups; ++gi) {      // group 0 writes (or adds to) the gamma/beta gradients, the others add
         const void* xg = off(x, (size_t)gi * Bg * C * HW, x_dtype);
@@ -715,7 +769,7 @@ int agan_bn_act_bwd_dt(const void* x, const void* dout, const float* mean, const
         const float* ig = invstd + (size_t)gi * C;
         void* dxg = off(dx, (size_t)gi * Bg * C * HW, x_dtype);
         const int acc = gi == 0 ? accumulate : 1;
-#define AGAN_P(A, XD, OD) hipLaunchKernelGGL((bn_bwd_partial_kernel<A, XD, OD>), grid, dim3(256), 0, st, xg, dg, mg, ig, gamma, beta, Bg, C, HW, nchunk, part)
+#define AGAN_P(A, XD, OD) do { log_launch(kLogBwdPartial, A, XD, OD, vw); hipLaunchKernelGGL((bn_bwd_partial_kernel<A, XD, OD>), grid, dim3(256), 0, st, xg, dg, mg, ig, gamma, beta, Bg, C, HW, nchunk, part); } while (0)
 #define AGAN_C(XD, OD)                                           \
     if (glu) AGAN_P(AGAN_ACT_GLU, XD, OD);                        \
     else if (act == AGAN_ACT_LRELU) AGAN_P(AGAN_ACT_LRELU, XD, OD); \
@@ -723,8 +777,9 @@ int agan_bn_act_bwd_dt(const void* x, const void* dout, const float* mean, const
         AGAN_BN_DT(x_dtype, out_dtype, AGAN_C);
 #undef AGAN_C
 #undef AGAN_P
+        log_launch(kLogBwdFinal, act, x_dtype, out_dtype, 1);
         hipLaunchKernelGGL(bn_bwd_final_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, part, C, Co, nchunk, Bg * HW, glu, dgamma, dbeta, coef, acc);
-#define AGAN_L(A, V, XD, OD) hipLaunchKernelGGL((bn_bwd_apply_kernel<A, V, XD, OD>), dim3(blocks), dim3(256), 0, st, xg, dg, mg, ig, gamma, beta, coef, dxg, Bg, C, HW, dx_amax)
+#define AGAN_L(A, V, XD, OD) do { log_launch(kLogBwdApply, A, XD, OD, V); hipLaunchKernelGGL((bn_bwd_apply_kernel<A, V, XD, OD>), dim3(blocks), dim3(256), 0, st, xg, dg, mg, ig, gamma, beta, coef, dxg, Bg, C, HW, dx_amax); } while (0)
 #define AGAN_V(A, XD, OD)                                                                                           \
     do {                                                                                                            \
         if (vw == 8) { if constexpr ((XD) != AGAN_DT_F32 || (OD) != AGAN_DT_F32) AGAN_L(A, 8, XD, OD); }             \
@@ -750,8 +805,10 @@ int agan_bn_act_bwd(const float* x, const float* dout, const float* mean, const 
 }
 
 int agan_act_fwd(const float* x, float* out, size_t n, int act, void* stream) {
+    log_reset();
     AGAN_REQUIRE(x && out && n > 0, "act_fwd: bad argument");
     hipStream_t st = as_stream(stream);
+    log_launch(kLogActFwd, act, AGAN_DT_F32, AGAN_DT_F32, 4);
     const int blocks = ew_blocks(n / 4 + 1);
     switch (act) {
         case AGAN_ACT_LRELU: hipLaunchKernelGGL((act_fwd_kernel<AGAN_ACT_LRELU>), dim3(blocks), dim3(256), 0, st, x, out, n); break;
@@ -763,8 +820,10 @@ int agan_act_fwd(const float* x, float* out, size_t n, int act, void* stream) {
 }
 
 int agan_act_bwd(const float* y, const float* dout, float* dx, size_t n, int act, void* stream) {
+    log_reset();
     AGAN_REQUIRE(y && dout && dx && n > 0, "act_bwd: bad argument");
     hipStream_t st = as_stream(stream);
+    log_launch(kLogActBwd, act, AGAN_DT_F32, AGAN_DT_F32, 4);
     const int blocks = ew_blocks(n / 4 + 1);
     switch (act) {
         case AGAN_ACT_LRELU: hipLaunchKernelGGL((act_bwd_kernel<AGAN_ACT_LRELU>), dim3(blocks), dim3(256), 0, st, y, dout, dx, n); break;
@@ -776,14 +835,18 @@ int agan_act_bwd(const float* y, const float* dout, float* dx, size_t n, int act
 }
 
 int agan_glu_fwd(const float* x, float* out, int B, int C, int HW, void* stream) {
+    log_reset();
     AGAN_REQUIRE(x && out && B > 0 && C > 0 && HW > 0, "glu_fwd: bad argument");
     AGAN_REQUIRE(C % 2 == 0, "channels dont divide 2!");
+    log_launch(kLogGluFwd, AGAN_ACT_GLU, AGAN_DT_F32, AGAN_DT_F32, 1);
     hipLaunchKernelGGL(glu_fwd_kernel, dim3(ew_blocks((size_t)B * (C / 2) * HW)), dim3(256), 0, as_stream(stream), x, out, B, C, HW);
     return check_launch("glu_fwd");
 }
 
 int agan_glu_bwd(const float* x, const float* dout, float* dx, int B, int C, int HW, void* stream) {
+    log_reset();
     AGAN_REQUIRE(x && dout && dx && B > 0 && C > 0 && HW > 0 && C % 2 == 0, "glu_bwd: bad argument");
+    log_launch(kLogGluBwd, AGAN_ACT_GLU, AGAN_DT_F32, AGAN_DT_F32, 1);
     hipLaunchKernelGGL(glu_bwd_kernel, dim3(ew_blocks((size_t)B * (C / 2) * HW)), dim3(256), 0, as_stream(stream), x, dout, dx, B, C, HW);
     return check_launch("glu_bwd");
 }
@@ -797,6 +860,7 @@ int agan_bn_train_fwd_dt(const void* x, const float* gamma, const float* beta, c
                          float* invstd, float* running_mean, float* running_var, int64_t* nbt, int B, int C, int HW, float eps,
                          float momentum, int act, int groups, void* ws, size_t ws_bytes, void* stream, float* out_amax, int x_dtype,
                          int out_dtype) {
+    log_reset();
     AGAN_REQUIRE(x && gamma && beta && out && mean && invstd && B > 0 && C > 0 && HW > 0, "bn_train_fwd: bad argument");
     AGAN_REQUIRE(act == AGAN_ACT_NONE || act == AGAN_ACT_GLU || act == AGAN_ACT_LRELU, "bn_train_fwd: activation %d", act);
     AGAN_REQUIRE(act != AGAN_ACT_GLU || (C % 2 == 0), "channels dont divide 2!");
@@ -816,7 +880,7 @@ int agan_bn_train_fwd_dt(const void* x, const float* gamma, const float* beta, c
             void* og = off(out, (size_t)gi * Bg * Co * HW, out_dtype);
             float* mg = mean + (size_t)gi * C;
             float* ig = invstd + (size_t)gi * C;
-#define AGAN_LP(A, XD, OD, P) hipLaunchKernelGGL((bn_small_fwd_kernel<A, XD, OD, P>), dim3(Co), dim3(256), 0, st, xg, gamma, beta, rg, og, mg, ig, running_mean, running_var, nbt, Bg, C, HW, eps, momentum, out_amax)
+#define AGAN_LP(A, XD, OD, P) do { log_launch(kLogSmallFwd, A, XD, OD, P); hipLaunchKernelGGL((bn_small_fwd_kernel<A, XD, OD, P>), dim3(Co), dim3(256), 0, st, xg, gamma, beta, rg, og, mg, ig, running_mean, running_var, nbt, Bg, C, HW, eps, momentum, out_amax); } while (0)
 #define AGAN_L(A, XD, OD) do { if (Bg * HW <= 512) AGAN_LP(A, XD, OD, 2); else if (Bg * HW <= 2048) AGAN_LP(A, XD, OD, 8); else AGAN_LP(A, XD, OD, kSmallPer); } while (0)
 #define AGAN_C(XD, OD)                                           \
     if (act == AGAN_ACT_GLU) AGAN_L(AGAN_ACT_GLU, XD, OD);       \
@@ -833,8 +897,8 @@ int agan_bn_train_fwd_dt(const void* x, const float* gamma, const float* beta, c
         const void* xg = off(x, (size_t)gi * Bg * C * HW, x_dtype);
         float* mg = mean + (size_t)gi * C;
         float* ig = invstd + (size_t)gi * C;
-        if (int e = agan_bn_stats_dt(xg, Bg, C, HW, eps, mg, ig, running_mean, running_var, nbt, momentum, ws, ws_bytes, stream, x_dtype)) return e;
-        if (int e = agan_bn_act_fwd_dt(xg, mg, ig, gamma, beta, residual ? off(residual, (size_t)gi * Bg * Co * HW, out_dtype) : nullptr,
+        if (int e = bn_stats_impl(xg, Bg, C, HW, eps, mg, ig, running_mean, running_var, nbt, momentum, ws, ws_bytes, stream, x_dtype)) return e;
+        if (int e = bn_act_fwd_impl(xg, mg, ig, gamma, beta, residual ? off(residual, (size_t)gi * Bg * Co * HW, out_dtype) : nullptr,
                                        off(out, (size_t)gi * Bg * Co * HW, out_dtype), Bg, C, HW, act, stream, out_amax, x_dtype, out_dtype))
             return e;
     }

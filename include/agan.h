@@ -236,6 +236,14 @@ int agan_act_bwd(const float* out, const float* dout, float* dx, size_t n, int a
 /* standalone GLU over channel halves of [B,C,HW] (utilities/layers.py:13-26; the CA-net's "relu", generator_submodules.py:153) */
 int agan_glu_fwd(const float* x, float* out, int B, int C, int HW, void* stream);
 int agan_glu_bwd(const float* x, const float* dout, float* dx, int B, int C, int HW, void* stream);
+/* Launch log of the calling thread's last agan_bn_* / agan_act_* / agan_glu_* call (tests): one code per kernel launch, in launch
+ * order, code = kind*100000 + act*10000 + x_dtype*1000 + out_dtype*100 + width.  kind: 1 statistics partial sums, 2 statistics
+ * final, 3 statistics of [B, C] rows, 4 forward apply, 5 one-launch small forward, 6 one-launch small backward, 7 backward partial
+ * sums, 8 backward final, 9 backward apply, 10 / 11 bare activation forward / backward, 12 / 13 GLU forward / backward.  width: the
+ * values per thread and loop step of the sweeping kernels (1, 4, 8), the values per thread of the small kernels (2, 8, 32), else 1
+ * (4 for the bare activations).  For the statistics kernels out_dtype repeats x_dtype.  Copies up to `capacity` codes into
+ * codes[] and returns how many launches the call made. */
+int agan_bn_last_launch(int* codes, int capacity);
 
 /* ------------------------------------------------------------------------------------------------
  * Word-context attention: AttentionModule.forward, networks/attention.py:25-79

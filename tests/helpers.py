@@ -86,7 +86,7 @@ def collect_from_children(q, procs, n=None, timeout=300.0, poll=0.5):
 
 
 class LeakyMaskRecorder:
-    """Records, in call order, the branch every LeakyReLU of the HIP path took (sign of its output), per discriminator call.
+    """Records, in call order, the branch every LeakyReLU of the HIP path took (output > 0: slope 1, else the slope: torch's rule at exactly 0), per discriminator call.
 
     `with LeakyMaskRecorder(discriminators) as rec:` ... run the HIP step ...; `rec.calls` is then a list of
     (discriminator index, batch size, [bool mask per LeakyReLU layer, CPU]) in the order the discriminators were called.
@@ -109,13 +109,13 @@ class LeakyMaskRecorder:
         def conv_fwd(mod, x, act=L.ACT_NONE, *a, **k):
             y = rec._conv(mod, x, act, *a, **k)
             if act == L.ACT_LRELU and rec._cur is not None:
-                rec._cur.append((y.detach() >= 0).cpu())
+                rec._cur.append((y.detach() > 0).cpu())
             return y
 
         def bn_fused(mod, x, act, residual=None):
             y = rec._fused(mod, x, act, residual)
             if act == L.ACT_LRELU and rec._cur is not None:
-                rec._cur.append((y.detach() >= 0).cpu())
+                rec._cur.append((y.detach() > 0).cpu())
             return y
 
         LAY.HipConv2d.forward, LAY._BNState.fused = conv_fwd, bn_fused

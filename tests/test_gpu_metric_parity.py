@@ -17,7 +17,7 @@ evaluation and 0.2 in another, and that one element moves every upstream gradien
 fp32 oracle against the fp64 oracle just as in HIP against either (measured).  The test therefore records
 the branch each LeakyReLU of the HIP step took and lets the oracle differentiate the SAME branch (oracle.LEAKY_MASKS), so what
 is compared at 1e-3 is the arithmetic of the kernels, not the coin flips of a measure-zero set.  The synchronisation is BOUNDED:
-the oracle also evaluates its own `x >= 0` in every LeakyReLU call, and the test asserts (oracle.check_leaky_stats) that the
+the oracle also evaluates its own `x > 0` in every LeakyReLU call, and the test asserts (oracle.check_leaky_stats) that the
 imposed branches differ from the oracle's own on at most a KINK_MAX_FRAC fraction of a call's elements, each with a
 pre-activation within KINK_MAX_REL of the tensor's maximum.  A disagreement at an element x means the HIP pre-activation is at
 least |x| away from the oracle's, so KINK_MAX_REL is a FORWARD-parity bound at every LeakyReLU input (kept below RTOL): a kernel

@@ -719,7 +719,7 @@ def test_paired_discriminator_pass_at_metric_size():
             assert not O.LEAKY_MASKS
         finally:
             O.LEAKY_MASKS = O.LEAKY_STATS = None
-        # the imposed branches may differ from the oracle's own x >= 0 only on a few elements within rounding of zero
+        # the imposed branches may differ from the oracle's own x > 0 only on a few elements within rounding of zero
         print(O.check_leaky_stats(stats, 1e-5, 1e-5, f"kink sync {form} {str(dt)[6:]}"))      # observed: 20 of 1e8, |x| <= 1.1e-6 max|x|
         return loss.detach(), dict(zip(keys, torch.autograd.grad(loss, [p[k] for k in keys]))), p
     ref = {form: (oracle(torch.float32, form), oracle(torch.float64, form)) for form in queues}
