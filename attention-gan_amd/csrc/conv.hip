@@ -438,8 +438,7 @@ __global__ __launch_bounds__(256) void sum_slabs_few_kernel_t(const float* __res
 template <int ODT>
 void launch_sum_slabs_t(const float* ws, int nsplit, size_t n, size_t slab, const float* bias, int C, int HW, void* out, int accumulate,
                         int act, const void* lrelu_mask, float* amax, hipStream_t st) {
-    static const bool few_off = getenv("AGAN_SUM_FEW_OFF") != nullptr;          // (A/B switch)
-    if (nsplit <= 8 && !few_off) {
+    if (nsplit <= 8) {
         const int blocks = (int)std::min<size_t>(cdivz(n / 4 + 1, 256), 32768);
         AGAN_LAUNCH(sum_slabs_few_kernel_t<ODT>, dim3(blocks), dim3(256), 0, st, ws, nsplit, n, slab, bias, C, HW, out, accumulate, act,
                     lrelu_mask, amax);
@@ -874,6 +873,172 @@ static inline void timer_end(hipStream_t st, int split) {
 }
 
 // ================================================================================================
+// routing: the one place that decides which kernel a conv call runs on
+// ================================================================================================
+// route_gather / route_wgrad apply the rules below in order and return the first path that takes the call, with its plan.  Every query
+// of the C ABI (effective mode, 16-bit storage, workspace, Winograd fraction) reads a route, and the two executors launch one, so a new
+// kernel is one more rule here.  The measured thresholds live in the plan_* functions.
+static bool dt16(int dt) { return dt == AGAN_DT_BF16 || dt == AGAN_DT_F16; }
+// the 16-bit storage type that goes with a one-plane mode (AGAN_DT_F32: none)
+static int mode_dtype(int mode) { return mode == AGAN_PREC_BF16 ? AGAN_DT_BF16 : (mode == AGAN_PREC_F16 ? AGAN_DT_F16 : AGAN_DT_F32); }
+
+enum class GatherPath { none, p16, patch, winograd, small_n, direct };
+struct GatherRoute {
+    int mode = AGAN_PREC_F32;           // the precision mode the call runs in (agan_conv_effective_prec)
+    GatherPath path = GatherPath::none;
+    P16Plan p16{};                      // the plan of the path (the others stay zero)
+    PatchPlan pp{};
+    PatchGather patch{};
+    WinoPlan wino{};
+    GatherPlan direct{};
+    size_t ws_bytes = 0;                // workspace the path needs
+    int split = 1;                      // partial-sum slabs its main kernel writes (1: the result itself)
+};
+
+// epilogue: the call carries a bias, an activation or a LeakyReLU mask
+static GatherRoute route_gather(const agan_conv_geom* gg, int prec, int in_dtype, int out_dtype, bool epilogue) {
+    GatherRoute r;
+    auto take = [&r](GatherPath path, size_t ws_bytes, int split) {
+        r.path = path;
+        r.ws_bytes = ws_bytes;
+        r.split = split;
+        return r;
+    };
+    if (check_geom(gg)) return r;
+    const Geom g = make_geom(gg);
+    // the 16-bit modes hold where the patch kernels take the geometry; every other call runs in fp32
+    if (prec_planes(prec) > 0 && patch_supported(g)) r.mode = prec;
+    const bool f32io = in_dtype == AGAN_DT_F32 && out_dtype == AGAN_DT_F32;
+    // 1. one-plane modes: the row-block gather (conv_p16.hip), fp32 or the mode's 16-bit storage on either side
+    if (const int want = mode_dtype(r.mode)) {
+        if ((in_dtype == AGAN_DT_F32 || in_dtype == want) && (out_dtype == AGAN_DT_F32 || out_dtype == want)) {
+            r.p16 = plan_p16(g, in_dtype != AGAN_DT_F32);
+            if (r.p16.ok) return take(GatherPath::p16, r.p16.ws_bytes, r.p16.ksplit);
+        }
+    }
+    // 2. every other 16-bit-mode call: the patch-resident gather (conv_patch.hip), fp32 storage
+    if (r.mode != AGAN_PREC_F32) {
+        if (!f32io) return r;
+        r.pp = make_patch_plan(g);
+        r.patch = plan_patch_gather(g, r.pp);
+        return take(GatherPath::patch, r.patch.ws_bytes, r.patch.ksplit);
+    }
+    // 3. fp32 conv3x3 stride 1 / conv4x4 stride 2 on enough pixels, no epilogue: Winograd (conv_wino.hip)
+    if (f32io && !epilogue) {
+        r.wino = plan_wino(g);
+        if (r.wino.ok) return take(GatherPath::winograd, r.wino.ws_bytes, r.wino.ksplit);
+    }
+    // 4. <= 4 output channels on the vector ALU (conv_small.hip): fp32 or 16-bit input (the linear-layer kernel: fp32), fp32 output
+    if (small_n_gather_supported(g)) {
+        const bool linear = g.RS == 1 && g.IH == 1 && g.IW == 1;
+        if ((in_dtype == AGAN_DT_F32 || (dt16(in_dtype) && !linear)) && out_dtype == AGAN_DT_F32) return take(GatherPath::small_n, 0, 1);
+        return r;
+    }
+    // 5. the k-table MFMA kernel above: fp32 input, fp32 or 16-bit output
+    if (in_dtype == AGAN_DT_F32 && (out_dtype == AGAN_DT_F32 || dt16(out_dtype))) {
+        r.direct = plan_gather(g, AGAN_PREC_F32);
+        return take(GatherPath::direct, r.direct.ws_bytes, r.direct.ksplit);
+    }
+    return r;
+}
+
+enum class WgradPath { none, winograd, rows, patch, small_n, direct };
+struct WgradRoute {
+    int mode = AGAN_PREC_F32;           // the precision mode the call runs in (agan_conv_wgrad_effective_prec)
+    WgradPath path = WgradPath::none;
+    WinoWgradPlan wino{};               // the plan of the path (the others stay zero)
+    RowsPlan rows{};
+    PatchPlan pp{};
+    PatchWgrad patch{};
+    SmallWgradPlan small{};
+    WgradPlan direct{};
+    size_t ws_bytes = 0;
+    int split = 1;
+};
+
+// g: the FORWARD geometry
+static WgradRoute route_wgrad(const agan_conv_geom* gg, int pack_mode, int prec, int x_dtype, int dy_dtype) {
+    WgradRoute r;
+    auto take = [&r](WgradPath path, size_t ws_bytes, int split) {
+        r.path = path;
+        r.ws_bytes = ws_bytes;
+        r.split = split;
+        return r;
+    };
+    if (check_geom(gg)) return r;
+    const Geom g = make_geom(gg);
+    const bool up = pack_mode == AGAN_PACK_UP_FWD, x16 = x_dtype != AGAN_DT_F32, y16 = dy_dtype != AGAN_DT_F32;
+    // The mode.  Besides the geometries the patch kernels do not take:
+    //   * AGAN_PREC_BF16X6 -- fp32-grade by definition, so it may use whichever fp32-grade kernel is fastest.  Its own six-product patch
+    //     kernel is not (three planes of two tensors: 10 vs 6.5 ms per step against the fp32 MFMA kernel; -DAGAN_BF16X6_PATCH_WGRAD=1
+    //     builds it in).  Round 3: the two-plane fp16 split (AGAN_PREC_F16X3: 22-bit products, the same full-size parity) is 1.35-2.2x
+    //     faster than the fp32 kernel on every layer, so bf16x6 weight gradients run there -- the caller supplies the amax slots of x
+    //     and dy exactly as in AGAN_PREC_F16X3;
+    //   * the folded upsample conv (4 classes of 2x2 taps) keeps its mode only where the row-resident kernel takes it as the conv3x3 on
+    //     the upsampled image it is (conv_wgrows.hip): the patch weight gradient of the folded form is slower than the fp32 kernel in
+    //     EVERY mode (0.61 / 0.52 vs 0.49 ms at 64x128 -> 64x256; 16 short reductions per tile) -- fp32 products are at least as accurate.
+    if (prec_planes(prec) > 0 && patch_supported(g)) {
+        r.mode = prec;
+#ifndef AGAN_BF16X6_PATCH_WGRAD
+        if (prec == AGAN_PREC_BF16X6) r.mode = AGAN_PREC_F16X3;
+#endif
+        if (up && !plan_rows_wgrad(g, r.mode, false, false, true).ok) r.mode = AGAN_PREC_F32;
+    }
+    // 16-bit storage: a 16-bit x into the <= 4-output-channel fp32 kernel, or the one-plane modes' own type on either side
+    if (x16 || y16) {
+        const int want = mode_dtype(r.mode);
+        const bool ok = r.mode == AGAN_PREC_F32
+                            ? pack_mode == AGAN_PACK_FWD && small_n_wgrad_supported(g) && dt16(x_dtype) && !y16
+                            : want != AGAN_DT_F32 && (!x16 || x_dtype == want) && (!y16 || dy_dtype == want);
+        if (!ok) return r;
+    }
+    // 1. fp32 conv3x3 stride 1 on enough pixels: Winograd F(3x3, 2x2) (conv_wino.hip)
+    if (r.mode == AGAN_PREC_F32 && !up && !x16 && !y16) {
+        r.wino = plan_wino_wgrad(g);
+        if (r.wino.ok) return take(WgradPath::winograd, r.wino.ws_bytes, r.wino.psplit);
+    }
+    // 2. the row-resident kernel (conv_wgrows.hip) where it takes the geometry, any mode
+    if (!(r.mode == AGAN_PREC_F32 && small_n_wgrad_supported(g))) {
+        r.rows = plan_rows_wgrad(g, r.mode, x16, y16, up);
+        if (r.rows.ok) return take(WgradPath::rows, r.rows.ws_bytes, r.rows.psplit);
+    }
+    // 3. every other 16-bit-mode call: the patch-resident weight gradient (conv_patch.hip)
+    if (r.mode != AGAN_PREC_F32) {
+        r.pp = make_patch_plan(g);
+        r.patch = plan_patch_wgrad(g, r.pp, r.mode);
+        return take(WgradPath::patch, r.patch.ws_bytes, r.patch.psplit);
+    }
+    // 4. <= 4 output channels on the vector ALU (conv_small.hip)
+    if (!up && small_n_wgrad_supported(g)) {
+        r.small = plan_wgrad_small_n(g);
+        return take(WgradPath::small_n, r.small.ws_bytes, r.small.nchunk);
+    }
+    // 5. the k-table MFMA kernel above
+    if (!x16 && !y16) {
+        r.direct = plan_wgrad(g, up);
+        return take(WgradPath::direct, r.direct.ws_bytes, r.direct.psplit);
+    }
+    return r;
+}
+
+static int check_ws(const char* who, size_t need, const void* ws, size_t ws_bytes) {
+    if (need > ws_bytes || (need && !ws)) {
+        set_error("%s: workspace %zu < %zu", who, ws_bytes, need);
+        return AGAN_EWORKSPACE;
+    }
+    return AGAN_OK;
+}
+
+// the main kernel of a routed call, bracketed by the measurement hook
+template <class Launch>
+static int launch_main(hipStream_t st, int split, const char* what, Launch&& launch) {
+    timer_begin(st);
+    launch();
+    timer_end(st, split);
+    return check_launch(what);
+}
+
+// ================================================================================================
 // C ABI
 // ================================================================================================
 extern "C" {
@@ -971,63 +1136,29 @@ int agan_pack_weights(const agan_pack_job* jobs, int njobs, int total_blocks, in
     return check_launch("pack_weights");
 }
 
-int agan_conv_effective_prec(const agan_conv_geom* g, int prec) {
-    if (prec == AGAN_PREC_F32 || check_geom(g)) return AGAN_PREC_F32;
-    if (prec_planes(prec) == 0) return AGAN_PREC_F32;
-    return patch_supported(make_geom(g)) ? prec : AGAN_PREC_F32;
-}
+int agan_conv_effective_prec(const agan_conv_geom* g, int prec) { return route_gather(g, prec, AGAN_DT_F32, AGAN_DT_F32, false).mode; }
 
-// the mode a weight gradient of forward geometry g runs in.  Besides the geometries the patch kernels do not take:
-//   * AGAN_PREC_BF16X6 -- fp32-grade by definition, so it may use whichever fp32-grade kernel is fastest.  Its own six-product patch
-//     kernel is not (three planes of two tensors: 10 vs 6.5 ms per step against the fp32 MFMA kernel; -DAGAN_BF16X6_PATCH_WGRAD=1
-//     builds it in).  Round 3: the two-plane fp16 split (AGAN_PREC_F16X3: 22-bit products, the same full-size parity) is 1.35-2.2x
-//     faster than the fp32 kernel on every layer, so bf16x6 weight gradients run there -- the caller supplies the amax slots of x
-//     and dy exactly as in AGAN_PREC_F16X3 (AGAN_BF16X6_WGRAD_F32=1 in the environment restores the fp32 kernel);
-//   * the folded upsample conv (4 classes of 2x2 taps): its patch weight gradient is slower than the fp32 kernel in EVERY mode
-//     (0.61 / 0.52 vs 0.49 ms at 64x128 -> 64x256; 16 short reductions per tile) -- fp32 products are at least as accurate.
 int agan_conv_wgrad_effective_prec(const agan_conv_geom* g, int pack_mode, int prec) {
-    if (prec == AGAN_PREC_F32 || check_geom(g) || prec_planes(prec) == 0) return AGAN_PREC_F32;
-    if (!patch_supported(make_geom(g))) return AGAN_PREC_F32;
-#ifndef AGAN_BF16X6_PATCH_WGRAD
-    if (prec == AGAN_PREC_BF16X6) {
-        static const bool f32wg = getenv("AGAN_BF16X6_WGRAD_F32") != nullptr;
-        prec = f32wg ? AGAN_PREC_F32 : AGAN_PREC_F16X3;
-    }
-#endif
-    // (round 3: the row-resident kernel takes the upsample conv as the conv3x3 on the upsampled image it is -- conv_wgrows.hip)
-    if (pack_mode == AGAN_PACK_UP_FWD && (prec == AGAN_PREC_F32 || !plan_rows_wgrad(make_geom(g), prec, false, false, true).ok)) return AGAN_PREC_F32;
-    return prec;
+    return route_wgrad(g, pack_mode, prec, AGAN_DT_F32, AGAN_DT_F32).mode;
 }
 
 double agan_conv_executed_fraction(const agan_conv_geom* g, int prec, int wgrad, int plain_epilogue) {
-    if (check_geom(g) || prec != AGAN_PREC_F32) return 1.0;
-    const Geom gg = make_geom(g);
-    if (wgrad) return plan_wino_wgrad(gg).ok ? 16.0 / 36.0 : 1.0;
-    if (!plain_epilogue) return 1.0;
-    const WinoPlan wp = plan_wino(gg);
-    if (!wp.ok) return 1.0;
-    return wp.s2 == 0 ? 16.0 / 36.0 : (wp.s2 == 1 ? 36.0 / 64.0 : 9.0 / 16.0);
+    if (prec != AGAN_PREC_F32) return 1.0;
+    if (wgrad)      // (Winograd takes the weight gradients of conv3x3 stride 1 only: AGAN_PACK_FWD)
+        return route_wgrad(g, AGAN_PACK_FWD, prec, AGAN_DT_F32, AGAN_DT_F32).path == WgradPath::winograd ? 16.0 / 36.0 : 1.0;
+    const GatherRoute r = route_gather(g, prec, AGAN_DT_F32, AGAN_DT_F32, !plain_epilogue);
+    if (r.path != GatherPath::winograd) return 1.0;
+    return r.wino.s2 == 0 ? 16.0 / 36.0 : (r.wino.s2 == 1 ? 36.0 / 64.0 : 9.0 / 16.0);
 }
 
+static const int kDtypes[] = {AGAN_DT_F32, AGAN_DT_BF16, AGAN_DT_F16};
+
 size_t agan_conv_gather_ws_bytes(const agan_conv_geom* g, int prec) {
-    if (check_geom(g)) return 0;
-    const Geom gg = make_geom(g);
-    prec = agan_conv_effective_prec(g, prec);
-    if (prec == AGAN_PREC_F32 && small_n_gather_supported(gg)) return 0;
-    if (prec == AGAN_PREC_F32) {
-        const WinoPlan wp = plan_wino(gg);
-        if (wp.ok) return std::max(wp.ws_bytes, plan_gather(gg, prec).ws_bytes);      // (a call with a bias / activation epilogue takes the direct kernel)
-    }
-    if (prec != AGAN_PREC_F32) {
-        size_t a = plan_patch_gather(gg, make_patch_plan(gg)).ws_bytes;
-        if (prec == AGAN_PREC_BF16 || prec == AGAN_PREC_F16)          // the row-block gather may split differently (either storage type)
-            for (int in16 = 0; in16 < 2; ++in16) {
-                const P16Plan p = plan_p16(gg, in16 != 0);
-                if (p.ok) a = std::max(a, p.ws_bytes);
-            }
-        return a;
-    }
-    return plan_gather(gg, prec).ws_bytes;
+    size_t a = 0;
+    for (int in_dtype : kDtypes)
+        for (int out_dtype : kDtypes)
+            for (int epilogue = 0; epilogue < 2; ++epilogue) a = std::max(a, route_gather(g, prec, in_dtype, out_dtype, epilogue != 0).ws_bytes);
+    return a;
 }
 
 size_t agan_conv_ktable_elems(const agan_conv_geom* g) {
@@ -1045,145 +1176,76 @@ int agan_conv_ktable(const agan_conv_geom* gg, int32_t* table, void* stream) {
     return check_launch("conv_ktable");
 }
 
-// does the row-block gather (conv_p16.hip) take this call?  (one-plane 16-bit modes; AGAN_P16_OFF=1 keeps fp32-storage calls on
-// the patch-resident kernel for A/B measurements)
-static bool p16_takes(const Geom& g, int prec, int in_dtype, int out_dtype, P16Plan* plan) {
-    if (prec != AGAN_PREC_BF16 && prec != AGAN_PREC_F16) return false;
-    const int want = prec == AGAN_PREC_BF16 ? AGAN_DT_BF16 : AGAN_DT_F16;
-    if ((in_dtype != AGAN_DT_F32 && in_dtype != want) || (out_dtype != AGAN_DT_F32 && out_dtype != want)) return false;
-    static const bool off = getenv("AGAN_P16_OFF") != nullptr;
-    if (off && in_dtype == AGAN_DT_F32 && out_dtype == AGAN_DT_F32) return false;
-    const P16Plan p = plan_p16(g, in_dtype != AGAN_DT_F32);
-    if (plan) *plan = p;
-    return p.ok != 0;
-}
-
-static bool dt16(int dt) { return dt == AGAN_DT_BF16 || dt == AGAN_DT_F16; }
-// the fp32-arithmetic kernels with typed storage: the <= 4-output-channel kernels read a 16-bit input (fp32 output), the k-table
-// MFMA kernels write a 16-bit output (fp32 input)
-static bool f32_kernel_takes(const Geom& g, const agan_conv_geom* gg, int prec, int in_dtype, int out_dtype) {
-    if (agan_conv_effective_prec(gg, prec) != AGAN_PREC_F32) return false;
-    if (small_n_gather_supported(g)) return (in_dtype == AGAN_DT_F32 || dt16(in_dtype)) && out_dtype == AGAN_DT_F32 && !(g.RS == 1 && g.IH == 1 && g.IW == 1 && in_dtype != AGAN_DT_F32);
-    return in_dtype == AGAN_DT_F32 && (out_dtype == AGAN_DT_F32 || dt16(out_dtype));
-}
-
 int agan_conv_gather_dt_supported(const agan_conv_geom* gg, int prec, int in_dtype, int out_dtype) {
-    if (check_geom(gg)) return 0;
-    if (in_dtype == AGAN_DT_F32 && out_dtype == AGAN_DT_F32) return 1;
-    const Geom g = make_geom(gg);
-    if (p16_takes(g, prec, in_dtype, out_dtype, nullptr)) return 1;
-    return f32_kernel_takes(g, gg, agan_conv_effective_prec(gg, prec), in_dtype, out_dtype) ? 1 : 0;
+    return route_gather(gg, prec, in_dtype, out_dtype, false).path != GatherPath::none ? 1 : 0;
 }
 
 int agan_conv_gather_dt(const void* in_v, const void* wkv, const float* bias, void* out_v, const agan_conv_geom* gg, const int32_t* ktable,
                         int prec, int act, const void* lrelu_mask_v, void* ws, size_t ws_bytes, void* stream, const float* in_scale,
                         float* out_amax, int in_dtype, int out_dtype) {
-    const float* wk = static_cast<const float*>(wkv);
     if (int e = check_geom(gg)) return e;
-    AGAN_REQUIRE(in_v && wk && out_v && ktable, "conv_gather: null pointer");
+    AGAN_REQUIRE(in_v && wkv && out_v && ktable, "conv_gather: null pointer");
     AGAN_REQUIRE(act == AGAN_ACT_NONE || (act == AGAN_ACT_LRELU && gg->Cout > 4),
                  "conv_gather: fused activation %d not available for this call (MFMA paths, LeakyReLU only)", act);
     AGAN_REQUIRE(!lrelu_mask_v || (gg->Cout > 4 && act == AGAN_ACT_NONE),
                  "conv_gather: the LeakyReLU-derivative mask needs an MFMA path and no other activation");
-    const int2* ktab = reinterpret_cast<const int2*>(ktable);
     AGAN_REQUIRE(prec == AGAN_PREC_F32 || prec_planes(prec) > 0, "conv_gather: unknown precision mode %d", prec);
-    AGAN_REQUIRE(agan_conv_effective_prec(gg, prec) == prec,
+    const GatherRoute r = route_gather(gg, prec, in_dtype, out_dtype, bias || act != AGAN_ACT_NONE || lrelu_mask_v);
+    AGAN_REQUIRE(r.mode == prec,
                  "conv_gather: precision mode %d does not take this geometry (agan_conv_effective_prec says which one does)", prec);
-    const Geom g = make_geom(gg);
-    hipStream_t st = as_stream(stream);
-    {
-        P16Plan p16;
-        if (p16_takes(g, prec, in_dtype, out_dtype, &p16)) {
-            if (p16.ws_bytes > ws_bytes || (p16.ws_bytes && !ws)) {
-                set_error("conv_gather: workspace %zu < %zu", ws_bytes, p16.ws_bytes);
-                return AGAN_EWORKSPACE;
-            }
-            void* dst = p16.ksplit > 1 ? ws : out_v;
-            timer_begin(st);
-            launch_p16_gather(in_v, wkv, bias, dst, g, p16, prec, act, lrelu_mask_v, st, in_dtype != AGAN_DT_F32, out_dtype != AGAN_DT_F32);
-            timer_end(st, p16.ksplit);
-            if (int e = check_launch("conv_gather/p16")) return e;
-            if (p16.ksplit > 1) {
-                const size_t n = (size_t)g.B * g.Cout * g.OH * g.OW;
-                launch_sum_slabs(static_cast<const float*>(ws), p16.ksplit, n, p16.slab, bias, g.Cout, g.OH * g.OW, out_v, 0, act, lrelu_mask_v,
-                                 nullptr, st, out_dtype);
-                return check_launch("conv_gather/p16/sum_slabs");
-            }
-            return AGAN_OK;
-        }
-    }
-    AGAN_REQUIRE((in_dtype == AGAN_DT_F32 && out_dtype == AGAN_DT_F32) || f32_kernel_takes(g, gg, prec, in_dtype, out_dtype),
+    AGAN_REQUIRE(r.path != GatherPath::none,
                  "conv_gather: 16-bit activation storage (%d -> %d) is not available for this geometry / precision %d "
                  "(agan_conv_gather_dt_supported)", in_dtype, out_dtype, prec);
+    AGAN_REQUIRE(prec != AGAN_PREC_F16X3 || in_scale != nullptr, "conv_gather: AGAN_PREC_F16X3 needs the operand's agan_absmax_scale pair");
+    if (int e = check_ws("conv_gather", r.ws_bytes, ws, ws_bytes)) return e;
+    const Geom g = make_geom(gg);
+    hipStream_t st = as_stream(stream);
     const float* in = static_cast<const float*>(in_v);
-    float* out = static_cast<float*>(out_v);
+    const float* wk = static_cast<const float*>(wkv);
     const float* lrelu_mask = static_cast<const float*>(lrelu_mask_v);
-    if (prec != AGAN_PREC_F32) {
-        const PatchPlan pp = make_patch_plan(g);
-        const PatchGather p = plan_patch_gather(g, pp);
-        if (p.ws_bytes > ws_bytes || (p.ws_bytes && !ws)) {
-            set_error("conv_gather: workspace %zu < %zu", ws_bytes, p.ws_bytes);
-            return AGAN_EWORKSPACE;
-        }
-        float* dst = p.ksplit > 1 ? static_cast<float*>(ws) : out;
-        timer_begin(st);
-        AGAN_REQUIRE(prec != AGAN_PREC_F16X3 || in_scale != nullptr, "conv_gather: AGAN_PREC_F16X3 needs the operand's agan_absmax_scale pair");
-        launch_patch_gather(in, wkv, bias, dst, g, pp, p, prec, act, lrelu_mask, st, in_scale, out_amax);
-        timer_end(st, p.ksplit);
-        if (int e = check_launch("conv_gather/patch")) return e;
-        if (p.ksplit > 1) {
-            const size_t n = (size_t)g.B * g.Cout * g.OH * g.OW;
-            launch_sum_slabs(static_cast<const float*>(ws), p.ksplit, n, p.slab, bias, g.Cout, g.OH * g.OW, out, 0, act, lrelu_mask, out_amax, st);
-            return check_launch("conv_gather/sum_slabs");
-        }
-        return AGAN_OK;
-    }
-    if (prec == AGAN_PREC_F32 && in_dtype == AGAN_DT_F32 && out_dtype == AGAN_DT_F32 && !bias && act == AGAN_ACT_NONE && !lrelu_mask_v) {
-        // conv3x3 stride 1 (forward or data gradient) on enough pixels: Winograd F(2x2, 3x3), 2.25x fewer fp32 MFMAs (conv_wino.hip)
-        const WinoPlan wp = plan_wino(g);
-        if (wp.ok) {
-            if (wp.ws_bytes > ws_bytes || !ws) {
-                set_error("conv_gather: workspace %zu < %zu", ws_bytes, wp.ws_bytes);
-                return AGAN_EWORKSPACE;
-            }
-            timer_begin(st);
-            launch_wino(in, wk, out, g, wp, ws, st);
-            timer_end(st, wp.ksplit);
-            if (int e = check_launch("conv_gather/winograd")) return e;
-            if (wp.ksplit > 1) {
-                const size_t n = (size_t)g.B * g.Cout * g.OH * g.OW;
-                launch_sum_slabs(reinterpret_cast<const float*>(static_cast<const char*>(ws) + wp.u_bytes), wp.ksplit, n, wp.slab, nullptr,
-                                 g.Cout, g.OH * g.OW, out, 0, AGAN_ACT_NONE, nullptr, nullptr, st);
-                return check_launch("conv_gather/winograd/sum_slabs");
-            }
-            return AGAN_OK;
+    // a split launch writes partial slabs into the workspace (Winograd: behind its transformed weights); the slab sum adds the epilogue
+    void* dst = r.split > 1 ? ws : out_v;
+    const float* slabs = static_cast<const float*>(ws);
+    size_t slab = 0;
+    float* sum_amax = nullptr;
+    int e = AGAN_OK;
+    switch (r.path) {
+        case GatherPath::p16:
+            slab = r.p16.slab;
+            e = launch_main(st, r.split, "conv_gather/p16", [&] {
+                launch_p16_gather(in_v, wkv, bias, dst, g, r.p16, prec, act, lrelu_mask_v, st, in_dtype != AGAN_DT_F32, out_dtype != AGAN_DT_F32);
+            });
+            break;
+        case GatherPath::patch:
+            slab = r.patch.slab;
+            sum_amax = out_amax;
+            e = launch_main(st, r.split, "conv_gather/patch", [&] {
+                launch_patch_gather(in, wkv, bias, static_cast<float*>(dst), g, r.pp, r.patch, prec, act, lrelu_mask, st, in_scale, out_amax);
+            });
+            break;
+        case GatherPath::winograd:
+            slab = r.wino.slab;
+            slabs = reinterpret_cast<const float*>(static_cast<const char*>(ws) + r.wino.u_bytes);
+            e = launch_main(st, r.split, "conv_gather/winograd", [&] { launch_wino(in, wk, static_cast<float*>(out_v), g, r.wino, ws, st); });
+            break;
+        case GatherPath::small_n:
+            e = launch_main(st, r.split, "conv_gather/small_n", [&] { launch_gather_small_n(in_v, wk, bias, static_cast<float*>(out_v), g, st, in_dtype); });
+            break;
+        default: {
+            const GatherPlan& p = r.direct;
+            slab = p.slab;
+            const int2* ktab = reinterpret_cast<const int2*>(ktable);
+            e = launch_main(st, r.split, "conv_gather", [&] {
+                if (p.bn == 128) launch_gather<128, 2, 2>(in, wk, bias, dst, ktab, g, p, act, lrelu_mask_v, st, out_dtype);
+                else if (p.bn == 64) launch_gather<64, 2, 2>(in, wk, bias, dst, ktab, g, p, act, lrelu_mask_v, st, out_dtype);
+                else launch_gather<32, 4, 1>(in, wk, bias, dst, ktab, g, p, act, lrelu_mask_v, st, out_dtype);
+            });
         }
     }
-    if (prec == AGAN_PREC_F32 && small_n_gather_supported(g)) {
-        timer_begin(st);
-        launch_gather_small_n(in_v, wk, bias, out, g, st, in_dtype);
-        timer_end(st, 1);
-        return check_launch("conv_gather/small_n");
-    }
-    const GatherPlan p = plan_gather(g, prec);
-    if (p.ws_bytes > ws_bytes || (p.ws_bytes && !ws)) {
-        set_error("conv_gather: workspace %zu < %zu", ws_bytes, p.ws_bytes);
-        return AGAN_EWORKSPACE;
-    }
-    void* dst = p.ksplit > 1 ? ws : out_v;
-    timer_begin(st);
-    if (p.bn == 128) launch_gather<128, 2, 2>(in, wk, bias, dst, ktab, g, p, act, lrelu_mask_v, st, out_dtype);
-    else if (p.bn == 64) launch_gather<64, 2, 2>(in, wk, bias, dst, ktab, g, p, act, lrelu_mask_v, st, out_dtype);
-    else launch_gather<32, 4, 1>(in, wk, bias, dst, ktab, g, p, act, lrelu_mask_v, st, out_dtype);
-    timer_end(st, p.ksplit);
-    if (int e = check_launch("conv_gather")) return e;
-    if (p.ksplit > 1) {
-        const size_t n = (size_t)g.B * g.Cout * g.OH * g.OW;
-        launch_sum_slabs(static_cast<const float*>(ws), p.ksplit, n, p.slab, bias, g.Cout, g.OH * g.OW, out_v, 0, act, lrelu_mask_v, nullptr, st,
-                         out_dtype);
-        return check_launch("conv_gather/sum_slabs");
-    }
-    return AGAN_OK;
+    if (e || r.split == 1) return e;
+    launch_sum_slabs(slabs, r.split, (size_t)g.B * g.Cout * g.OH * g.OW, slab, bias, g.Cout, g.OH * g.OW, out_v, 0, act, lrelu_mask_v, sum_amax, st,
+                     out_dtype);
+    return check_launch("conv_gather/sum_slabs");
 }
 
 int agan_conv_gather(const float* in, const void* wkv, const float* bias, float* out, const agan_conv_geom* gg, const int32_t* ktable,
@@ -1193,43 +1255,20 @@ int agan_conv_gather(const float* in, const void* wkv, const float* bias, float*
                                AGAN_DT_F32, AGAN_DT_F32);
 }
 
+static const int kPrecs[] = {AGAN_PREC_F32, AGAN_PREC_BF16, AGAN_PREC_BF16X3, AGAN_PREC_F16, AGAN_PREC_BF16X6, AGAN_PREC_F16X3};
+
 size_t agan_conv_wgrad_ws_bytes(const agan_conv_geom* g) {
     if (check_geom(g)) return 0;
-    const Geom gg = make_geom(g);
-    // the larger of the two candidate paths (the small-N path is fp32-only; the caller does not pass the precision here)
-    size_t a = plan_wgrad(gg, g->OS == 2).ws_bytes;
-    if (small_n_wgrad_supported(gg)) a = std::max(a, plan_wgrad_small_n(gg).ws_bytes);
-    if (patch_supported(gg)) {
-        const PatchPlan pp = make_patch_plan(gg);
-        a = std::max({a, plan_patch_wgrad(gg, pp, AGAN_PREC_BF16).ws_bytes, plan_patch_wgrad(gg, pp, AGAN_PREC_BF16X6).ws_bytes});
-        for (int up = 0; up < 2; ++up) {     // (the plan's split does not depend on planes / storage; one plane: the most geometries)
-            const RowsPlan rp = plan_rows_wgrad(gg, AGAN_PREC_BF16, false, false, up != 0);
-            if (rp.ok) a = std::max(a, rp.ws_bytes);
-        }
-    }
-    {
-        const RowsPlan rp = plan_rows_wgrad(gg, AGAN_PREC_F32, false, false, false);
-        if (rp.ok) a = std::max(a, rp.ws_bytes);
-        const WinoWgradPlan wp = plan_wino_wgrad(gg);
-        if (wp.ok) a = std::max(a, wp.ws_bytes);
-    }
+    const int pack_mode = g->OS == 2 ? AGAN_PACK_UP_FWD : AGAN_PACK_FWD;
+    size_t a = 0;
+    for (int prec : kPrecs)
+        for (int x_dtype : kDtypes)
+            for (int dy_dtype : kDtypes) a = std::max(a, route_wgrad(g, pack_mode, prec, x_dtype, dy_dtype).ws_bytes);
     return a;
 }
 
-// 1 if agan_conv_wgrad_dt takes x / dy in these storage types for forward geometry g (both fp32: always; 16-bit: the one-plane patch
-// weight gradient in the matching mode)
 int agan_conv_wgrad_dt_supported(const agan_conv_geom* gg, int pack_mode, int prec, int x_dtype, int dy_dtype) {
-    if (check_geom(gg)) return 0;
-    if (x_dtype == AGAN_DT_F32 && dy_dtype == AGAN_DT_F32) return 1;
-    {   // the <= 4-output-channel weight gradient (RGB heads) reads a 16-bit x
-        const Geom g = make_geom(gg);
-        if (pack_mode == AGAN_PACK_FWD && small_n_wgrad_supported(g) && agan_conv_wgrad_effective_prec(gg, pack_mode, prec) == AGAN_PREC_F32)
-            return (dt16(x_dtype) && dy_dtype == AGAN_DT_F32) ? 1 : 0;
-    }
-    if (prec != AGAN_PREC_BF16 && prec != AGAN_PREC_F16) return 0;
-    const int want = prec == AGAN_PREC_BF16 ? AGAN_DT_BF16 : AGAN_DT_F16;
-    if ((x_dtype != AGAN_DT_F32 && x_dtype != want) || (dy_dtype != AGAN_DT_F32 && dy_dtype != want)) return 0;
-    return agan_conv_wgrad_effective_prec(gg, pack_mode, prec) == prec ? 1 : 0;
+    return route_wgrad(gg, pack_mode, prec, x_dtype, dy_dtype).path != WgradPath::none ? 1 : 0;
 }
 
 int agan_conv_wgrad(const float* x, const float* dy, float* dw, const agan_conv_geom* gg, const int32_t* ktable, int pack_mode,
@@ -1242,16 +1281,11 @@ int agan_conv_wgrad(const float* x, const float* dy, float* dw, const agan_conv_
 int agan_conv_wgrad_dt(const void* x_v, const void* dy_v, float* dw, const agan_conv_geom* gg, const int32_t* ktable, int pack_mode,
                        int kh, int kw, int prec, int accumulate, void* ws, size_t ws_bytes, void* stream, const float* x_scale,
                        const float* dy_scale, int x_dtype, int dy_dtype) {
-    AGAN_REQUIRE(agan_conv_wgrad_dt_supported(gg, pack_mode, prec, x_dtype, dy_dtype),
+    const WgradRoute r = route_wgrad(gg, pack_mode, prec, x_dtype, dy_dtype);
+    AGAN_REQUIRE(r.path != WgradPath::none,
                  "conv_wgrad: 16-bit activation storage (%d, %d) is not available for this geometry / precision %d", x_dtype, dy_dtype, prec);
-    const float* x = static_cast<const float*>(x_v);
-    const float* dy = static_cast<const float*>(dy_v);
-
-    if (int e = check_geom(gg)) return e;
-    AGAN_REQUIRE(x && dy && dw && ktable, "conv_wgrad: null pointer");
+    AGAN_REQUIRE(x_v && dy_v && dw && ktable, "conv_wgrad: null pointer");
     AGAN_REQUIRE(prec == AGAN_PREC_F32 || prec_planes(prec) > 0, "conv_wgrad: unknown precision mode %d", prec);
-    const int prec_asked = prec;
-    prec = agan_conv_wgrad_effective_prec(gg, pack_mode, prec);     // (callers may pass the mode that is set: fp32 operands either way)
     AGAN_REQUIRE(pack_mode == AGAN_PACK_FWD || pack_mode == AGAN_PACK_UP_FWD, "conv_wgrad: pack mode %d is not a forward mode", pack_mode);
     const Geom g = make_geom(gg);
     const bool up = pack_mode == AGAN_PACK_UP_FWD;
@@ -1259,134 +1293,85 @@ int agan_conv_wgrad_dt(const void* x_v, const void* dy_v, float* dw, const agan_
                  "conv_wgrad: tensor exceeds 2^29 elements");
     if (!up) AGAN_REQUIRE(g.R == kh && g.S == kw && g.OS == 1, "conv_wgrad: geometry is not a direct %dx%d conv", kh, kw);
     else AGAN_REQUIRE(g.R == 2 && g.S == 2 && g.OS == 2 && kh == 3 && kw == 3, "conv_wgrad: geometry is not the folded upsample conv");
+    AGAN_REQUIRE(r.mode != AGAN_PREC_F16X3 || (x_scale && dy_scale),
+                 "conv_wgrad: precision mode %d runs this weight gradient as AGAN_PREC_F16X3 (agan_conv_wgrad_effective_prec), which needs the "
+                 "amax slots of x and dy (x_amax / dy_amax)", prec);
+    if (int e = check_ws("conv_wgrad", r.ws_bytes, ws, ws_bytes)) return e;
     hipStream_t st = as_stream(stream);
-    if (prec == AGAN_PREC_F32 && !up && x_dtype == AGAN_DT_F32 && dy_dtype == AGAN_DT_F32) {
-        // conv3x3 stride 1 on enough pixels: Winograd F(3x3, 2x2), 2.25x fewer fp32 MFMAs (conv_wino.hip)
-        const WinoWgradPlan wp = plan_wino_wgrad(g);
-        if (wp.ok) {
-            if (wp.ws_bytes > ws_bytes || !ws) {
-                set_error("conv_wgrad: workspace %zu < %zu", ws_bytes, wp.ws_bytes);
-                return AGAN_EWORKSPACE;
-            }
-            float* wsf = static_cast<float*>(ws);
-            timer_begin(st);
-            launch_wino_wgrad(x, dy, wsf, g, wp, st);
-            timer_end(st, wp.psplit);
-            if (int e = check_launch("conv_wgrad/winograd")) return e;
-            launch_wino_wgrad_sum(wsf, g, wp, dw, accumulate ? 1 : 0, st);
-            return check_launch("conv_wgrad/winograd/sum");
-        }
-    }
-    if (!(prec == AGAN_PREC_F32 && small_n_wgrad_supported(g))) {
-        // the row-resident kernel (conv_wgrows.hip) where it takes the geometry (any mode, fp32 included): [cout][K'] slabs, its own pixel split
-        const RowsPlan rp = plan_rows_wgrad(g, prec, x_dtype != AGAN_DT_F32, dy_dtype != AGAN_DT_F32, up);
-        if (rp.ok) {
-            if (rp.ws_bytes > ws_bytes || !ws) {
-                set_error("conv_wgrad: workspace %zu < %zu", ws_bytes, rp.ws_bytes);
-                return AGAN_EWORKSPACE;
-            }
-            float* wsf = static_cast<float*>(ws);
-            AGAN_REQUIRE(prec != AGAN_PREC_F16X3 || (x_scale && dy_scale),
-                         "conv_wgrad: precision mode %d runs this weight gradient as AGAN_PREC_F16X3 (agan_conv_wgrad_effective_prec), which needs the "
-                         "amax slots of x and dy (x_amax / dy_amax)", prec_asked);
-            timer_begin(st);
-            launch_rows_wgrad(x_v, dy_v, wsf, g, rp, prec, st, x_scale, dy_scale, x_dtype != AGAN_DT_F32, dy_dtype != AGAN_DT_F32);
-            timer_end(st, rp.psplit);
-            if (int e = check_launch("conv_wgrad/rows")) return e;
-            // few slabs: summed inside the unpack pass; many (the small layers, split 100-fold over their pixels): the bandwidth-bound slab sum first
-            const float* src = wsf;
-            int nsl = rp.psplit;
-            if (rp.psplit > 4) {
-                float* reduced = wsf + rp.slab * rp.psplit;
-                const size_t n = (size_t)g.Cout * rp.Kp;
-                launch_sum_slabs(wsf, rp.psplit, n, rp.slab, nullptr, 1, 1, reduced, 0, AGAN_ACT_NONE, nullptr, nullptr, st);
-                if (int e = check_launch("conv_wgrad/sum_slabs")) return e;
-                src = reduced;
-                nsl = 1;
-            }
-            launch_wgrad_sum_unpack(src, nsl, rp.slab, dw, g.Cout, g.Cin, kh, kw, rp.NPH, rp.NT, rp.Kp, accumulate, st);      // (ups: a plain 3x3 result)
-            return check_launch("conv_wgrad/sum_unpack");
-        }
-    }
-    if (prec != AGAN_PREC_F32) {
-        const PatchPlan pp = make_patch_plan(g);
-        const PatchWgrad p = plan_patch_wgrad(g, pp, prec);
-        if (p.ws_bytes > ws_bytes || !ws) {
-            set_error("conv_wgrad: workspace %zu < %zu", ws_bytes, p.ws_bytes);
-            return AGAN_EWORKSPACE;
-        }
-        float* wsf = static_cast<float*>(ws);
-        float* reduced = p.psplit > 1 ? wsf + p.slab * p.psplit : wsf;
-        timer_begin(st);
-        AGAN_REQUIRE(prec != AGAN_PREC_F16X3 || (x_scale && dy_scale),
-                         "conv_wgrad: precision mode %d runs this weight gradient as AGAN_PREC_F16X3 (agan_conv_wgrad_effective_prec), which needs the "
-                         "amax slots of x and dy (x_amax / dy_amax)", prec_asked);
-        launch_patch_wgrad(x_v, dy_v, wsf, g, pp, p, prec, st, x_scale, dy_scale, x_dtype != AGAN_DT_F32, dy_dtype != AGAN_DT_F32);
-        timer_end(st, p.psplit);
-        if (int e = check_launch("conv_wgrad/patch")) return e;
-        if (!up && p.psplit <= 4) {
-            launch_wgrad_sum_unpack(wsf, p.psplit, p.slab, dw, g.Cout, g.Cin, kh, kw, pp.NPH, pp.NT, p.Kp, accumulate, st);
-            return check_launch("conv_wgrad/sum_unpack");
-        }
-        if (p.psplit > 1) {
-            const size_t n = (size_t)p.ncls * g.Cout * p.Kp;
-            launch_sum_slabs(wsf, p.psplit, n, p.slab, nullptr, 1, 1, reduced, 0, AGAN_ACT_NONE, nullptr, nullptr, st);
-            if (int e = check_launch("conv_wgrad/sum_slabs")) return e;
-        }
-        if (!up) launch_wgrad_sum_unpack(reduced, 1, p.slab, dw, g.Cout, g.Cin, kh, kw, pp.NPH, pp.NT, p.Kp, accumulate, st);
-        else launch_patch_wgrad_unpack(reduced, dw, g.Cout, g.Cin, kh, kw, up, pp, p, accumulate, st);
-        return check_launch("conv_wgrad/unpack");
-    }
-    if (prec == AGAN_PREC_F32 && !up && small_n_wgrad_supported(g)) {
-        const SmallWgradPlan sp = plan_wgrad_small_n(g);
-        if (sp.ws_bytes > ws_bytes || !ws) {
-            set_error("conv_wgrad: workspace %zu < %zu", ws_bytes, sp.ws_bytes);
-            return AGAN_EWORKSPACE;
-        }
-        float* part = static_cast<float*>(ws);
-        timer_begin(st);
-        launch_wgrad_small_n(x_v, dy, part, g, sp, st, x_dtype);
-        timer_end(st, sp.nchunk);
-        const size_t n = (size_t)g.Cout * g.K;
-        launch_sum_slabs(part, sp.nchunk, n, sp.slab, nullptr, 1, 1, dw, accumulate, AGAN_ACT_NONE, nullptr, nullptr, st);
-        return check_launch("conv_wgrad/small_n");
-    }
-    const WgradPlan p = plan_wgrad(g, up);
-    if (p.ws_bytes > ws_bytes || (p.ws_bytes && !ws)) {
-        set_error("conv_wgrad: workspace %zu < %zu", ws_bytes, p.ws_bytes);
-        return AGAN_EWORKSPACE;
-    }
-    const int2* ktab = reinterpret_cast<const int2*>(ktable);
+    const float* x = static_cast<const float*>(x_v);
+    const float* dy = static_cast<const float*>(dy_v);
     float* wsf = static_cast<float*>(ws);
-    // where the (reduced) [cls][cout][K] result lands: dw itself for a direct conv, a scratch slab before the tap combine.
-    // Under `accumulate` an unsplit direct conv also goes through one scratch slab so that the sum pass can add to dw.
-    // an unsplit direct conv accumulates in its own epilogue (f32 kernels); every other case goes through the slab sum
-    const int acc_in_kernel = (accumulate && !up && p.psplit == 1) ? 1 : 0;
-    const bool via_sum = p.psplit > 1 || (accumulate && !up && !acc_in_kernel);
-    float* reduced = up ? wsf + (p.psplit > 1 ? p.slab * p.psplit : 0) : dw;
-    float* part = via_sum ? wsf : reduced;
-    dim3 grid(p.itiles, p.jtiles, p.ncls * p.psplit);
+    const bool x16 = x_dtype != AGAN_DT_F32, y16 = dy_dtype != AGAN_DT_F32;
+    switch (r.path) {
+        case WgradPath::winograd:
+            if (int e = launch_main(st, r.split, "conv_wgrad/winograd", [&] { launch_wino_wgrad(x, dy, wsf, g, r.wino, st); })) return e;
+            launch_wino_wgrad_sum(wsf, g, r.wino, dw, accumulate ? 1 : 0, st);
+            return check_launch("conv_wgrad/winograd/sum");
+        case WgradPath::rows:
+        case WgradPath::patch: {
+            // [split][cls][cout][K'] slabs.  Few: summed inside the unpack pass; many (the small layers, split 100-fold over their pixels):
+            // the bandwidth-bound slab sum into the slab behind them first
+            const bool rows = r.path == WgradPath::rows;
+            int e;
+            if (rows) e = launch_main(st, r.split, "conv_wgrad/rows", [&] {
+                launch_rows_wgrad(x_v, dy_v, wsf, g, r.rows, r.mode, st, x_scale, dy_scale, x16, y16);
+            });
+            else e = launch_main(st, r.split, "conv_wgrad/patch", [&] {
+                launch_patch_wgrad(x_v, dy_v, wsf, g, r.pp, r.patch, r.mode, st, x_scale, dy_scale, x16, y16);
+            });
+            if (e) return e;
+            const size_t slab = rows ? r.rows.slab : r.patch.slab;
+            const int NPH = rows ? r.rows.NPH : r.pp.NPH, NT = rows ? r.rows.NT : r.pp.NT, Kp = rows ? r.rows.Kp : r.patch.Kp;
+            const int ncls = rows ? 1 : r.patch.ncls;      // (the row-resident kernel takes the upsample conv unfolded: a plain 3x3 result)
+            const bool unfold = up && !rows;
+            float* reduced = r.split > 1 ? wsf + slab * r.split : wsf;
+            const bool sum_first = unfold ? r.split > 1 : r.split > 4;
+            if (sum_first) {
+                launch_sum_slabs(wsf, r.split, (size_t)ncls * g.Cout * Kp, slab, nullptr, 1, 1, reduced, 0, AGAN_ACT_NONE, nullptr, nullptr, st);
+                if (int e2 = check_launch("conv_wgrad/sum_slabs")) return e2;
+            }
+            if (unfold) launch_patch_wgrad_unpack(reduced, dw, g.Cout, g.Cin, kh, kw, up, r.pp, r.patch, accumulate, st);
+            else launch_wgrad_sum_unpack(sum_first ? reduced : wsf, sum_first ? 1 : r.split, slab, dw, g.Cout, g.Cin, kh, kw, NPH, NT, Kp, accumulate, st);
+            return check_launch("conv_wgrad/unpack");
+        }
+        case WgradPath::small_n: {
+            if (int e = launch_main(st, r.split, "conv_wgrad/small_n", [&] { launch_wgrad_small_n(x_v, dy, wsf, g, r.small, st, x_dtype); })) return e;
+            launch_sum_slabs(wsf, r.split, (size_t)g.Cout * g.K, r.small.slab, nullptr, 1, 1, dw, accumulate, AGAN_ACT_NONE, nullptr, nullptr, st);
+            return check_launch("conv_wgrad/small_n/sum_slabs");
+        }
+        default: {
+            const WgradPlan& p = r.direct;
+            // where the (reduced) [cls][cout][K] result lands: dw itself for a direct conv, a scratch slab before the tap combine.
+            // An unsplit direct conv accumulates in its own epilogue; every other case goes through the slab sum.
+            const int acc_in_kernel = (accumulate && !up && p.psplit == 1) ? 1 : 0;
+            const bool via_sum = p.psplit > 1 || (accumulate && !up && !acc_in_kernel);
+            float* reduced = up ? wsf + (p.psplit > 1 ? p.slab * p.psplit : 0) : dw;
+            float* part = via_sum ? wsf : reduced;
+            const int2* ktab = reinterpret_cast<const int2*>(ktable);
+            dim3 grid(p.itiles, p.jtiles, p.ncls * p.psplit);
 #define AGAN_WG(BI, BJ) AGAN_LAUNCH((conv_wgrad_f32_kernel<BI, BJ>), grid, dim3(256), 0, st, x, dy, part, ktab, g, p.psplit, p.pchunk, p.slab, acc_in_kernel)
-    timer_begin(st);
-    if (p.bi == 128 && p.bj == 128) AGAN_WG(128, 128);
-    else if (p.bi == 128) AGAN_WG(128, 64);
-    else if (p.bj == 128) AGAN_WG(64, 128);
-    else AGAN_WG(64, 64);
-    timer_end(st, p.psplit);
+            const int e = launch_main(st, r.split, "conv_wgrad", [&] {
+                if (p.bi == 128 && p.bj == 128) AGAN_WG(128, 128);
+                else if (p.bi == 128) AGAN_WG(128, 64);
+                else if (p.bj == 128) AGAN_WG(64, 128);
+                else AGAN_WG(64, 64);
+            });
 #undef AGAN_WG
-    if (int e = check_launch("conv_wgrad")) return e;
-    const size_t n = (size_t)p.ncls * g.Cout * g.K;
-    if (via_sum) {
-        launch_sum_slabs(part, p.psplit, n, p.slab, nullptr, 1, 1, reduced, (accumulate && !up) ? 1 : 0, AGAN_ACT_NONE, nullptr, nullptr, st);
-        if (int e = check_launch("conv_wgrad/sum_slabs")) return e;
+            if (e) return e;
+            if (via_sum) {
+                launch_sum_slabs(part, p.psplit, (size_t)p.ncls * g.Cout * g.K, p.slab, nullptr, 1, 1, reduced, (accumulate && !up) ? 1 : 0,
+                                 AGAN_ACT_NONE, nullptr, nullptr, st);
+                if (int e2 = check_launch("conv_wgrad/sum_slabs")) return e2;
+            }
+            if (up) {
+                const size_t total = (size_t)g.Cout * g.Cin * 9;
+                AGAN_LAUNCH(unpack_wgrad_up_kernel, dim3((unsigned)std::min<size_t>(cdivz(total, 256), 4096)), dim3(256), 0, st,
+                            reduced, dw, g.Cout, g.Cin, accumulate);
+                return check_launch("conv_wgrad/unpack");
+            }
+            return AGAN_OK;
+        }
     }
-    if (up) {
-        const size_t total = (size_t)g.Cout * g.Cin * 9;
-        AGAN_LAUNCH(unpack_wgrad_up_kernel, dim3((unsigned)std::min<size_t>(cdivz(total, 256), 4096)), dim3(256), 0, st,
-                           reduced, dw, g.Cout, g.Cin, accumulate);
-        return check_launch("conv_wgrad/unpack");
-    }
-    return AGAN_OK;
 }
 
 int agan_bias_grad(const float* dy, float* dbias, int B, int C, int HW, int accumulate, void* stream) {

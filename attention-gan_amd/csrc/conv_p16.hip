@@ -641,8 +641,7 @@ static P16Plan plan_impl(const Geom& g, bool in16, bool allow_px2, int tile = 0)
     if (tile == 2 && g.Cout >= 224) { p.wc = 2; p.bn = 256; }
     if (p.wc == 1 && tile != 0) return plan_impl(g, in16, allow_px2, 0);
     // both column-parity classes of a stride-2 lattice in one workgroup (64 lattice points x 2): see the kernel's PX2
-    static const bool px2_off = getenv("AGAN_P16_PX2_OFF") != nullptr;
-    p.px2 = (p.wc == 1 && allow_px2 && p.gk == 1 && g.OS == 2 && p.bn >= 64 && g.OY1 >= g.OY0 && !px2_off) ? 1 : 0;
+    p.px2 = (p.wc == 1 && allow_px2 && p.gk == 1 && g.OS == 2 && p.bn >= 64 && g.OY1 >= g.OY0) ? 1 : 0;
     const int lp = p.px2 ? 6 : (tile == 1 ? 8 : 7);
     p.lp = lp;
     p.twl = std::min(5, pow2ceil_log_(g.OWs));

@@ -1110,8 +1110,7 @@ static bool wg_block16_ok(const Geom& g, const PatchPlan& pp) {
     const int spanx = pp.IS * (pp.PW - 1) + 1;
     const int nxb = (7 + spanx + 7) / 8;
     const int tb = 128 >> (pp.twl + pp.thl);
-    static const bool off = getenv("AGAN_WG_B16_OFF") != nullptr;
-    return !off && (kCH / 8) * tb * pp.PH * nxb <= 256;
+    return (kCH / 8) * tb * pp.PH * nxb <= 256;
 }
 template <int ET, int BJ>
 void launch_wg_b16(const void* x, const void* dy, float* part, const Geom& g, const PatchPlan& pp, const PatchWgrad& p, hipStream_t st) {

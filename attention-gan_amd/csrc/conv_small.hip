@@ -568,13 +568,11 @@ __global__ __launch_bounds__(256) void wgrad_small_strip_kernel(const void* __re
 
 // the row-strip kernels take a 3x3 / stride 1 / pad 1 layer on whole 4-pixel blocks
 bool strip_ok(const Geom& g) {
-    static const bool off = getenv("AGAN_SMALL_STRIP_OFF") != nullptr;
-    return !off && g.RS == 9 && g.S == 3 && g.OS == 1 && g.SY == 1 && g.DY == 1 && g.OY0 == -1 && g.IH == g.OH && g.IW == g.OW && (g.IW & 3) == 0 && g.Cout <= 4;
+    return g.RS == 9 && g.S == 3 && g.OS == 1 && g.SY == 1 && g.DY == 1 && g.OY0 == -1 && g.IH == g.OH && g.IW == g.OW && (g.IW & 3) == 0 && g.Cout <= 4;
 }
 // the 4-class strip kernel takes the data gradient of conv4x4 s2 p1 (functional.py conv_geoms "down") on whole 4-point blocks
 bool dgrad4_strip_ok(const Geom& g) {
-    static const bool off = getenv("AGAN_SMALL_STRIP_OFF") != nullptr || getenv("AGAN_DGRAD4_STRIP_OFF") != nullptr;
-    return !off && g.R == 2 && g.S == 2 && g.OS == 2 && g.SY == 1 && g.DY == -1 && g.OY0 == 0 && g.OY1 == 1 && g.OH == 2 * g.IH && g.OW == 2 * g.IW &&
+    return g.R == 2 && g.S == 2 && g.OS == 2 && g.SY == 1 && g.DY == -1 && g.OY0 == 0 && g.OY1 == 1 && g.OH == 2 * g.IH && g.OW == 2 * g.IW &&
            (g.IW & 3) == 0 && g.Cout <= 4;
 }
 
@@ -661,8 +659,7 @@ SmallWgradPlan plan_wgrad_small_n(const Geom& g) {
 }
 
 void launch_wgrad_small_n(const void* x, const float* dy, float* part, const Geom& g, const SmallWgradPlan& p, hipStream_t st, int x_dtype) {
-    static const bool wg_off = getenv("AGAN_WGRAD_STRIP_OFF") != nullptr;
-    if (strip_ok(g) && (p.pchunk & 255) == 0 && !wg_off) {     // the plan's pixel chunks are whole waves of strips (multiples of 256 pixels)
+    if (strip_ok(g) && (p.pchunk & 255) == 0) {     // the plan's pixel chunks are whole waves of strips (multiples of 256 pixels)
         const dim3 sg(g.Cin, p.nchunk);
 #define AGAN_STRIP(NC_)                                                                                                                   \
     do {                                                                                                                                  \

@@ -29,7 +29,6 @@
 #include "conv_common.h"
 #include "split16.h"
 
-#include <cstdlib>
 #include <cstring>
 
 using namespace agan;
@@ -412,8 +411,8 @@ int pow2ceil_log_w(int v) {
 template <int ET, int NPL, int GK, bool CI2, bool X16, bool Y16, bool UPS>
 void launch_rows(const void* x, const void* dy, float* part, const Geom& g, const RowsPlan& p, hipStream_t st, const float* xs, const float* ys) {
     // staging items per thread (16-byte LDS blocks): the plan checks the geometry against these
-    constexpr int NIX = ET == 2 ? (GK == 2 ? 20 : (CI2 ? 16 : 8)) : (GK == 2 ? 10 : (CI2 ? 8 : 4));
-    constexpr int NIY = ET == 2 ? (GK == 2 ? 10 : (CI2 ? 9 : 18)) : (GK == 2 ? 6 : (CI2 ? 5 : 10));
+    constexpr int NIX = ET == 2 ? (CI2 ? 16 : 8) : (GK == 2 ? 10 : (CI2 ? 8 : 4));
+    constexpr int NIY = ET == 2 ? (CI2 ? 9 : 18) : (GK == 2 ? 6 : (CI2 ? 5 : 10));
     dim3 grid(p.jtiles, p.ngroups, p.psplit);
 #define AGAN_ROWS_LAUNCH(PC_)                                                                                                                         \
     do {                                                                                                                                              \
@@ -431,8 +430,9 @@ void launch_rows(const void* x, const void* dy, float* part, const Geom& g, cons
 }
 template <int ET, int NPL, bool X16, bool Y16>
 void launch_rows_gk(const void* x, const void* dy, float* part, const Geom& g, const RowsPlan& p, hipStream_t st, const float* xs, const float* ys) {
-    if (p.gk == 2) launch_rows<ET, NPL, 2, false, X16, Y16, false>(x, dy, part, g, p, st, xs, ys);
-    else if (p.ups) {
+    if (p.gk == 2) {
+        if constexpr (ET != 2) launch_rows<ET, NPL, 2, false, X16, Y16, false>(x, dy, part, g, p, st, xs, ys);      // (fp32: conv3x3 only, see the plan)
+    } else if (p.ups) {
         if constexpr (ET != 2) {
             if (p.ci2) launch_rows<ET, NPL, 0, true, X16, Y16, true>(x, dy, part, g, p, st, xs, ys);
             else launch_rows<ET, NPL, 0, false, X16, Y16, true>(x, dy, part, g, p, st, xs, ys);
@@ -473,15 +473,11 @@ Geom rows_geom(const Geom& g, bool up) {
 RowsPlan plan_rows_wgrad(const Geom& gf, int prec, bool x16, bool y16, bool up) {
     RowsPlan p;
     memset(&p, 0, sizeof(p));
-    static const bool noup = getenv("AGAN_WG_ROWS_NOUP") != nullptr;
-    if (up && (noup || gf.R != 2 || gf.S != 2 || gf.OS != 2 || gf.OH != 2 * gf.IH || gf.OW != 2 * gf.IW)) return p;
+    if (up && (gf.R != 2 || gf.S != 2 || gf.OS != 2 || gf.OH != 2 * gf.IH || gf.OW != 2 * gf.IW)) return p;
     const Geom g = rows_geom(gf, up);
     p.ups = up ? 1 : 0;
-    static const bool off = getenv("AGAN_WG_ROWS_OFF") != nullptr;
-    if (off) return p;
     const bool f32 = prec == AGAN_PREC_F32;
-    static const bool nof32 = getenv("AGAN_WG_ROWS_NOF32") != nullptr;
-    if (f32 && (up || x16 || y16 || nof32)) return p;     // (fp32: the folded upsample kernel does 4 taps per pixel instead of 9 at the same rate)
+    if (f32 && (up || x16 || y16)) return p;     // (fp32: the folded upsample kernel does 4 taps per pixel instead of 9 at the same rate)
     const int planes = f32 ? 1 : prec_planes(prec);
     if (planes < 1 || planes > 2) return p;
     if ((x16 || y16) && planes != 1) return p;
@@ -495,8 +491,7 @@ RowsPlan plan_rows_wgrad(const Geom& gf, int prec, bool x16, bool y16, bool up) 
     // fp32: measured against conv.hip's k-table kernel (profiles/r03_conv_micro_wgrad.txt): 10-20 % faster on the 3x3 layers of 64-128 channels
     // (their K = 576 pads to 640 there), the same on the stride-2 layers (both sit at the sustained fp32-MFMA rate, ~120 TF/s), slower on the
     // 4x4 maps -- so only the former come here
-    static const bool f32all = getenv("AGAN_WG_ROWS_F32_ALL") != nullptr;
-    if (f32 && !f32all && (p.gk != 0 || g.OW < 16)) return p;
+    if (f32 && (p.gk != 0 || g.OW < 16)) return p;
     p.ci2 = (p.gk == 0 && g.Cout <= 64) ? 1 : 0;
     const int tpl = 7;
     p.twl = std::min(p.gk == 2 ? 5 : 6, pow2ceil_log_w(g.OW));
@@ -521,8 +516,7 @@ RowsPlan plan_rows_wgrad(const Geom& gf, int prec, bool x16, bool y16, bool up) 
     p.bj = (p.gk == 2 || p.ci2) ? 64 : 128;
     const int nci = p.ci2 ? 64 : 32;
     p.plane_bytes = nci * p.cpitch + p.bj * p.dpitch;
-    static const bool nopc = getenv("AGAN_WG_ROWS_NOPC") != nullptr;
-    p.pc = (!nopc && !f32 && planes == 1 && 2 * p.plane_bytes <= 160 * 1024) ? 1 : 0;      // producer / consumer waves on two LDS buffers
+    p.pc = (!f32 && planes == 1 && 2 * p.plane_bytes <= 160 * 1024) ? 1 : 0;      // producer / consumer waves on two LDS buffers
     p.smem_bytes = (p.pc ? 2 : 1) * planes * p.plane_bytes;
     if (p.smem_bytes > 160 * 1024) return p;
     p.nxbl = pow2ceil_log_w(IS * TW / PXB);
@@ -530,8 +524,8 @@ RowsPlan plan_rows_wgrad(const Geom& gf, int prec, bool x16, bool y16, bool up) 
     p.NBY = TW / PXB + 2 * p.halo;
     p.nyitems = p.bj * TB * TH * p.NBY;
     // (items per thread the kernels are instantiated for: launch_rows; fp32 storage in a 16-bit mode loads a block as two 16-byte pieces)
-    const int nix = f32 ? (p.gk == 2 ? 20 : (p.ci2 ? 16 : 8)) : (p.gk == 2 ? 10 : (p.ci2 ? 8 : 4));
-    const int niy = f32 ? (p.gk == 2 ? 10 : (p.ci2 ? 9 : 18)) : (p.gk == 2 ? 6 : (p.ci2 ? 5 : 10));
+    const int nix = f32 ? (p.ci2 ? 16 : 8) : (p.gk == 2 ? 10 : (p.ci2 ? 8 : 4));
+    const int niy = f32 ? (p.ci2 ? 9 : 18) : (p.gk == 2 ? 6 : (p.ci2 ? 5 : 10));
     if (cdiv(p.nxitems, 256) > nix || cdiv(p.nyitems, 256) > niy) return p;
     p.jtiles = cdiv(g.Cout, p.bj);
     p.nchunks = cdiv(g.Cin, 32);
@@ -540,8 +534,7 @@ RowsPlan plan_rows_wgrad(const Geom& gf, int prec, bool x16, bool y16, bool up) 
     int ps = 1;
     // one workgroup per CU is resident: split the pixel tiles until the grid is ONE round of the 256 CUs (measured sweep, round 3: 256 slots
     // 86-96 us per layer, 512: 99-131, 1024: 126-154 -- every further split writes and re-reads one more [cout][K'] slab)
-    static const int slots = getenv("AGAN_WG_ROWS_SLOTS") ? atoi(getenv("AGAN_WG_ROWS_SLOTS")) : 256;
-    if (wgs < slots) ps = std::max(1, std::min(slots / wgs, p.mtiles));
+    if (wgs < 256) ps = std::max(1, std::min(256 / wgs, p.mtiles));
     p.tiles_per_split = cdiv(p.mtiles, ps);
     p.psplit = cdiv(p.mtiles, p.tiles_per_split);
     p.NPH = IS == 2 ? 4 : 1;

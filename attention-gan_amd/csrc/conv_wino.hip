@@ -17,7 +17,6 @@
 // followed by BatchNorm (utilities/layers.py:45-53); calls with one fall back to the direct kernel.
 #include "conv_common.h"
 
-#include <cstdlib>
 #include <cstring>
 
 using namespace agan;
@@ -1073,12 +1072,9 @@ namespace conv {
 WinoPlan plan_wino(const Geom& g) {
     WinoPlan p;
     memset(&p, 0, sizeof(p));
-    static const bool off = getenv("AGAN_WINO_OFF") != nullptr;
-    if (off) return p;
-    static const bool s2off = getenv("AGAN_WINO_S2_OFF") != nullptr;
     if (g.SY == 1 && g.R == 3 && g.S == 3 && g.DY == 1 && g.OS == 1 && g.OY0 == -1 && g.IH == g.OH && g.IW == g.OW) p.s2 = 0;
-    else if (!s2off && g.SY == 2 && g.R == 4 && g.S == 4 && g.DY == 1 && g.OS == 1 && g.OY0 == -1 && g.IH == 2 * g.OH && g.IW == 2 * g.OW) p.s2 = 1;
-    else if (!s2off && g.SY == 1 && g.R == 2 && g.S == 2 && g.DY == -1 && g.OS == 2 && g.OY0 == 0 && g.OY1 == 1 && g.OH == 2 * g.IH && g.OW == 2 * g.IW) p.s2 = 2;
+    else if (g.SY == 2 && g.R == 4 && g.S == 4 && g.DY == 1 && g.OS == 1 && g.OY0 == -1 && g.IH == 2 * g.OH && g.IW == 2 * g.OW) p.s2 = 1;
+    else if (g.SY == 1 && g.R == 2 && g.S == 2 && g.DY == -1 && g.OS == 2 && g.OY0 == 0 && g.OY1 == 1 && g.OH == 2 * g.IH && g.OW == 2 * g.IW) p.s2 = 2;
     else return p;
     if ((g.OHs & 1) || (g.OWs & 1) || (g.Cin & 7) || g.Cout < 32) return p;
     if (p.s2 == 1 && g.Cout < 96) return p;                   // (the stride-2 forward kernel is built for 128-channel tiles)
@@ -1088,8 +1084,7 @@ WinoPlan plan_wino(const Geom& g) {
     const int tw = g.OWs / 2, th = g.OHs / 2;                 // tiles per row / column of the output lattice
     if (tw < 4) return p;                                     // (4x4 maps: two tiles per row -- the direct kernel's K split serves them better)
     p.nf = g.Cout >= 96 ? 4 : 2;                             // cout fragments per workgroup; 4: 32 tiles, 2: 64 tiles
-    static const bool hoff = getenv("AGAN_WINO_H_OFF") != nullptr;
-    p.hmode = (p.s2 == 0 && !hoff && (g.Cout & 7) == 0) ? 1 : 0;   // conv3x3: 32 tiles x 64 channels, two workgroups per CU (conv_wino_h_f32_kernel)
+    p.hmode = (p.s2 == 0 && (g.Cout & 7) == 0) ? 1 : 0;   // conv3x3: 32 tiles x 64 channels, two workgroups per CU (conv_wino_h_f32_kernel)
     if (p.hmode) p.nf = 4;                                    // (tile geometry of the 32-tile blocks)
     const int lt = p.nf == 4 ? 5 : 6;
     p.txl = std::min(3, pow2floor_log(tw));
@@ -1176,8 +1171,6 @@ void launch_wino(const float* in, const float* wk, float* out, const Geom& g, co
 WinoWgradPlan plan_wino_wgrad(const Geom& g) {
     WinoWgradPlan p;
     memset(&p, 0, sizeof(p));
-    static const bool off = getenv("AGAN_WINO_OFF") != nullptr || getenv("AGAN_WINO_WGRAD_OFF") != nullptr;
-    if (off) return p;
     if (!(g.SY == 1 && g.R == 3 && g.S == 3 && g.DY == 1 && g.OS == 1 && g.OY0 == -1)) return p;
     if (g.IH != g.OH || g.IW != g.OW || (g.OH & 1) || (g.OW & 15) || g.Cin < 32 || g.Cout < 32 || (g.Cin & 3) || (g.Cout & 7)) return p;
     p.noct = g.B * (g.OH / 2) * (g.OW / 16);

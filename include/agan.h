@@ -50,10 +50,11 @@ enum {
                              fp16's range: fp32-grade products at 5.3x the fp32-MFMA rate.  The gathered operand's scale comes
                              from an amax slot (see agan_absmax below), the weights are packed times 2^11                   */
 };
-/* The 16-bit modes run on the patch-resident kernels (csrc/conv_patch.hip), which take 3x3 / 2x2-per-class stride-1 and 4x4
+/* A 16-bit mode holds where the patch-resident kernels (csrc/conv_patch.hip) take the geometry: 3x3 / 2x2-per-class stride-1 and 4x4
  * stride-2 geometries with more than 4 input and output channels and images of at least 4x4; any other call (linear layers, the RGB
- * heads) runs in AGAN_PREC_F32 whatever mode is asked for.  agan_conv_effective_prec says which one a geometry gets -- pack the
- * weights for THAT precision (declared below, after agan_conv_geom). */
+ * heads) runs in AGAN_PREC_F32 whatever mode is asked for.  Which kernel then runs the call is the conv routing's choice (see "Conv
+ * routing" below).  agan_conv_effective_prec says which mode a geometry gets -- pack the weights for THAT precision (declared below,
+ * after agan_conv_geom). */
 
 /* Storage type of an ACTIVATION tensor in HBM (round 3).  fp32 is the reference's layout and the default everywhere.  The
  * one-plane 16-bit modes can also keep activations in their operand type -- AGAN_DT_BF16 with AGAN_PREC_BF16, AGAN_DT_F16 with
@@ -126,6 +127,25 @@ int agan_pack_weights(const agan_pack_job* jobs, int njobs, int total_blocks, in
 size_t agan_conv_ktable_elems(const agan_conv_geom* g);
 int agan_conv_ktable(const agan_conv_geom* g, int32_t* table, void* stream);
 
+/* Conv routing.  One function per direction in csrc/conv.hip picks the kernel of a call (route_gather / route_wgrad): the first rule
+ * below that takes it.  Every query of this section reads that choice, and the conv entry points run it.
+ *   forward / data gradient:
+ *     1. one-plane modes (AGAN_PREC_BF16 / F16): the row-block gather (csrc/conv_p16.hip), fp32 or the mode's 16-bit storage on either side;
+ *     2. the other 16-bit-mode calls: the patch-resident gather (csrc/conv_patch.hip), fp32 storage;
+ *     3. AGAN_PREC_F32 conv3x3 stride 1, conv4x4 stride 2 and its data gradient on enough pixels, fp32 storage, no bias / activation /
+ *        mask: Winograd (csrc/conv_wino.hip);
+ *     4. <= 4 output channels: the vector-ALU kernels (csrc/conv_small.hip), fp32 output, fp32 or 16-bit input (linear layers: fp32);
+ *     5. the k-table MFMA kernel (csrc/conv.hip): fp32 input, fp32 or 16-bit output.
+ *   weight gradient (g = the FORWARD geometry):
+ *     1. AGAN_PREC_F32 conv3x3 stride 1 on enough pixels, fp32 storage: Winograd;
+ *     2. the row-resident kernel (csrc/conv_wgrows.hip) where it takes the geometry, in any mode; fp32 or the one-plane mode's 16-bit storage;
+ *     3. the other 16-bit-mode calls: the patch-resident weight gradient, fp32 or the one-plane mode's 16-bit storage;
+ *     4. AGAN_PREC_F32 with <= 4 output channels: the vector-ALU kernel, fp32 or 16-bit x, fp32 dy;
+ *     5. the k-table MFMA kernel: fp32 storage.
+ * agan_conv_gather_dt_supported / agan_conv_wgrad_dt_supported say whether a rule takes the storage types asked for.
+ * agan_conv_gather_ws_bytes / agan_conv_wgrad_ws_bytes return the largest workspace among the kernels this geometry can be routed to
+ * over every argument the query does not name: gather -- the storage pairs, with and without an epilogue; weight gradient -- every mode,
+ * the pack mode the geometry implies (AGAN_PACK_UP_FWD for OS = 2) and the storage pairs. */
 int agan_conv_effective_prec(const agan_conv_geom* g, int prec);
 /* ... and the one its weight gradient gets (agan_conv_wgrad demotes by itself; a caller needs this to know whether the
  * AGAN_PREC_F16X3 scales are wanted).  g = the FORWARD geometry, pack_mode = AGAN_PACK_FWD or AGAN_PACK_UP_FWD. */
@@ -145,8 +165,9 @@ int agan_conv_gather(const float* in, const void* wk, const float* bias, float* 
                      float* out_amax /* optional: amax slot that receives max|out| (16-bit MFMA paths) */);
 
 /* The same call with typed activation storage: `in` has in_dtype, `out` and `lrelu_mask` have out_dtype (AGAN_DT_*).  16-bit
- * tensors need prec == AGAN_PREC_BF16 (AGAN_DT_BF16) / AGAN_PREC_F16 (AGAN_DT_F16) and a geometry the row-block gather
- * (csrc/conv_p16.hip) takes: agan_conv_gather_dt_supported says so (1 / 0) -- a caller converts around an unsupported layer.
+ * tensors go with the one-plane mode of the same type (AGAN_PREC_BF16 / AGAN_PREC_F16) on the row-block gather, or with the fp32
+ * kernels (rules 4 and 5 of the conv routing): agan_conv_gather_dt_supported says so (1 / 0) -- a caller converts around an
+ * unsupported layer.
  * With both dtypes AGAN_DT_F32 this IS agan_conv_gather (workspace: agan_conv_gather_ws_bytes in every case). */
 int agan_conv_gather_dt_supported(const agan_conv_geom* g, int prec, int in_dtype, int out_dtype);
 int agan_conv_gather_dt(const void* in, const void* wk, const float* bias, void* out, const agan_conv_geom* g,
@@ -174,7 +195,8 @@ int agan_conv_wgrad(const float* x, const float* dy, float* dw, const agan_conv_
                     const float* x_amax, const float* dy_amax);
 
 /* the same with typed activation storage (x: x_dtype, dy: dy_dtype; dw stays fp32): 16-bit tensors where
- * agan_conv_wgrad_dt_supported says 1 -- the one-plane patch weight gradient of the matching precision mode */
+ * agan_conv_wgrad_dt_supported says 1 -- the row-resident and patch weight gradients in the one-plane mode of the same type, and a
+ * 16-bit x into the <= 4-output-channel fp32 kernel (rules 2-4 of the conv routing) */
 int agan_conv_wgrad_dt_supported(const agan_conv_geom* g, int pack_mode, int prec, int x_dtype, int dy_dtype);
 int agan_conv_wgrad_dt(const void* x, const void* dy, float* dw, const agan_conv_geom* g, const int32_t* ktable, int pack_mode,
                        int kh, int kw, int prec, int accumulate, void* ws, size_t ws_bytes, void* stream,

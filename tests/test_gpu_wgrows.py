@@ -8,8 +8,8 @@ One case per code path of the kernel and its plan, each in every arithmetic mode
   * the upsample conv taken as conv3x3 on the upsampled image built in LDS;
   * fp32 operands on v_mfma_f32_32x32x2 (AGAN_PREC_F32, 3x3 layers), the two-plane splits, 16-bit and fp32 activation storage.
 The operands are exactly representable in the mode's operand type (16-bit modes), so the fp32 result differs from the reference only by
-accumulation order.  `AGAN_WG_ROWS_OFF=1` (checked at library load) would send every case to the older kernels: the last test makes sure the
-plan really takes these geometries.
+accumulation order.  The last test makes sure the plan really takes these geometries (a library whose routing sent them to the older kernels
+would pass the cases above without testing this kernel).
 """
 import ctypes
 import importlib
@@ -115,7 +115,7 @@ def test_second_backward_accumulates(mode):
 
 def test_the_plan_takes_these_geometries():
     """agan_conv_wgrad_effective_prec keeps the mode for the upsample conv only when the row-resident kernel takes it: a cheap probe that the
-    library under test was not loaded with AGAN_WG_ROWS_OFF / _NOUP (which would make the cases above test the older kernels)"""
+    library under test routes these geometries to it (otherwise the cases above would test the older kernels)"""
     lib = L.load()
     HF.set_precision(L.PREC_BF16)
     try:
