@@ -11,6 +11,11 @@ four fused Adam steps; under N > 1 every rank runs its own 24-image shard (weak 
 all-reduced over RCCL.  Inputs are synthetic and already resident in HBM when the timed region starts.
 Prints ONE JSON line on rank 0.
 
+A plain run does only what the headline needs: set up, warm up, time the steps, write --dump-outputs, print the line.  --full
+adds everything measured beside it, each in runs of its own after the timed region: the per-kernel roofline (and --layer-table)
+from instrumented steps, the exposed gradient exchange under N > 1, the side measurements (`variants`) and the CPU oracle
+baseline (`cpu_baseline`).
+
 --workload picks the BASELINE.json configuration (default: configs[2], the one the metric is quoted on):
     full3        configs[2]  full 3-stage step, batch 24, f32 arithmetic (the parity-proven headline)
     stage1_b64   configs[1]  stage-1 only (CA-net + gen1 + img_out1 + Disc64), batch 64, bf16 arithmetic
@@ -433,7 +438,7 @@ def roofline_objects(timer, args, elapsed_ms_per_step, roof_steps, timing_note):
     return roofline, by_kernel
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=120, help="timed steps (default: a >= 3 s timed region at the metric config)")
@@ -460,23 +465,37 @@ def main():
     ap.add_argument("--single-stream", action="store_true",
                     help="run the discriminator updates on ONE stream (profiling aid: per-kernel PMC counters of a rocprofv3 pass are "
                          "diluted when kernels of different streams share the chip; the headline run overlaps them)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure what is reported beside the headline, each in runs of its own: `roofline` / "
+                         "`roofline_by_kernel` / algorithmic_conv_gflop_per_step from instrumented steps, the exposed gradient exchange "
+                         "under N > 1, `variants` and `cpu_baseline` (the last two at --workload full3 on one GPU)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baseline")
     ap.add_argument("--no-variants", action="store_true",
-                    help="skip the short side measurements reported beside the headline (random caption lengths, the other arithmetic modes, "
-                         "the end-to-end step with the Inception-shaped trunk and the LSTM text encoder, the other two BASELINE configs)")
+                    help="with --full: skip the short side measurements reported beside the headline (random caption lengths, the other "
+                         "arithmetic modes, the end-to-end step with the Inception-shaped trunk and the LSTM text encoder, the other two "
+                         "BASELINE configs)")
     ap.add_argument("--cpu-baseline-batch", type=int, default=24)
-    ap.add_argument("--layer-table", default=None, help="write the per-layer conv timing table of the instrumented steps to this file")
+    ap.add_argument("--layer-table", default=None,
+                    help="with --full: write the per-layer conv timing table of the instrumented steps to this file")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="write what the last timed step returned (losses, fake images, attention maps, mu / logvar) to DIR/<name>.npy "
                          "in float32, at most 64 MB in all (larger arrays: a fixed seeded sample), so that two builds can be compared")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.layer_table and not args.full:
+        ap.error("--layer-table needs --full (the table comes from the instrumented steps)")
     spec = WORKLOADS[args.workload]
     if args.batch is None:
         args.batch = spec["batch"]
     if args.precision is None:
         args.precision = spec["precision"]
+    return args
+
+
+def main():
+    args = parse_args()
+    spec = WORKLOADS[args.workload]
 
     # stdout carries exactly ONE line, the JSON report of rank 0.  Libraries write there too (RCCL prints its version banner to
     # stdout when a communicator is created, MIOpen its find-db notes): everything but the report goes to stderr.
@@ -627,48 +646,53 @@ def main():
                                                          else "the capture's and probe's untimed steps, then warm-up and timed replays")
     finite = all(bool(torch.isfinite(out[k]).all()) for k in (f"d_loss{len(step.Ds) - 1}", "g_total"))
     if dp:
-        # EXPOSED exchange: HIP events around every wait of a compute stream on the exchange (GradBuckets._join), over two more
-        # steps in the launch mode of the timed region; max over ranks.  Host enqueue of the timed region per rank beside it.
-        for bk in buckets:
-            bk.measure = True
-        for _ in range(2):
-            one_step()
-        exposed = sum(bk.exposed_ms() for bk in buckets) / 2.0
-        for bk in buckets:
-            bk.measure = False
+        # host enqueue of the timed region per rank; with --full, beside it the EXPOSED exchange: HIP events around every wait of a
+        # compute stream on the exchange (GradBuckets._join), over two more steps in the launch mode of the timed region, max over ranks
+        exposed = None
+        if args.full:
+            for bk in buckets:
+                bk.measure = True
+            for _ in range(2):
+                one_step()
+            exposed = round(sum(bk.exposed_ms() for bk in buckets) / 2.0, 3)
+            for bk in buckets:
+                bk.measure = False
         per_rank = [None] * dist.get_world_size()
-        dist.all_gather_object(per_rank, (round(t_enqueued / args.steps * 1e3, 2), round(exposed, 3)))
+        dist.all_gather_object(per_rank, (round(t_enqueued / args.steps * 1e3, 2), exposed))
         dp_info = dict(dp_info or {})
         dp_info.update({"exchange": step.g_buckets.mode, "bucket_mb": [round((e - s) * 4 / 2 ** 20, 1) for s, e in step.d_buckets[-1].bounds][:3],
-                        "timed_host_enqueue_ms_per_step_per_rank": [p[0] for p in per_rank],
-                        "exposed_exchange_ms_per_step_per_rank": [p[1] for p in per_rank],
-                        "exposed_exchange_ms_per_step": max(p[1] for p in per_rank),
-                        "exposed_exchange_note": "time the compute streams sat blocked on the gradient exchange (events around each wait), "
-                                                 "2 untimed steps after the timed region, same launch mode"})
-    # Per-launch kernel durations for the roofline object.  The timed region above overlaps the discriminator branches on
+                        "timed_host_enqueue_ms_per_step_per_rank": [p[0] for p in per_rank]})
+        if args.full:
+            dp_info.update({"exposed_exchange_ms_per_step_per_rank": [p[1] for p in per_rank],
+                            "exposed_exchange_ms_per_step": max(p[1] for p in per_rank),
+                            "exposed_exchange_note": "time the compute streams sat blocked on the gradient exchange (events around each "
+                                                     "wait), 2 untimed steps after the timed region, same launch mode"})
+    # Per-launch kernel durations for the roofline object (--full).  The timed region above overlaps the discriminator branches on
     # separate HIP streams (and, at N=1, may replay a captured graph with no host code between launches), so a launch's
     # event-to-event time there includes whatever runs beside it.  The same launches (same shapes, same kernels, same inputs) are
     # therefore timed in ROOF_STEPS instrumented eager steps on one stream, right after the timed region, in this process.
     ROOF_STEPS = 2
-    overlap = step.overlap_discriminators, step.overlap_weight_gradients
-    step.overlap_discriminators = step.overlap_weight_gradients = False
-    timer.clear()
-    timer.enabled = True
-    for _ in range(ROOF_STEPS):
-        step.step(words, sent, lens_dev, None, reals)
-    torch.cuda.synchronize()
-    timer.enabled = False
-    step.overlap_discriminators, step.overlap_weight_gradients = overlap
-    roofline_timing = ("HIP events recorded by the library on the launch stream immediately around each main conv kernel "
-                       f"(agan_timer_arm), over {ROOF_STEPS} single-stream eager steps run right after the timed region; the timed "
-                       "region itself overlaps streams / replays a HIP graph")
-    if rank == 0 and args.layer_table:
-        with open(args.layer_table, "w") as f:
-            f.write(timer.layer_table(ROOF_STEPS) + "\n")
+    if args.full:
+        overlap = step.overlap_discriminators, step.overlap_weight_gradients
+        step.overlap_discriminators = step.overlap_weight_gradients = False
+        timer.clear()
+        timer.enabled = True
+        for _ in range(ROOF_STEPS):
+            step.step(words, sent, lens_dev, None, reals)
+        torch.cuda.synchronize()
+        timer.enabled = False
+        step.overlap_discriminators, step.overlap_weight_gradients = overlap
+        if rank == 0 and args.layer_table:
+            with open(args.layer_table, "w") as f:
+                f.write(timer.layer_table(ROOF_STEPS) + "\n")
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
-        roofline, by_kernel = roofline_objects(timer, args, ms_per_step, ROOF_STEPS, roofline_timing)
-        alg_gflop = sum(v[2] for v in timer.summary().values()) / ROOF_STEPS / 1e9
+        if args.full:
+            roofline_timing = ("HIP events recorded by the library on the launch stream immediately around each main conv kernel "
+                               f"(agan_timer_arm), over {ROOF_STEPS} single-stream eager steps run right after the timed region; the timed "
+                               "region itself overlaps streams / replays a HIP graph")
+            roofline, by_kernel = roofline_objects(timer, args, ms_per_step, ROOF_STEPS, roofline_timing)
+            alg_gflop = sum(v[2] for v in timer.summary().values()) / ROOF_STEPS / 1e9
         launch = (("hip-graph segments + eager gradient exchange" if launch_note == "segments" else "hip-graph replay") if use_graph else "eager")
         line = {
             "metric": baseline_metric_name() if args.workload == "full3" else
@@ -688,18 +712,17 @@ def main():
                        "text_encoder": "bypassed (frozen; N(0,1) embeddings)", "parallelism": f"dp{world}",
                        "discriminator_streams": 1 if args.single_stream else len(step.Ds),
                        "launch": launch, "gradient_exchange": step.g_buckets.mode,
-                       "algorithmic_conv_gflop_per_step": round(alg_gflop, 1),
+                       **({"algorithmic_conv_gflop_per_step": round(alg_gflop, 1)} if args.full else {}),
                        "losses_finite": finite},
-            "roofline": roofline,
-            "roofline_by_kernel": by_kernel,
+            **({"roofline": roofline, "roofline_by_kernel": by_kernel} if args.full else {}),
         }
         if dp_info:
             line["data_parallel"] = dp_info
         if args.dump_outputs:
             line["dumped_outputs"] = dumped
-        if world == 1 and not dp and not args.no_variants and args.workload == "full3":
+        if args.full and world == 1 and not dp and not args.no_variants and args.workload == "full3":
             line["variants"] = side_measurements(args, dev, HF, LIB, step, words, sent, reals)
-        if world == 1 and not args.no_cpu_baseline and args.workload == "full3":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.workload == "full3":
             line["cpu_baseline"] = cpu_baseline(args.cpu_baseline_batch)
         sys.stdout.flush()
         os.write(report_fd, (json.dumps(line) + "\n").encode())

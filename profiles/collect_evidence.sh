@@ -11,7 +11,7 @@ TAG=${3:-$DEF}
 R=$GRAFT_REPO_ROOT
 case $MODE in f16*) LOWC=SQ_INSTS_VALU_MFMA_MOPS_F16;; *) LOWC=SQ_INSTS_VALU_MFMA_MOPS_BF16;; esac
 cd /tmp && export TMPDIR=/tmp
-B="python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-variants --graph off --workload $WORKLOAD --precision $MODE --storage $STORAGE"
+B="python3 $R/bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-variants --graph off --workload $WORKLOAD --precision $MODE --storage $STORAGE"
 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/ev_${TAG}_stats -o p -- $B > /dev/null 2>&1 &&
 # (the counter passes run the three discriminator updates on ONE stream: a kernel's counters are per dispatch, and kernels of different
 #  streams sharing the chip dilute each other's busy fractions; the kernel-time shares come from the pass above, which overlaps them)

@@ -3,7 +3,7 @@
 
 Collection (on the GPU box; counters in their own runs, kernel trace only; the program directly after `--`):
 
-    cd /tmp && export TMPDIR=/tmp; R=$GRAFT_REPO_ROOT; B="python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-variants --graph off --precision $MODE"
+    R=$PWD; cd /tmp && export TMPDIR=/tmp; B="python3 $R/bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-variants --graph off --precision $MODE"
     rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/ev_${MODE}_stats -o p -- $B
     rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_INSTS_VALU_MFMA_MOPS_BF16 \   # (_F16 for the f16 modes)
               --kernel-trace --output-format csv -d $R/gpurun_out/ev_${MODE}_mfma -o p -- $B
@@ -223,7 +223,7 @@ def main():
                    "write_size": round(c["write"] / max(1, c["nw"])),
                    "traffic": round(2 * c["fetch"] / max(1, c["nf"]) + c["write"] / max(1, c["nw"]))} for b, c in sorted(conv.items())}
     doc = {"source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, kernel trace only) over `python bench.py --steps 2 "
-                     f"--warmup 1 --no-cpu-baseline --no-variants --graph off --precision {mode}" + (f" --storage {mode}" if parts[-1] == "s16" else "") +
+                     f"--warmup 1 --full --no-cpu-baseline --no-variants --graph off --precision {mode}" + (f" --storage {mode}" if parts[-1] == "s16" else "") +
                      "`; summarised by profiles/make_counters.py",
            "unit": "bytes per launch (average over all launches of the kernel in the run)",
            "correction": "gfx950: FETCH_SIZE counts 64 B per 128-B request (MI355X_MICROARCH.md, HBM): traffic = 2*FETCH_SIZE + WRITE_SIZE; "

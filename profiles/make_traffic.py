@@ -3,11 +3,11 @@
 
 Collection (on the GPU box; counters in their own runs, kernel trace only -- see DESIGN.md "Measurement"):
 
-    cd /tmp && export TMPDIR=/tmp
-    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $R/gpurun_out/pmc_fetch -o p -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --graph off
-    rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $R/gpurun_out/pmc_write -o p -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --graph off
+    R=$PWD; OUT=$R/pmc; cd /tmp && export TMPDIR=/tmp
+    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/fetch -o p -- python3 $R/bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --graph off
+    rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/write -o p -- python3 $R/bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --graph off
 
-    python profiles/make_traffic.py gpurun_out/pmc_fetch gpurun_out/pmc_write profiles r02
+    cd $R && python profiles/make_traffic.py $OUT/fetch $OUT/write profiles r02
 
 rocprofv3 reports both counters in KB.  gfx950 correction (MI355X_MICROARCH.md, HBM): FETCH_SIZE tallies a 128-B request as 64 B,
 so reads = 2 * FETCH_SIZE; WRITE_SIZE is exact.  traffic = 2 * FETCH_SIZE + WRITE_SIZE, averaged per launch of the kernel.
@@ -79,7 +79,7 @@ def main():
         kernels[b] = {"launches": g["launches"], "fetch_size_raw": round(fr), "write_size": round(wr), "traffic": round(2 * fr + wr)}
     doc = {
         "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, kernel trace only) over "
-                  "`python bench.py --steps 2 --warmup 1 --no-cpu-baseline --graph off`; summarised by profiles/make_traffic.py",
+                  "`python bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --graph off`; summarised by profiles/make_traffic.py",
         "unit": "bytes per launch (average over all launches of the kernel in the run)",
         "correction": "gfx950: FETCH_SIZE counts 64 B per 128-B request, i.e. half of a streamed read (MI355X_MICROARCH.md, HBM): "
                       "traffic = 2*FETCH_SIZE + WRITE_SIZE.  The x2 is calibrated for 16-B/lane streams; the conv gathers issue "

@@ -400,6 +400,17 @@ def test_bench_kernel_symbol_key():
     assert [bench.WORKLOADS[k]["config"] for k in ("stage1_b64", "full3", "stage4_b8")] == [1, 2, 4]
 
 
+def test_bench_plain_run_leaves_side_measurements_to_full():
+    """a plain `bench.py --gpus 1 --steps N --warmup W` times the headline only; roofline, variants and cpu_baseline need --full"""
+    sys.path.insert(0, ROOT)
+    import bench
+    args = bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert not args.full and (args.workload, args.batch, args.precision) == ("full3", 24, "f32")
+    assert bench.parse_args(["--full", "--layer-table", "t.txt"]).full
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--layer-table", "t.txt"])
+
+
 def test_golden_fixtures_are_data_only():
     for f in os.listdir(GOLDEN):
         if f.endswith(".npz"):
