@@ -1144,3 +1144,163 @@ def adam_step_(param: Tensor, grad: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor,
         rng[2] += 1
     else:
         bump_weight_epoch()
+
+
+# --------------------------------------------------------------------------------------------------------------
+# frozen Inception-v3 image-encoder trunk (networks/cnn_encoder.py::CNNEncoder, backend="hip"; eval mode only)
+# --------------------------------------------------------------------------------------------------------------
+# Each conv's eval-mode BatchNorm folds into its weights and a per-channel bias (w' = w*gamma*invstd, b' = beta - mean*gamma*invstd,
+# invstd = 1/sqrt(running_var + eps)), followed by the ReLU epilogue of agan_conv2d_fwd.  The folded weights are packed once per
+# direction and cached on the module; a conv is re-folded when any of its five tensors changed -- in-place version bump
+# (load_state_dict, an in-place edit) or new storage (.to()): the invalidation rule of packed_weight.  The trunk runs in fp32 in every
+# precision mode (agan_conv2d_effective_prec).  The layer plan (which tensors, slices, write/accumulate order) is
+# networks/inception_plan.py.
+def _conv2d_desc(op, B: int) -> "L.Conv2dDesc":
+    d = L.Conv2dDesc()
+    d.B, d.Cin, d.IH, d.IW, d.Cout, d.OH, d.OW = B, op.C, op.H, op.W, op.Cout, op.OH, op.OW
+    d.KH, d.KW = op.k
+    d.SH, d.SW = op.s
+    d.PH, d.PW = op.p
+    d.in_c0, d.in_ctot, d.out_c0, d.out_ctot = 0, op.C, op.out_c0, op.out_ctot
+    return d
+
+
+_CONV2D_KTABLES = {}
+
+
+def conv2d_ktable(d: "L.Conv2dDesc", dgrad: int, device) -> Tensor:
+    """k-table of a general conv descriptor and direction (agan_conv2d_ktable), built once per (geometry, device)."""
+    key = (tuple(getattr(d, n) for n, _ in L.Conv2dDesc._fields_), dgrad, str(device))
+    t = _CONV2D_KTABLES.get(key)
+    if t is None:
+        n = L.load().agan_conv2d_ktable_elems(byref(d), dgrad)
+        if n == 0:
+            raise L.AganError(f"conv2d: no k-table for this geometry ({L.load().agan_last_error().decode()})")
+        t = torch.empty(n, dtype=torch.int32, device=device)
+        L.call("agan_conv2d_ktable", byref(d), dgrad, _p(t), _stream())
+        _CONV2D_KTABLES[key] = t
+    return t
+
+
+def conv2d_pack(w: Tensor, d: "L.Conv2dDesc", dgrad: int) -> Tensor:
+    """pack an OIHW fp32 weight for one direction of a general conv (agan_conv2d_pack_mode picks the layout)"""
+    mode = L.load().agan_conv2d_pack_mode(byref(d), dgrad)
+    if mode < 0:
+        raise L.AganError(f"conv2d: {L.load().agan_last_error().decode()}")
+    cout, cin, kh, kw = w.shape
+    wk = torch.empty(L.load().agan_packed_weight_bytes(mode, cout, cin, kh, kw, L.PREC_F32), dtype=torch.uint8, device=w.device)
+    L.call("agan_pack_weight", _p(w), _p(wk), mode, cout, cin, kh, kw, L.PREC_F32, _stream())
+    return wk
+
+
+def _trunk_layer(module, op, device):
+    """(folded bias, packed forward weight, packed data-gradient weight) of one conv of the plan, re-folded when stale"""
+    m = module.get_submodule(op.name)
+    ts = (m.conv.weight, m.bn.weight, m.bn.bias, m.bn.running_mean, m.bn.running_var)
+    ver = tuple((t.data_ptr(), t._version) for t in ts) + (float(m.bn.eps), str(device))
+    cache = module.__dict__.setdefault("_agan_trunk_fold", {})
+    hit = cache.get(op.name)
+    if hit is not None and hit[0] == ver:
+        return hit[1]
+    w, gamma, beta, mean, var = (_dev(t.detach(), f"trunk {op.name}") for t in ts)
+    with torch.no_grad():
+        scale = gamma * torch.rsqrt(var + m.bn.eps)
+        wf = (w * scale.view(-1, 1, 1, 1)).contiguous()
+        bf = (beta - mean * scale).contiguous()
+    d = _conv2d_desc(op, 1)
+    val = (bf, conv2d_pack(wf, d, 0), conv2d_pack(wf, d, 1))
+    cache[op.name] = (ver, val)
+    return val
+
+
+class _InceptionTrunkFn(Function):
+    """image [B,3,H,W] -> (Mixed_6e output [B,768,17,17], pooled Mixed_7c [B,2048]); backward: the image gradient only."""
+
+    @staticmethod
+    def forward(ctx, image: Tensor, module, plan):
+        image = _dev(image, "inception trunk")
+        B, dev = image.shape[0], image.device
+        st = _stream()
+        _, ws = _ws(0, image)
+        T: Dict[str, Tensor] = {"image": image}
+        argmax: Dict[int, Tensor] = {}
+        for i, op in enumerate(plan.ops):
+            dst = T.get(op.dst)
+            if dst is None:
+                t = plan.tensors[op.dst]
+                dst = T[op.dst] = torch.empty((B, t.C) if op.kind == "gap" else (B, t.C, t.H, t.W), device=dev)
+            src = T[op.src]
+            if op.kind == "conv":
+                d = _conv2d_desc(op, B)
+                bias, wk, _ = _trunk_layer(module, op, dev)
+                L.call("agan_conv2d_fwd", _p(src), _p(wk), _p(bias), _p(dst), byref(d), _p(conv2d_ktable(d, 0, dev)), L.ACT_RELU,
+                       ws, 0, st)
+            elif op.kind == "maxpool":
+                am = argmax[i] = torch.empty(B * op.C * op.OH * op.OW, dtype=torch.uint8, device=dev)
+                L.call("agan_maxpool3s2_fwd", _p(src), _p(dst), _p(am), B, op.C, op.H, op.W, op.out_c0, op.out_ctot, st)
+            elif op.kind == "avgpool":
+                L.call("agan_avgpool3s1_fwd", _p(src), _p(dst), B, op.C, op.H, op.W, st)
+            elif op.kind == "gap":
+                L.call("agan_global_avgpool_fwd", _p(src), _p(dst), B, op.C, op.H * op.W, st)
+            else:   # resize
+                L.call("agan_resize_bilinear_fwd", _p(src), _p(dst), B, op.C, op.H, op.W, op.OH, op.OW, st)
+        ctx.module, ctx.plan, ctx.B = module, plan, B
+        ctx.masks = {n: T[n] for n, t in plan.tensors.items() if t.relu}      # the ReLU outputs: masks of the backward
+        ctx.argmax = argmax
+        from ..networks.inception_plan import FEATURES, POOLED
+        return T[FEATURES], T[POOLED]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_feat: Optional[Tensor], g_pooled: Optional[Tensor]):
+        from ..networks.inception_plan import FEATURES, POOLED
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        plan, B, masks = ctx.plan, ctx.B, ctx.masks
+        feat = masks[FEATURES]
+        dev, st = feat.device, _stream()
+        _, ws = _ws(0, feat)
+        G: Dict[str, Tensor] = {}
+        # the external gradient of the Mixed_6e output seeds its buffer (masked by its ReLU); Mixed_7a's ops then add
+        G[FEATURES] = torch.empty_like(feat)
+        if g_feat is None:
+            G[FEATURES].zero_()
+        else:
+            g_feat = _dev(g_feat, "trunk backward")
+            L.call("agan_relu_bwd", _p(feat), _p(g_feat), _p(G[FEATURES]), feat.numel(), 0, st)
+        G[POOLED] = torch.zeros(B, plan.tensors[POOLED].C, device=dev) if g_pooled is None else _dev(g_pooled, "trunk backward")
+        first_producer = {}
+        for i, op in enumerate(plan.ops):
+            first_producer.setdefault(op.dst, i)
+        for i in range(len(plan.ops) - 1, -1, -1):
+            op = plan.ops[i]
+            gy = G[op.dst] if first_producer[op.dst] != i else G.pop(op.dst)     # (the last reader of this gradient frees it)
+            gx = G.get(op.src)
+            if gx is None:
+                t = plan.tensors[op.src]
+                gx = G[op.src] = torch.empty(B, t.C, t.H, t.W, device=dev)
+            mask = masks.get(op.src)
+            acc = int(op.accumulate)
+            if op.kind == "conv":
+                d = _conv2d_desc(op, B)
+                _, _, wkd = _trunk_layer(ctx.module, op, dev)
+                L.call("agan_conv2d_dgrad", _p(gy), _p(wkd), _p(gx), byref(d), _p(conv2d_ktable(d, 1, dev)), _p(mask), acc, ws, 0, st)
+            elif op.kind == "maxpool":
+                L.call("agan_maxpool3s2_bwd", _p(gy), _p(ctx.argmax[i]), _p(mask), _p(gx), B, op.C, op.H, op.W, op.out_c0, op.out_ctot,
+                       acc, st)
+            elif op.kind == "avgpool":
+                L.call("agan_avgpool3s1_bwd", _p(gy), _p(mask), _p(gx), B, op.C, op.H, op.W, acc, st)
+            elif op.kind == "gap":
+                L.call("agan_global_avgpool_bwd", _p(gy), _p(mask), _p(gx), B, op.C, op.H * op.W, acc, st)
+            else:   # resize: the image is the first and only reader of nothing else -- a plain write
+                L.call("agan_resize_bilinear_bwd", _p(gy), _p(gx), B, op.C, op.H, op.W, op.OH, op.OW, st)
+        ctx.masks = ctx.argmax = None
+        return G["image"], None, None
+
+
+def inception_trunk(image: Tensor, module) -> Tuple[Tensor, Tensor]:
+    """Eval-mode Inception-v3 trunk of `module` (a networks.cnn_encoder.CNNEncoder) on the library's kernels:
+    image [B,3,H,W] -> (Mixed_6e output [B,768,17,17], global average of Mixed_7c [B,2048]), differentiable w.r.t. the image."""
+    from ..networks.inception_plan import build_plan
+    plan = build_plan(image.shape[-2], image.shape[-1])
+    return _InceptionTrunkFn.apply(image, module, plan)

@@ -15,8 +15,8 @@ LIB_PATH = os.environ.get("AGAN_LIB") or os.path.join(os.path.dirname(_HERE), "c
 # enums of include/agan.h
 PREC_F32, PREC_BF16, PREC_BF16X3, PREC_F16, PREC_BF16X6, PREC_F16X3 = 0, 1, 2, 3, 4, 5
 PRECISIONS = {"f32": PREC_F32, "bf16": PREC_BF16, "bf16x3": PREC_BF16X3, "f16": PREC_F16, "bf16x6": PREC_BF16X6, "f16x3": PREC_F16X3}
-PACK_FWD, PACK_DGRAD_S1, PACK_DGRAD_4x4S2, PACK_UP_FWD, PACK_UP_DGRAD = 0, 1, 2, 3, 4
-ACT_NONE, ACT_GLU, ACT_LRELU, ACT_TANH, ACT_SIGMOID = 0, 1, 2, 3, 4
+PACK_FWD, PACK_DGRAD_S1, PACK_DGRAD_4x4S2, PACK_UP_FWD, PACK_UP_DGRAD, PACK_DGRAD_3x3S2 = 0, 1, 2, 3, 4, 5
+ACT_NONE, ACT_GLU, ACT_LRELU, ACT_TANH, ACT_SIGMOID, ACT_RELU = 0, 1, 2, 3, 4, 5
 COMM_ID_BYTES = 128    # include/agan.h: AGAN_COMM_ID_BYTES
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2          # include/agan.h: AGAN_DT_* (storage type of an activation tensor)
 AMAX_SLOT = 256        # floats per amax slot (include/agan.h: AGAN_AMAX_SLOT)
@@ -28,6 +28,12 @@ class ConvGeom(Structure):
     _fields_ = [("B", c_int32), ("Cin", c_int32), ("IH", c_int32), ("IW", c_int32),
                 ("Cout", c_int32), ("OH", c_int32), ("OW", c_int32), ("R", c_int32), ("S", c_int32),
                 ("OS", c_int32), ("SY", c_int32), ("DY", c_int32), ("OY", c_int32 * 2)]
+
+
+class Conv2dDesc(Structure):
+    """struct agan_conv2d_desc (the general 2-D conv of the image-encoder trunk)."""
+    _fields_ = [(n, c_int32) for n in ("B", "Cin", "IH", "IW", "Cout", "OH", "OW", "KH", "KW", "SH", "SW", "PH", "PW",
+                                       "in_c0", "in_ctot", "out_c0", "out_ctot")]
 
 
 _P = c_void_p
@@ -106,6 +112,22 @@ _SIGNATURES = {
     "agan_kl_loss": (c_int, [_P, _P, _P, _P, _P, c_int, _P]),
     "agan_reparam_fwd": (c_int, [_P, _P, _P, _P, c_int, _P]),
     "agan_reparam_bwd": (c_int, [_P, _P, _P, _P, _P, c_int, _P]),
+    "agan_conv2d_pack_mode": (c_int, [POINTER(Conv2dDesc), c_int]),
+    "agan_conv2d_effective_prec": (c_int, [POINTER(Conv2dDesc), c_int]),
+    "agan_conv2d_ws_bytes": (c_size_t, [POINTER(Conv2dDesc), c_int]),
+    "agan_conv2d_ktable_elems": (c_size_t, [POINTER(Conv2dDesc), c_int]),
+    "agan_conv2d_ktable": (c_int, [POINTER(Conv2dDesc), c_int, _P, _P]),
+    "agan_conv2d_fwd": (c_int, [_P, _P, _P, _P, POINTER(Conv2dDesc), _P, c_int, _P, c_size_t, _P]),
+    "agan_conv2d_dgrad": (c_int, [_P, _P, _P, POINTER(Conv2dDesc), _P, _P, c_int, _P, c_size_t, _P]),
+    "agan_maxpool3s2_fwd": (c_int, [_P, _P, _P] + [c_int] * 6 + [_P]),
+    "agan_maxpool3s2_bwd": (c_int, [_P, _P, _P, _P] + [c_int] * 7 + [_P]),
+    "agan_avgpool3s1_fwd": (c_int, [_P, _P] + [c_int] * 4 + [_P]),
+    "agan_avgpool3s1_bwd": (c_int, [_P, _P, _P] + [c_int] * 5 + [_P]),
+    "agan_global_avgpool_fwd": (c_int, [_P, _P] + [c_int] * 3 + [_P]),
+    "agan_global_avgpool_bwd": (c_int, [_P, _P, _P] + [c_int] * 4 + [_P]),
+    "agan_resize_bilinear_fwd": (c_int, [_P, _P] + [c_int] * 6 + [_P]),
+    "agan_resize_bilinear_bwd": (c_int, [_P, _P] + [c_int] * 6 + [_P]),
+    "agan_relu_bwd": (c_int, [_P, _P, _P, c_size_t, c_int, _P]),
     "agan_adam_step": (c_int, [_P, _P, _P, _P, c_size_t, _P, c_double, c_double, c_double, c_double, c_float, _P]),
 }
 

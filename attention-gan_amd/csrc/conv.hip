@@ -62,7 +62,11 @@ __global__ __launch_bounds__(256) void ktable_kernel(int2* __restrict__ tab, int
 #endif
 // ODT: storage type of `out` and of `lrelu_mask` (AGAN_DT_*; fp32 arithmetic either way -- a 16-bit output is the data gradient or
 // the first-layer output of a network that keeps its activations in 16 bits: rounded once here instead of by a cast kernel)
-template <int BM, int BN, int WM, int WN, int ODT = AGAN_DT_F32>
+// GEN: the general 2-D conv of agan_conv2d_fwd / agan_conv2d_dgrad -- per-axis stride and offset (g.SX, g.OX*), up to 25 taps,
+// channel-slice addressing on both tensors (g.in0/inB, g.out0/outB), class grids of ceil(OH/OS) x ceil(OW/OS) with the overhang
+// dropped, and the epilogue bias -> ReLU (g.relu), x ReLU'(mask) (lrelu_mask is then a ReLU mask), += out (g.accumulate).  Only
+// ever launched unsplit with fp32 output.  GEN = false compiles to the kernel the other conv calls have always run.
+template <int BM, int BN, int WM, int WN, int ODT = AGAN_DT_F32, bool GEN = false>
 __global__ __launch_bounds__(256, AGAN_GATHER_WAVES) void conv_gather_f32_kernel(const float* __restrict__ in, const float* __restrict__ wk,
                                                                const float* __restrict__ bias, void* __restrict__ out_v,
                                                                const int2* __restrict__ ktab, const Geom g, const int ksplit,
@@ -81,7 +85,8 @@ __global__ __launch_bounds__(256, AGAN_GATHER_WAVES) void conv_gather_f32_kernel
     __shared__ float Bs[2][BK][BN];
     // per-pixel byte offset of every tap (padding test folded in as an out-of-range offset), row RS = "always out of range":
     // computed once per workgroup, so the K loop does no address arithmetic beyond one LDS read per gathered element
-    __shared__ unsigned Toff[kMaxTaps + 1][BM];
+    constexpr int kTaps = GEN ? kMaxTaps2d : kMaxTaps;
+    __shared__ unsigned Toff[kTaps + 1][BM];
     static_assert(BM * 4 == kTapRowBytes, "tap table row size");
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -111,7 +116,7 @@ __global__ __launch_bounds__(256, AGAN_GATHER_WAVES) void conv_gather_f32_kernel
     const int nkt = cdiv(kend - kbeg, BK);
     const int ihw = g.IH * g.IW;
 
-    const __amdgpu_buffer_rsrc_t rin = make_rsrc(in, (size_t)g.B * g.Cin * ihw * sizeof(float));
+    const __amdgpu_buffer_rsrc_t rin = make_rsrc(in, (size_t)g.B * (GEN ? g.inB : g.Cin * ihw) * sizeof(float));
     const __amdgpu_buffer_rsrc_t rwk = make_rsrc(wk + (size_t)cls * g.K * g.Nld, (size_t)g.K * g.Nld * sizeof(float));
 
     // ---- per-thread pixel for the A gather -------------------------------------------------------
@@ -123,8 +128,9 @@ __global__ __launch_bounds__(256, AGAN_GATHER_WAVES) void conv_gather_f32_kernel
         const int mm = mvalid ? m : 0;
         const int b = g.dHWs.div(mm), rem = mm - b * g.HWs;
         const int yq = g.dOWs.div(rem), xq = rem - yq * g.OWs;
-        const int iy0 = yq * g.SY + (py ? g.OY1 : g.OY0), ix0 = xq * g.SY + (px ? g.OY1 : g.OY0);
-        const int pix0 = b * g.Cin * ihw + iy0 * g.IW + ix0;
+        const int iy0 = yq * g.SY + (py ? g.OY1 : g.OY0);
+        const int ix0 = GEN ? xq * g.SX + (px ? g.OX1 : g.OX0) : xq * g.SY + (px ? g.OY1 : g.OY0);
+        const int pix0 = (GEN ? b * g.inB + g.in0 : b * g.Cin * ihw) + iy0 * g.IW + ix0;
         int r = 0, q = akg;                       // this thread fills taps akg, akg + NG, ... (q may start beyond S: normalise)
         while (q >= g.S) { q -= g.S; ++r; }
         for (int t = akg; t < g.RS; t += NG) {
@@ -255,13 +261,13 @@ __global__ __launch_bounds__(256, AGAN_GATHER_WAVES) void conv_gather_f32_kernel
     const bool typed = (ODT != AGAN_DT_F32) && (ksplit == 1);
     const unsigned esz = typed ? 2u : 4u;
     float* dst = (ksplit > 1) ? static_cast<float*>(out_v) + (size_t)split * slab : static_cast<float*>(out_v);
-    const __amdgpu_buffer_rsrc_t rout = make_rsrc(dst, (size_t)g.B * g.Cout * ohw * esz);
+    const __amdgpu_buffer_rsrc_t rout = make_rsrc(dst, (size_t)g.B * (GEN ? (size_t)g.outB : g.Cout * ohw) * esz);
     const bool add_bias = (bias != nullptr) && (ksplit == 1);
     const bool lrelu = (act == AGAN_ACT_LRELU) && (ksplit == 1);          // fused LeakyReLU(0.2) (a split launch applies it in the slab sum)
     // data-gradient launches: out *= LeakyReLU'(mask) where mask is the tensor the output is the gradient OF (same shape) -- the
     // backward of the activation that produced this conv's input, folded into the epilogue instead of a separate pass
     const bool masked = (lrelu_mask != nullptr) && (ksplit == 1);
-    const __amdgpu_buffer_rsrc_t rmask = make_rsrc(masked ? lrelu_mask : (const void*)dst, (size_t)g.B * g.Cout * ohw * esz);
+    const __amdgpu_buffer_rsrc_t rmask = make_rsrc(masked ? lrelu_mask : (const void*)dst, (size_t)g.B * (GEN ? (size_t)g.outB : g.Cout * ohw) * esz);
 #pragma unroll
     for (int tm = 0; tm < TM; ++tm) {
         const int mo = m0 + wm * WTM + tm * 32 + l31;
@@ -269,13 +275,25 @@ __global__ __launch_bounds__(256, AGAN_GATHER_WAVES) void conv_gather_f32_kernel
         const int mm = pvalid ? mo : 0;
         const int b = g.dHWs.div(mm), rem = mm - b * g.HWs;
         const int yq = g.dOWs.div(rem), xq = rem - yq * g.OWs;
-        const unsigned pixoff = (unsigned)(b * g.Cout) * (unsigned)ohw + (unsigned)((yq * g.OS + py) * g.OW + (xq * g.OS + px));
+        const int oy = yq * g.OS + py, ox = xq * g.OS + px;
+        const unsigned pixoff = GEN ? (unsigned)(b * g.outB + g.out0 + oy * g.OW + ox)
+                                    : (unsigned)(b * g.Cout) * (unsigned)ohw + (unsigned)(oy * g.OW + ox);
 #pragma unroll
         for (int tn = 0; tn < TN; ++tn) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int n = n0 + wn * WTN + tn * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
                 float v = acc[tn][tm][r];
+                if (GEN) {
+                    const bool inside = pvalid & (n < g.Cout) & (oy < g.OH) & (ox < g.OW);
+                    const unsigned off = inside ? (pixoff + (unsigned)n * (unsigned)ohw) * 4u : kOOB;
+                    if (bias) v += bias[min(n, g.Cout - 1)];
+                    if (g.relu) v = v < 0.f ? 0.f : v;
+                    if (masked) v = buf_load(rmask, off) > 0.f ? v : 0.f;
+                    if (g.accumulate) v = buf_load(rout, off) + v;
+                    buf_store(rout, off, v);
+                    continue;
+                }
                 if (add_bias) v += bias[min(n, g.Cout - 1)];
                 if (lrelu) v = v > 0.f ? v : 0.2f * v;
                 const unsigned off = (pvalid & (n < g.Cout)) ? (pixoff + (unsigned)n * (unsigned)ohw) * esz : kOOB;
@@ -468,6 +486,23 @@ void launch_gather(const float* in, const float* wk, const float* bias, void* ds
     else
         AGAN_LAUNCH((conv_gather_f32_kernel<128, BN, WM, WN>), grid, dim3(256), 0, st, in, wk, bias, dst, ktab, g, p.ksplit,
                            p.kchunk, p.slab, act, lrelu_mask);
+}
+
+// the general 2-D conv (agan_conv2d_fwd / agan_conv2d_dgrad): one unsplit launch, fp32 output, K tile AGAN_GATHER_BK
+static void launch_gather_2d(const float* in, const float* wk, const float* bias, float* out, const int2* ktab, const Geom& g,
+                             const float* relu_mask, hipStream_t st) {
+    const int bn = g.Cout >= 96 ? 128 : (g.Cout >= 48 ? 64 : 32);
+    dim3 grid(cdiv(g.Mtot, 128), cdiv(g.Cout, bn), g.OS * g.OS);
+    const int kchunk = cdiv(g.K, AGAN_GATHER_BK) * AGAN_GATHER_BK;
+    if (bn == 128)
+        AGAN_LAUNCH((conv_gather_f32_kernel<128, 128, 2, 2, AGAN_DT_F32, true>), grid, dim3(256), 0, st, in, wk, bias, (void*)out, ktab, g, 1,
+                    kchunk, (size_t)0, (int)AGAN_ACT_NONE, (const void*)relu_mask);
+    else if (bn == 64)
+        AGAN_LAUNCH((conv_gather_f32_kernel<128, 64, 2, 2, AGAN_DT_F32, true>), grid, dim3(256), 0, st, in, wk, bias, (void*)out, ktab, g, 1,
+                    kchunk, (size_t)0, (int)AGAN_ACT_NONE, (const void*)relu_mask);
+    else
+        AGAN_LAUNCH((conv_gather_f32_kernel<128, 32, 4, 1, AGAN_DT_F32, true>), grid, dim3(256), 0, st, in, wk, bias, (void*)out, ktab, g, 1,
+                    kchunk, (size_t)0, (int)AGAN_ACT_NONE, (const void*)relu_mask);
 }
 
 // ================================================================================================
@@ -1089,6 +1124,7 @@ size_t agan_packed_weight_bytes(int mode, int cout, int cin, int kh, int kw, int
     int ncls, K, N;
     if (pack_dims(mode, cout, cin, kh, kw, ncls, K, N)) return 0;
     if (prec == AGAN_PREC_F32) return (size_t)ncls * K * ((N + 31) / 32 * 32) * sizeof(float);
+    if (mode == AGAN_PACK_DGRAD_3x3S2) return 0;                         // fp32 layout only (the general conv runs in fp32)
     if (prec_planes(prec) > 0) return patch_packed_weight_bytes(mode, cout, cin, kh, kw, prec);
     return 0;
 }
@@ -1098,6 +1134,7 @@ int agan_pack_weight(const float* w, void* wkv, int mode, int cout, int cin, int
     AGAN_REQUIRE(w && wkv, "pack_weight: null pointer");
     AGAN_REQUIRE(prec == AGAN_PREC_F32 || prec_planes(prec) > 0, "pack_weight: unknown precision mode %d", prec);
     if (prec != AGAN_PREC_F32) {
+        AGAN_REQUIRE(mode != AGAN_PACK_DGRAD_3x3S2, "pack_weight: AGAN_PACK_DGRAD_3x3S2 has an fp32 layout only");
         AGAN_REQUIRE(pack_dims(mode, cout, cin, kh, kw, ncls, K, N) == 0, "pack_weight: mode %d does not take %dx%d", mode, kh, kw);
         return pack_weight_patch(w, wkv, mode, cout, cin, kh, kw, prec, as_stream(stream));
     }
@@ -1378,6 +1415,126 @@ int agan_bias_grad(const float* dy, float* dbias, int B, int C, int HW, int accu
     AGAN_REQUIRE(dy && dbias && B > 0 && C > 0 && HW > 0, "bias_grad: bad argument");
     AGAN_LAUNCH(bias_grad_kernel, dim3(C), dim3(256), 0, as_stream(stream), dy, dbias, B, C, HW, accumulate);
     return check_launch("bias_grad");
+}
+
+// ---- general 2-D conv (agan_conv2d_desc) ----------------------------------------------------------------------------
+// The descriptor maps onto the k-table gather's geometry: the forward gathers x; a stride-1 data gradient gathers dy over the
+// flipped weights (AGAN_PACK_DGRAD_S1) with offset -(K-1-P) per axis; the 3x3 stride-2 unpadded data gradient splits dx into its 4
+// parity classes of 2x2 taps (AGAN_PACK_DGRAD_3x3S2: class 0 reads dy rows q-1, q with taps 2, 0; class 1 row q with tap 1, plus a
+// zero-weight tap), ceil(IH/2) x ceil(IW/2) class grids whose overhang row / column is dropped.
+static int conv2d_geom(const agan_conv2d_desc* d, int dgrad, Geom& g, int& pack_mode) {
+    AGAN_REQUIRE(d != nullptr, "conv2d: null descriptor");
+    AGAN_REQUIRE(d->B > 0 && d->Cin > 0 && d->IH > 0 && d->IW > 0 && d->Cout > 0 && d->OH > 0 && d->OW > 0, "conv2d: non-positive dimension");
+    AGAN_REQUIRE(d->KH > 0 && d->KW > 0 && d->KH * d->KW <= kMaxTaps2d, "conv2d: %dx%d taps unsupported (at most %d)", d->KH, d->KW, kMaxTaps2d);
+    AGAN_REQUIRE((d->SH == 1 || d->SH == 2) && (d->SW == 1 || d->SW == 2), "conv2d: strides %dx%d unsupported (1 or 2 per axis)", d->SH, d->SW);
+    AGAN_REQUIRE(d->PH >= 0 && d->PW >= 0 && d->PH < d->KH && d->PW < d->KW, "conv2d: padding %dx%d unsupported for %dx%d taps", d->PH, d->PW,
+                 d->KH, d->KW);
+    AGAN_REQUIRE(d->OH == (d->IH + 2 * d->PH - d->KH) / d->SH + 1 && d->OW == (d->IW + 2 * d->PW - d->KW) / d->SW + 1 &&
+                     d->IH + 2 * d->PH >= d->KH && d->IW + 2 * d->PW >= d->KW,
+                 "conv2d: output %dx%d does not match input %dx%d, taps %dx%d, stride %dx%d, padding %dx%d", d->OH, d->OW, d->IH, d->IW, d->KH,
+                 d->KW, d->SH, d->SW, d->PH, d->PW);
+    AGAN_REQUIRE(d->in_c0 >= 0 && d->in_c0 + d->Cin <= d->in_ctot && d->out_c0 >= 0 && d->out_c0 + d->Cout <= d->out_ctot,
+                 "conv2d: channel slice out of range (in %d+%d of %d, out %d+%d of %d)", d->in_c0, d->Cin, d->in_ctot, d->out_c0, d->Cout,
+                 d->out_ctot);
+    const long long xe = 1LL * d->B * d->in_ctot * d->IH * d->IW, ye = 1LL * d->B * d->out_ctot * d->OH * d->OW;
+    AGAN_REQUIRE(xe < (1LL << 30) && ye < (1LL << 30), "conv2d: tensor exceeds 2^30 elements (32-bit buffer offsets)");
+    Geom& r = g;
+    r = Geom{};
+    r.B = d->B;
+    r.DY = 1;
+    const int xhw = d->IH * d->IW, yhw = d->OH * d->OW;
+    if (!dgrad) {
+        r.Cin = d->Cin; r.IH = d->IH; r.IW = d->IW; r.Cout = d->Cout; r.OH = d->OH; r.OW = d->OW;
+        r.R = d->KH; r.S = d->KW; r.OS = 1; r.SY = d->SH; r.SX = d->SW;
+        r.OY0 = r.OY1 = -d->PH; r.OX0 = r.OX1 = -d->PW;
+        r.in0 = d->in_c0 * xhw; r.inB = d->in_ctot * xhw; r.out0 = d->out_c0 * yhw; r.outB = d->out_ctot * yhw;
+        pack_mode = AGAN_PACK_FWD;
+    } else {
+        r.Cin = d->Cout; r.IH = d->OH; r.IW = d->OW; r.Cout = d->Cin; r.OH = d->IH; r.OW = d->IW;
+        r.in0 = d->out_c0 * yhw; r.inB = d->out_ctot * yhw; r.out0 = d->in_c0 * xhw; r.outB = d->in_ctot * xhw;
+        r.SY = r.SX = 1;
+        if (d->SH == 1 && d->SW == 1) {
+            r.R = d->KH; r.S = d->KW; r.OS = 1;
+            r.OY0 = r.OY1 = -(d->KH - 1 - d->PH); r.OX0 = r.OX1 = -(d->KW - 1 - d->PW);
+            pack_mode = AGAN_PACK_DGRAD_S1;
+        } else {
+            AGAN_REQUIRE(d->SH == 2 && d->SW == 2 && d->KH == 3 && d->KW == 3 && d->PH == 0 && d->PW == 0,
+                         "conv2d: no data-gradient decomposition for %dx%d taps, stride %dx%d, padding %dx%d (stride 2: 3x3 unpadded only)",
+                         d->KH, d->KW, d->SH, d->SW, d->PH, d->PW);
+            r.R = r.S = 2; r.OS = 2;
+            r.OY0 = r.OX0 = -1; r.OY1 = r.OX1 = 0;
+            pack_mode = AGAN_PACK_DGRAD_3x3S2;
+        }
+    }
+    r.OHs = cdiv(r.OH, r.OS); r.OWs = cdiv(r.OW, r.OS); r.HWs = r.OHs * r.OWs; r.Mtot = r.B * r.HWs;
+    r.RS = r.R * r.S; r.K = r.Cin * r.RS; r.Nld = agan_round_up(r.Cout, 32);
+    r.dHWs = make_fastdiv((unsigned)r.HWs); r.dOWs = make_fastdiv((unsigned)r.OWs);
+    return AGAN_OK;
+}
+
+int agan_conv2d_pack_mode(const agan_conv2d_desc* d, int dgrad) {
+    Geom g;
+    int mode = -1;
+    if (int e = conv2d_geom(d, dgrad, g, mode)) return e;
+    return mode;
+}
+
+int agan_conv2d_effective_prec(const agan_conv2d_desc* d, int prec) {
+    (void)prec;
+    Geom g;
+    int mode = -1;
+    if (int e = conv2d_geom(d, 0, g, mode)) return e;
+    return AGAN_PREC_F32;         // no 16-bit kernel takes these geometries: fp32 products in every mode
+}
+
+size_t agan_conv2d_ws_bytes(const agan_conv2d_desc* d, int dgrad) {
+    (void)d; (void)dgrad;
+    return 0;                     // the general conv launches unsplit
+}
+
+size_t agan_conv2d_ktable_elems(const agan_conv2d_desc* d, int dgrad) {
+    Geom g;
+    int mode = -1;
+    if (conv2d_geom(d, dgrad, g, mode)) return 0;
+    return (size_t)ktable_entries(g.K) * 4;
+}
+
+int agan_conv2d_ktable(const agan_conv2d_desc* d, int dgrad, int32_t* table, void* stream) {
+    Geom g;
+    int mode = -1;
+    if (int e = conv2d_geom(d, dgrad, g, mode)) return e;
+    AGAN_REQUIRE(table != nullptr, "conv2d_ktable: null pointer");
+    const int n = ktable_entries(g.K);
+    AGAN_LAUNCH(ktable_kernel, dim3(cdiv(n, 256)), dim3(256), 0, as_stream(stream), reinterpret_cast<int2*>(table), n, g.K, g.RS, g.S,
+                g.IH * g.IW, g.IW, g.DY);
+    return check_launch("conv2d_ktable");
+}
+
+int agan_conv2d_fwd(const float* x, const void* wkv, const float* bias, float* y, const agan_conv2d_desc* d, const int32_t* ktable, int act,
+                    void* ws, size_t ws_bytes, void* stream) {
+    (void)ws; (void)ws_bytes;
+    Geom g;
+    int mode = -1;
+    if (int e = conv2d_geom(d, 0, g, mode)) return e;
+    AGAN_REQUIRE(x && wkv && y && ktable, "conv2d_fwd: null pointer");
+    const float* wk = static_cast<const float*>(wkv);
+    AGAN_REQUIRE(act == AGAN_ACT_NONE || act == AGAN_ACT_RELU, "conv2d_fwd: activation %d unsupported (none or ReLU)", act);
+    g.relu = act == AGAN_ACT_RELU;
+    hipStream_t st = as_stream(stream);
+    return launch_main(st, 1, "conv2d_fwd", [&] { launch_gather_2d(x, wk, bias, y, reinterpret_cast<const int2*>(ktable), g, nullptr, st); });
+}
+
+int agan_conv2d_dgrad(const float* dy, const void* wkv, float* dx, const agan_conv2d_desc* d, const int32_t* ktable, const float* relu_mask,
+                      int accumulate, void* ws, size_t ws_bytes, void* stream) {
+    (void)ws; (void)ws_bytes;
+    Geom g;
+    int mode = -1;
+    if (int e = conv2d_geom(d, 1, g, mode)) return e;
+    AGAN_REQUIRE(dy && wkv && dx && ktable, "conv2d_dgrad: null pointer");
+    const float* wk = static_cast<const float*>(wkv);
+    g.accumulate = accumulate != 0;
+    hipStream_t st = as_stream(stream);
+    return launch_main(st, 1, "conv2d_dgrad", [&] { launch_gather_2d(dy, wk, nullptr, dx, reinterpret_cast<const int2*>(ktable), g, relu_mask, st); });
 }
 
 }  // extern "C"

@@ -39,6 +39,11 @@ struct Geom {
     int B, Cin, IH, IW, Cout, OH, OW, R, S, OS, SY, DY, OY0, OY1;
     int OHs, OWs, HWs, Mtot, K, Nld, RS;
     FastDiv dHWs, dOWs;
+    // general 2-D conv (agan_conv2d_*; read only by the GEN instantiation of the k-table gather): x step / offsets, channel-slice
+    // addressing (element offset of the first channel and batch stride of the gathered / produced tensor), epilogue flags
+    int SX, OX0, OX1;
+    int in0, inB, out0, outB;
+    int relu, accumulate;
 };
 
 // Reduction-index table: entry k = (ci, r, s) -> { element offset ci*IH*IW + r*DY*IW + s*DY , packed (dy = r*DY, dx = s*DY) }.
@@ -47,6 +52,7 @@ struct Geom {
 constexpr int kTabPad = 128;
 constexpr int kSentinelDy = -32768;
 constexpr int kMaxTaps = 16;           // taps per class the gather kernels' LDS tap table holds (RS <= 16: up to 4x4)
+constexpr int kMaxTaps2d = 25;        // ... and the GEN instantiation of agan_conv2d_* (up to 5x5)
 constexpr int kTapRowBytes = 128 * 4;  // one tap row = 128 pixels of a workgroup tile
 // weight-gradient kernels add a per-lane channel offset to the tabulated tap offset, so their out-of-range marker must
 // survive that add without wrapping: tensors on that path stay below 2^31 bytes (checked on the host)
@@ -60,6 +66,9 @@ inline Geom make_geom(const agan_conv_geom* g) {
     d.OHs = g->OH / g->OS; d.OWs = g->OW / g->OS; d.HWs = d.OHs * d.OWs; d.Mtot = g->B * d.HWs;
     d.RS = g->R * g->S; d.K = g->Cin * d.RS; d.Nld = agan_round_up(g->Cout, 32);
     d.dHWs = make_fastdiv((unsigned)d.HWs); d.dOWs = make_fastdiv((unsigned)d.OWs);
+    d.SX = d.SY; d.OX0 = d.OY0; d.OX1 = d.OY1;
+    d.in0 = 0; d.inB = d.Cin * d.IH * d.IW; d.out0 = 0; d.outB = d.Cout * d.OH * d.OW;
+    d.relu = 0; d.accumulate = 0;
     return d;
 }
 
@@ -126,6 +135,11 @@ __device__ inline float packed_weight_value_f(W4 w4, int mode, int cls, int k, i
         const int py = cls >> 1, px = cls & 1, co = k >> 2, r = (k >> 1) & 1, s = k & 1;
         const int th = ((py + 1) & 1) + 2 * r, tw = ((px + 1) & 1) + 2 * s;
         if (n < cin) v = w4(co, n, th, tw);
+    } else if (mode == AGAN_PACK_DGRAD_3x3S2) {
+        // cls = (py,px); k = (co, r, s) with r,s in {0,1}; n = ci; class 0 taps {2, 0}, class 1 taps {1, none (zero weight)}
+        const int py = cls >> 1, px = cls & 1, co = k >> 2, r = (k >> 1) & 1, s = k & 1;
+        const int th = py ? (r ? -1 : 1) : 2 - 2 * r, tw = px ? (s ? -1 : 1) : 2 - 2 * s;
+        if (n < cin && th >= 0 && tw >= 0) v = w4(co, n, th, tw);
     } else if (mode == AGAN_PACK_UP_FWD) {
         // cls = (py,px); k = (ci, r', s'); n = co
         const int py = cls >> 1, px = cls & 1, ci = k >> 2, r = (k >> 1) & 1, s = k & 1;
@@ -167,6 +181,7 @@ __host__ __device__ inline int pack_dims(int mode, int cout, int cin, int kh, in
         case AGAN_PACK_DGRAD_4x4S2: if (kh != 4 || kw != 4) return -1; ncls = 4; K = cout * 4; N = cin; return 0;
         case AGAN_PACK_UP_FWD: if (kh != 3 || kw != 3) return -1; ncls = 4; K = cin * 4; N = cout; return 0;
         case AGAN_PACK_UP_DGRAD: if (kh != 3 || kw != 3) return -1; ncls = 1; K = cout * 16; N = cin; return 0;
+        case AGAN_PACK_DGRAD_3x3S2: if (kh != 3 || kw != 3) return -1; ncls = 4; K = cout * 4; N = cin; return 0;
     }
     return -1;
 }

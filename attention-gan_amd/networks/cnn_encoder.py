@@ -6,7 +6,7 @@ What the training step needs from the encoder is only its output contract
 
 with gradients flowing back to the images.  The reference's CNNEncoder is a frozen torchvision Inception-v3 trunk with
 weights downloaded at construction (cnn_encoder.py:26-27): third-party, not constructible offline, and outside the
-hand-written-kernel scope.  Two implementations of the contract live here, both on stock
+hand-written-kernel scope.  Two implementations of the contract live here, by default both on stock
 PyTorch-ROCm ops (MIOpen convolutions) on the same device/stream as the HIP path:
 
 * `CNNEncoder(out_dim)` -- an Inception-v3-shaped trunk written from the published architecture (Szegedy et al. 2016),
@@ -14,6 +14,12 @@ PyTorch-ROCm ops (MIOpen convolutions) on the same device/stream as the HIP path
   supplied `inception_v3_google-*.pth` can be loaded with `load_trunk_state_dict()`; nothing is ever fetched.  Heads
   `emb_features` (conv1x1 768->out_dim, no bias) and `emb_cnn_code` (Linear 2048->out_dim) with uniform(-0.1, 0.1) init
   follow the reference (:56-63).  Parity of the trunk against torchvision is UNPINNED here (torchvision is not installed).
+  `CNNEncoder(out_dim, backend="hip")` runs the same module in EVAL mode on the library's kernels instead: every eval-mode
+  BatchNorm folded into its conv (weights + bias, ReLU epilogue), the layer plan of networks/inception_plan.py on the general 2-D
+  conv, pool and resize kernels (include/agan.h: agan_conv2d_*, agan_maxpool3s2_* ...), fp32 in every precision mode; the heads on
+  functional.conv2d / functional.linear.  In TRAIN mode (batch statistics, e.g. a DAMSM pretrain step) `backend="hip"` runs the
+  stock path below unchanged: train-mode BatchNorm of the trunk is not on the library.  `backend` is an attribute and can be
+  switched; the state_dict keys are the same for both.
 * `StandInImageEncoder(out_dim)` -- a deliberately tiny frozen map honouring only the contract (adaptive 17x17 average pool
   -> 1x1 projection; region mean -> linear).  bench.py's default: its FLOPs are negligible, i.e. the timed step is the hot
   path of SURVEY.md §8d (which prices the trunk separately); `bench.py --image-encoder inception` times the full trunk too.
@@ -161,9 +167,12 @@ class CNNEncoder(nn.Module):
     """Drop-in for the reference CNNEncoder: same attribute names (`Conv2d_1a_3x3` ... `Mixed_7c`, `emb_features`,
     `emb_cnn_code`), `freeze_all_weights()`, and `forward(x) -> (features [B,out_dim,17,17], cnn_code [B,out_dim])`."""
 
-    def __init__(self, out_dim: int = 256):
+    BACKENDS = ("torch", "hip")
+
+    def __init__(self, out_dim: int = 256, backend: str = "torch"):
         super().__init__()
         self.out_dim = out_dim
+        self.backend = backend
         self.Conv2d_1a_3x3 = _ConvBNReLU(3, 32, 3, 2)
         self.Conv2d_2a_3x3 = _ConvBNReLU(32, 32, 3)
         self.Conv2d_2b_3x3 = _ConvBNReLU(32, 64, 3, 1, 1)
@@ -190,7 +199,30 @@ class CNNEncoder(nn.Module):
         own = self.state_dict()
         self.load_state_dict({k: v for k, v in state.items() if k in own and not k.startswith("emb_")}, strict=False)
 
+    @property
+    def backend(self) -> str:
+        return self._backend
+
+    @backend.setter
+    def backend(self, value: str) -> None:
+        if value not in self.BACKENDS:
+            raise ValueError(f"CNNEncoder backend must be one of {self.BACKENDS}, got {value!r}")
+        self._backend = value
+
     def forward(self, x: Tensor) -> Tuple[Tensor, Tensor]:
+        if self._backend == "hip" and not self.training:
+            return self._forward_hip(x)
+        return self._forward_torch(x)
+
+    def _forward_hip(self, x: Tensor) -> Tuple[Tensor, Tensor]:
+        """eval mode on the library: folded trunk (functional.inception_trunk) + the heads as a 1x1 conv and a linear layer"""
+        from ..backend import functional as AF
+        x6e, pooled = AF.inception_trunk(x, self)
+        cache = self.__dict__.setdefault("_agan_head_cache", ({}, {}))
+        features = AF.conv2d(x6e, self.emb_features.weight, None, "same", cache[0])
+        return features, AF.linear(pooled, self.emb_cnn_code.weight, self.emb_cnn_code.bias, cache[1])
+
+    def _forward_torch(self, x: Tensor) -> Tuple[Tensor, Tensor]:
         x = F.interpolate(x, size=(299, 299), mode="bilinear", align_corners=False)      # :75
         x = self.Conv2d_2b_3x3(self.Conv2d_2a_3x3(self.Conv2d_1a_3x3(x)))
         x = F.max_pool2d(x, 3, 2)

@@ -30,6 +30,9 @@ extern "C" {
  * version change: a caller built against the 100 header must be rebuilt -- bind by version, backend/lib.py asserts it);
  * agan_allreduce_bucket_dt + agan_exchange_* (16-bit wire format of the gradient exchange); amax slots of agan_conv_wgrad are
  * needed whenever agan_conv_wgrad_effective_prec says AGAN_PREC_F16X3, which includes AGAN_PREC_BF16X6 callers. */
+/* Added within 101 without changing any existing argument list or enum value (a binding written against the earlier 101 header keeps
+ * working unchanged): the general 2-D conv (agan_conv2d_*), AGAN_PACK_DGRAD_3x3S2, AGAN_ACT_RELU and the pools / bilinear resize of the
+ * Inception-v3 image-encoder trunk (agan_maxpool3s2_*, agan_avgpool3s1_*, agan_global_avgpool_*, agan_resize_bilinear_*, agan_relu_bwd). */
 
 enum {
     AGAN_OK = 0,
@@ -96,7 +99,9 @@ enum {
     AGAN_PACK_DGRAD_S1 = 1,  /* dgrad of a stride-1 'same' conv: wk[(co,r,s)][ci] = w[co][ci][KH-1-r][KW-1-s]              */
     AGAN_PACK_DGRAD_4x4S2 = 2,/* dgrad of conv4x4 s2 p1 as 4 parity classes of 2x2 taps                                     */
     AGAN_PACK_UP_FWD = 3,    /* Upsample(x2 nearest)+conv3x3 (layers.py:64-65) folded into 4 parity classes of 2x2 taps    */
-    AGAN_PACK_UP_DGRAD = 4   /* its dgrad folded into one 4x4 stride-2 conv over dY                                         */
+    AGAN_PACK_UP_DGRAD = 4,  /* its dgrad folded into one 4x4 stride-2 conv over dY                                         */
+    AGAN_PACK_DGRAD_3x3S2 = 5/* dgrad of conv3x3 s2 p0 (agan_conv2d_dgrad) as 4 parity classes of 2x2 taps, zero-weight padded
+                                (class 0: taps {2,0}, class 1: taps {1,-}); fp32 layout only                              */
 };
 
 /* Packed size in BYTES for a precision mode: AGAN_PREC_F32 -> fp32 [cls][K][Nld];  the 16-bit modes -> [cls][k-step][plane][Nld][16]
@@ -208,7 +213,7 @@ int agan_bias_grad(const float* dy, float* dbias, int B, int C, int HW, int accu
 /* ------------------------------------------------------------------------------------------------
  * Train-mode BatchNorm + activation (utilities/layers.py:66-67,123-124,143-144,164-174; generator_submodules.py:38)
  * ---------------------------------------------------------------------------------------------- */
-enum { AGAN_ACT_NONE = 0, AGAN_ACT_GLU = 1, AGAN_ACT_LRELU = 2, AGAN_ACT_TANH = 3, AGAN_ACT_SIGMOID = 4 };
+enum { AGAN_ACT_NONE = 0, AGAN_ACT_GLU = 1, AGAN_ACT_LRELU = 2, AGAN_ACT_TANH = 3, AGAN_ACT_SIGMOID = 4, AGAN_ACT_RELU = 5 };
 
 /* batch statistics over (B, HW) per channel: mean[C], invstd[C] = 1/sqrt(biased var + eps).  If running_mean is
  * non-NULL also does running = (1-momentum)*running + momentum*stat (unbiased var) and ++*num_batches_tracked. */
@@ -396,6 +401,66 @@ int agan_exchange_unpack_bf16(const void* wire, float* g, size_t n, void* stream
 /* the reduce-scatter / all-gather chunk of a bucket of n floats over `world` ranks (rank r owns elements [r*chunk, (r+1)*chunk));
  * 0 = the bucket does not split into 16-byte aligned equal chunks and goes out as one library all-reduce.  Pure host arithmetic. */
 size_t agan_allreduce_chunk_elems(size_t n, int world);
+
+/* ------------------------------------------------------------------------------------------------
+ * General 2-D convolution (the frozen Inception-v3 image-encoder trunk, reference networks/cnn_encoder.py:65-101): per-axis taps,
+ * stride and padding, channel-slice addressing on both sides.  fp32 products and storage in every precision mode
+ * (agan_conv2d_effective_prec says AGAN_PREC_F32); runs on the k-table MFMA gather (csrc/conv.hip, conv routing rule 5).
+ *
+ *   y[b, out_c0 + n, oy, ox] = act(bias[n] + sum_{c<Cin, r<KH, s<KW} x[b, in_c0 + c, oy*SH + r - PH, ox*SW + s - PW] * w[n][c][r][s])
+ *
+ * x is [B, in_ctot, IH, IW], y is [B, out_ctot, OH, OW] (a branch of a block writes its channel range of the block output).
+ * SH, SW in {1, 2}; KH*KW <= 25; 0 <= P < K per axis; OH, OW as F.conv2d computes them.  The data gradient
+ *   dx[b, in_c0 + c, ...] (+)= ReLU'(relu_mask) * conv_transpose(dy[b, out_c0 + n, ...])
+ * exists for stride 1 (the gather over flipped weights with padding K-1-P) and for 3x3 stride 2 unpadded (4 parity classes of 2x2
+ * taps); any other stride-2 data gradient is AGAN_EINVAL.  dgrad = 0 / 1 below selects the direction.
+ *   - weights: pack the OIHW weight with agan_pack_weight(mode = agan_conv2d_pack_mode(d, dgrad), prec = AGAN_PREC_F32);
+ *   - k-table: agan_conv2d_ktable into agan_conv2d_ktable_elems int32s, once per descriptor and direction;
+ *   - act: AGAN_ACT_NONE or AGAN_ACT_RELU (after the bias); bias may be NULL;
+ *   - relu_mask (optional, data gradient): a tensor laid out like dx (the forward input, same slice); dx is zeroed where mask <= 0;
+ *   - accumulate != 0: dx += gradient (a tensor several branches read: the first writes, the others add, in launch order).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct agan_conv2d_desc {
+    int32_t B;
+    int32_t Cin, IH, IW;          /* forward input  (the channels this conv reads)  */
+    int32_t Cout, OH, OW;         /* forward output (the channels this conv writes) */
+    int32_t KH, KW, SH, SW, PH, PW;
+    int32_t in_c0, in_ctot;       /* x holds in_ctot channels; this conv reads [in_c0, in_c0 + Cin)   */
+    int32_t out_c0, out_ctot;     /* y holds out_ctot channels; this conv writes [out_c0, out_c0 + Cout) */
+} agan_conv2d_desc;
+int agan_conv2d_pack_mode(const agan_conv2d_desc* d, int dgrad);        /* AGAN_PACK_*, or AGAN_EINVAL if no route takes it */
+int agan_conv2d_effective_prec(const agan_conv2d_desc* d, int prec);
+size_t agan_conv2d_ws_bytes(const agan_conv2d_desc* d, int dgrad);
+size_t agan_conv2d_ktable_elems(const agan_conv2d_desc* d, int dgrad);
+int agan_conv2d_ktable(const agan_conv2d_desc* d, int dgrad, int32_t* table, void* stream);
+int agan_conv2d_fwd(const float* x, const void* wk, const float* bias, float* y, const agan_conv2d_desc* d, const int32_t* ktable, int act,
+                    void* ws, size_t ws_bytes, void* stream);
+int agan_conv2d_dgrad(const float* dy, const void* wk, float* dx, const agan_conv2d_desc* d, const int32_t* ktable, const float* relu_mask,
+                      int accumulate, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Pools and resize of the trunk (csrc/pool_resize.hip), NCHW fp32.  Every backward is a gather: each input pixel sums, in a fixed
+ * order, the outputs that read it -- no atomics.  relu_mask (optional) is laid out like dx: dx is zeroed where mask <= 0 (the
+ * derivative of the ReLU that produced the pool's input); accumulate != 0: dx += gradient.
+ *   agan_maxpool3s2_*: 3x3 window, stride 2, no padding, OH = (H-3)/2+1.  Tie-break as torch's: the first maximum in row-major
+ *     window order wins, a NaN wins over every number (a later NaN over an earlier one).  The forward writes the window-local argmax
+ *     (0..8) as one byte per output pixel ([B, C, OH, OW]) and y into channels [out_c0, out_c0 + C) of a [B, out_ctot, OH, OW] tensor;
+ *     the backward reads dy from that slice.
+ *   agan_avgpool3s1_*: 3x3 window, stride 1, padding 1, always divided by 9 (count_include_pad).
+ *   agan_global_avgpool_*: mean over H*W per (b, c): y [B, C].
+ *   agan_resize_bilinear_*: align_corners=False: src = (dst + 0.5) * in / out - 0.5 clamped at 0, upper neighbour clamped to in-1.
+ *   agan_relu_bwd: dx (+)= dy * (y > 0) over n elements.
+ * ---------------------------------------------------------------------------------------------- */
+int agan_maxpool3s2_fwd(const float* x, float* y, uint8_t* argmax, int B, int C, int H, int W, int out_c0, int out_ctot, void* stream);
+int agan_maxpool3s2_bwd(const float* dy, const uint8_t* argmax, const float* relu_mask, float* dx, int B, int C, int H, int W, int out_c0,
+                        int out_ctot, int accumulate, void* stream);
+int agan_avgpool3s1_fwd(const float* x, float* y, int B, int C, int H, int W, void* stream);
+int agan_avgpool3s1_bwd(const float* dy, const float* relu_mask, float* dx, int B, int C, int H, int W, int accumulate, void* stream);
+int agan_global_avgpool_fwd(const float* x, float* y, int B, int C, int HW, void* stream);
+int agan_global_avgpool_bwd(const float* dy, const float* relu_mask, float* dx, int B, int C, int HW, int accumulate, void* stream);
+int agan_resize_bilinear_fwd(const float* x, float* y, int B, int C, int IH, int IW, int OH, int OW, void* stream);
+int agan_resize_bilinear_bwd(const float* dy, float* dx, int B, int C, int IH, int IW, int OH, int OW, void* stream);
+int agan_relu_bwd(const float* y, const float* dy, float* dx, size_t n, int accumulate, void* stream);
 
 #ifdef __cplusplus
 }
