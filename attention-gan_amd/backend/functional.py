@@ -1304,3 +1304,98 @@ def inception_trunk(image: Tensor, module) -> Tuple[Tensor, Tensor]:
     from ..networks.inception_plan import build_plan
     plan = build_plan(image.shape[-2], image.shape[-1])
     return _InceptionTrunkFn.apply(image, module, plan)
+
+
+# --------------------------------------------------------------------------------------------------------------
+# caption encoder (networks/rnn_encoder.py::RNNEncoder, backend="hip"; train and eval mode)
+# --------------------------------------------------------------------------------------------------------------
+# embedding gather -> (the module's dropout) -> input projection per direction on `linear` (packed W_ih cached per direction by
+# packed_weight's rule; fp32: a linear layer is a 1x1 geometry, which every precision mode runs in fp32) -> one recurrence launch
+# for both directions (agan_lstm_fwd).  Backward: agan_lstm_bwd (gate gradients) + agan_lstm_wgrad (W_hh, b_hh), the projections'
+# own backward (W_ih, b_ih, data) and agan_embedding_bwd.  Nothing is atomic.
+class _EmbeddingFn(Function):
+    @staticmethod
+    def forward(ctx, weight: Tensor, ids: Tensor, T: int):
+        w = _dev(weight.detach(), "embedding weight")
+        if not ids.is_cuda or ids.dtype != torch.int64 or ids.dim() != 2 or ids.stride(1) != 1:
+            raise L.AganError(f"embedding: ids must be a [B, T] int64 device tensor with unit column stride, got {ids.dtype} "
+                              f"{tuple(ids.shape)} on {ids.device}")
+        B = ids.shape[0]
+        V, E = w.shape
+        y = torch.empty(B, T, E, device=w.device)
+        L.call("agan_embedding_fwd", _p(ids), ids.stride(0), _p(w), _p(y), B, T, V, E, _stream())
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(ids)
+        ctx.V = V
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy: Tensor):
+        (ids,) = ctx.saved_tensors
+        dy = _dev(dy, "embedding grad")
+        B, T, E = dy.shape
+        dw = torch.empty(ctx.V, E, device=dy.device)
+        L.call("agan_embedding_bwd", _p(ids), ids.stride(0), _p(dy), _p(dw), B, T, ctx.V, E, _stream())
+        return dw, None, None
+
+
+def embedding(ids: Tensor, weight: Tensor, T: int) -> Tensor:
+    """weight[ids[:, :T]] -> [B, T, E]; an id outside the table gives a zero row (include/agan.h: agan_embedding_fwd)"""
+    return _EmbeddingFn.apply(weight, ids, T)
+
+
+class _LSTMFn(Function):
+    """(lens, save, xg_0, W_hh_0, b_hh_0[, xg_1, W_hh_1, b_hh_1]) -> (out [B, T, D*H], hN [B, D*H])"""
+
+    @staticmethod
+    def forward(ctx, lens: Tensor, save: bool, *tensors: Tensor):
+        D = len(tensors) // 3
+        xg = [_dev(t, "lstm input projection") for t in tensors[0::3]]
+        whh = [_dev(t.detach(), "lstm weight_hh") for t in tensors[1::3]]
+        bhh = [_dev(t.detach(), "lstm bias_hh") for t in tensors[2::3]]
+        B, T, G = xg[0].shape
+        H = G // 4
+        dev = xg[0].device
+        out = torch.empty(B, T, D * H, device=dev)
+        hN = torch.empty(B, D * H, device=dev)
+        gates = torch.empty(D, B, T, G, device=dev) if save else None
+        cells = torch.empty(D, B, T, H, device=dev) if save else None
+        two = D == 2
+        L.call("agan_lstm_fwd", _p(xg[0]), _p(xg[1] if two else None), _p(whh[0]), _p(whh[1] if two else None), _p(bhh[0]),
+               _p(bhh[1] if two else None), _p(lens), _p(out), _p(hN), _p(gates), _p(cells), B, T, H, D, _stream())
+        if save:
+            ctx.save_for_backward(lens, out, gates, cells, *whh)
+        ctx.dims = (B, T, H, D)
+        return out, hN
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout: Optional[Tensor], dhN: Optional[Tensor]):
+        lens, out, gates, cells, *whh = ctx.saved_tensors
+        B, T, H, D = ctx.dims
+        two = D == 2
+        dout = _dev(dout, "lstm grad") if dout is not None else None
+        dhN = _dev(dhN, "lstm grad") if dhN is not None else None
+        dg = torch.empty(D, B, T, 4 * H, device=out.device)
+        L.call("agan_lstm_bwd", _p(dout), _p(dhN), _p(whh[0]), _p(whh[1] if two else None), _p(gates), _p(cells), _p(lens), _p(dg[0]),
+               _p(dg[1] if two else None), B, T, H, D, _stream())
+        need_w = any(ctx.needs_input_grad[3 + 3 * d] or ctx.needs_input_grad[4 + 3 * d] for d in range(D))
+        dwhh = dbhh = None
+        if need_w:
+            dwhh = torch.empty(D, 4 * H, H, device=out.device)
+            dbhh = torch.empty(D, 4 * H, device=out.device)
+            L.call("agan_lstm_wgrad", _p(dg[0]), _p(dg[1] if two else None), _p(out), _p(dwhh), _p(dbhh), B, T, H, D, _stream())
+        grads = []
+        for d in range(D):
+            grads += [dg[d], dwhh[d] if dwhh is not None else None, dbhh[d] if dbhh is not None else None]
+        return (None, None, *grads)
+
+
+def lstm(xg, whh, bhh, lens: Tensor, save: bool) -> Tuple[Tensor, Tensor]:
+    """One LSTM layer over [B, T, 4H] input projections, one per direction (include/agan.h: agan_lstm_fwd).  lens: int32 [B] on
+    the device.  save: keep the gates and cells for a backward (False under no_grad or with everything frozen)."""
+    args = []
+    for x, w, b in zip(xg, whh, bhh):
+        args += [x, w, b]
+    return _LSTMFn.apply(lens, save, *args)

@@ -128,6 +128,11 @@ _SIGNATURES = {
     "agan_resize_bilinear_fwd": (c_int, [_P, _P] + [c_int] * 6 + [_P]),
     "agan_resize_bilinear_bwd": (c_int, [_P, _P] + [c_int] * 6 + [_P]),
     "agan_relu_bwd": (c_int, [_P, _P, _P, c_size_t, c_int, _P]),
+    "agan_embedding_fwd": (c_int, [_P, c_int, _P, _P] + [c_int] * 4 + [_P]),
+    "agan_embedding_bwd": (c_int, [_P, c_int, _P, _P] + [c_int] * 4 + [_P]),
+    "agan_lstm_fwd": (c_int, [_P] * 11 + [c_int] * 4 + [_P]),
+    "agan_lstm_bwd": (c_int, [_P] * 9 + [c_int] * 4 + [_P]),
+    "agan_lstm_wgrad": (c_int, [_P] * 5 + [c_int] * 4 + [_P]),
     "agan_adam_step": (c_int, [_P, _P, _P, _P, c_size_t, _P, c_double, c_double, c_double, c_double, c_float, _P]),
 }
 

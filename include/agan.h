@@ -32,7 +32,8 @@ extern "C" {
  * needed whenever agan_conv_wgrad_effective_prec says AGAN_PREC_F16X3, which includes AGAN_PREC_BF16X6 callers. */
 /* Added within 101 without changing any existing argument list or enum value (a binding written against the earlier 101 header keeps
  * working unchanged): the general 2-D conv (agan_conv2d_*), AGAN_PACK_DGRAD_3x3S2, AGAN_ACT_RELU and the pools / bilinear resize of the
- * Inception-v3 image-encoder trunk (agan_maxpool3s2_*, agan_avgpool3s1_*, agan_global_avgpool_*, agan_resize_bilinear_*, agan_relu_bwd). */
+ * Inception-v3 image-encoder trunk (agan_maxpool3s2_*, agan_avgpool3s1_*, agan_global_avgpool_*, agan_resize_bilinear_*, agan_relu_bwd);
+ * the embedding gather and the LSTM recurrence of the caption encoder (agan_embedding_*, agan_lstm_*). */
 
 enum {
     AGAN_OK = 0,
@@ -461,6 +462,32 @@ int agan_global_avgpool_bwd(const float* dy, const float* relu_mask, float* dx, 
 int agan_resize_bilinear_fwd(const float* x, float* y, int B, int C, int IH, int IW, int OH, int OW, void* stream);
 int agan_resize_bilinear_bwd(const float* dy, float* dx, int B, int C, int IH, int IW, int OH, int OW, void* stream);
 int agan_relu_bwd(const float* y, const float* dy, float* dx, size_t n, int accumulate, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Caption encoder (csrc/lstm.hip; networks/rnn_encoder.py, backend="hip"), fp32 in every precision mode.
+ *   agan_embedding_fwd: y[b, t, :] = table[ids[b * ids_ld + t], :] for t < T (ids_ld >= T: the caption tensor may be wider than the
+ *     longest length).  An id outside [0, V) gives a row of zeros: the table is never read out of bounds.
+ *   agan_embedding_bwd: dense dtable [V, E]: each row sums dy over the (b, t) holding its id in ascending b * T + t, rows no position
+ *     holds are written 0.  No atomics.
+ *   agan_lstm_fwd: one layer, D = 1 or 2 directions (index 1 = reverse), per-direction hidden size H a multiple of 16 in 16..128,
+ *     gate order i, f, g, o and torch's nn.LSTM equations from h = c = 0.  xg_d [B, T, 4H] is x W_ih_d^T + b_ih_d (the caller's input
+ *     projection), whh_d [4H, H], bhh_d [4H], lens [B] int32 on the device (clamped to 0..T).  Row b runs t = 0 .. len-1 (forward) or
+ *     len-1 .. 0 (reverse).  out [B, T, D*H] (direction d in columns d*H ..), 0 at t >= len; hN [B, D*H]: each direction's last h.
+ *     gates [D, B, T, 4H] (post-activation) and cells [D, B, T, H] are what agan_lstm_bwd needs: both null when no backward follows.
+ *   agan_lstm_bwd: backward through time.  dout [B, T, D*H] and dhN [B, D*H] may be null (zero gradient).  Writes dg_d [B, T, 4H], the
+ *     gradient of the gate pre-activations (that of xg_d, and the per-(b, t) terms of b_hh), 0 at t >= len.
+ *   agan_lstm_wgrad: dwhh [D, 4H, H] = sum over b, t of dg_d[b, t]^T h_prev, dbhh [D, 4H] = sum of dg_d, in ascending b then t; h_prev
+ *     is out at t-1 (forward) / t+1 (reverse), 0 outside the sequence.
+ * Every entry returns AGAN_EINVAL with a message for B < 1, T < 1, D outside {1, 2}, an unsupported H or a missing pointer.  One
+ * workgroup owns 4 batch rows of one direction for the whole sequence: no inter-workgroup barrier, no atomics, run-to-run identical.
+ * ---------------------------------------------------------------------------------------------- */
+int agan_embedding_fwd(const int64_t* ids, int ids_ld, const float* table, float* y, int B, int T, int V, int E, void* stream);
+int agan_embedding_bwd(const int64_t* ids, int ids_ld, const float* dy, float* dtable, int B, int T, int V, int E, void* stream);
+int agan_lstm_fwd(const float* xg0, const float* xg1, const float* whh0, const float* whh1, const float* bhh0, const float* bhh1,
+                  const int32_t* lens, float* out, float* hN, float* gates, float* cells, int B, int T, int H, int D, void* stream);
+int agan_lstm_bwd(const float* dout, const float* dhN, const float* whh0, const float* whh1, const float* gates, const float* cells,
+                  const int32_t* lens, float* dg0, float* dg1, int B, int T, int H, int D, void* stream);
+int agan_lstm_wgrad(const float* dg0, const float* dg1, const float* out, float* dwhh, float* dbhh, int B, int T, int H, int D, void* stream);
 
 #ifdef __cplusplus
 }
