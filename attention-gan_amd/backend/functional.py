@@ -1213,37 +1213,88 @@ def _trunk_layer(module, op, device):
     return val
 
 
+def _trunk_forward(image: Tensor, plan, conv_fwd) -> Tuple[Dict[str, Tensor], Dict[int, Tensor]]:
+    """the forward walk of the plan shared by both trunk modes: conv_fwd(i, op, src, dst) runs a conv op, the pools / resize / global
+    mean run here.  -> (every tensor of the plan by name, max-pool argmax bytes by op index)"""
+    B, dev = image.shape[0], image.device
+    st = _stream()
+    T: Dict[str, Tensor] = {"image": image}
+    argmax: Dict[int, Tensor] = {}
+    for i, op in enumerate(plan.ops):
+        dst = T.get(op.dst)
+        if dst is None:
+            t = plan.tensors[op.dst]
+            dst = T[op.dst] = torch.empty((B, t.C) if op.kind == "gap" else (B, t.C, t.H, t.W), device=dev)
+        src = T[op.src]
+        if op.kind == "conv":
+            conv_fwd(i, op, src, dst)
+        elif op.kind == "maxpool":
+            am = argmax[i] = torch.empty(B * op.C * op.OH * op.OW, dtype=torch.uint8, device=dev)
+            L.call("agan_maxpool3s2_fwd", _p(src), _p(dst), _p(am), B, op.C, op.H, op.W, op.out_c0, op.out_ctot, st)
+        elif op.kind == "avgpool":
+            L.call("agan_avgpool3s1_fwd", _p(src), _p(dst), B, op.C, op.H, op.W, st)
+        elif op.kind == "gap":
+            L.call("agan_global_avgpool_fwd", _p(src), _p(dst), B, op.C, op.H * op.W, st)
+        else:   # resize
+            L.call("agan_resize_bilinear_fwd", _p(src), _p(dst), B, op.C, op.H, op.W, op.OH, op.OW, st)
+    return T, argmax
+
+
+def _trunk_backward(plan, B: int, masks: Dict[str, Tensor], argmax: Dict[int, Tensor], g_feat: Optional[Tensor],
+                    g_pooled: Optional[Tensor], conv_bwd) -> Tensor:
+    """the reversed walk of the plan shared by both trunk modes -> the image gradient.  conv_bwd(i, op, gy, gx, mask, acc) runs a conv
+    op's data gradient: gy is the whole gradient of op.dst (the op reads its slice), gx that of op.src, written (acc 0) or added to."""
+    from ..networks.inception_plan import FEATURES, POOLED
+    feat = masks[FEATURES]
+    dev, st = feat.device, _stream()
+    G: Dict[str, Tensor] = {}
+    # the external gradient of the Mixed_6e output seeds its buffer (masked by its ReLU); Mixed_7a's ops then add
+    G[FEATURES] = torch.empty_like(feat)
+    if g_feat is None:
+        G[FEATURES].zero_()
+    else:
+        g_feat = _dev(g_feat, "trunk backward")
+        L.call("agan_relu_bwd", _p(feat), _p(g_feat), _p(G[FEATURES]), feat.numel(), 0, st)
+    G[POOLED] = torch.zeros(B, plan.tensors[POOLED].C, device=dev) if g_pooled is None else _dev(g_pooled, "trunk backward")
+    first_producer = {}
+    for i, op in enumerate(plan.ops):
+        first_producer.setdefault(op.dst, i)
+    for i in range(len(plan.ops) - 1, -1, -1):
+        op = plan.ops[i]
+        gy = G[op.dst] if first_producer[op.dst] != i else G.pop(op.dst)     # (the last reader of this gradient frees it)
+        gx = G.get(op.src)
+        if gx is None:
+            t = plan.tensors[op.src]
+            gx = G[op.src] = torch.empty(B, t.C, t.H, t.W, device=dev)
+        mask = masks.get(op.src)
+        acc = int(op.accumulate)
+        if op.kind == "conv":
+            conv_bwd(i, op, gy, gx, mask, acc)
+        elif op.kind == "maxpool":
+            L.call("agan_maxpool3s2_bwd", _p(gy), _p(argmax[i]), _p(mask), _p(gx), B, op.C, op.H, op.W, op.out_c0, op.out_ctot,
+                   acc, st)
+        elif op.kind == "avgpool":
+            L.call("agan_avgpool3s1_bwd", _p(gy), _p(mask), _p(gx), B, op.C, op.H, op.W, acc, st)
+        elif op.kind == "gap":
+            L.call("agan_global_avgpool_bwd", _p(gy), _p(mask), _p(gx), B, op.C, op.H * op.W, acc, st)
+        else:   # resize: the image is the first and only reader of nothing else -- a plain write
+            L.call("agan_resize_bilinear_bwd", _p(gy), _p(gx), B, op.C, op.H, op.W, op.OH, op.OW, st)
+    return G["image"]
+
+
 class _InceptionTrunkFn(Function):
     """image [B,3,H,W] -> (Mixed_6e output [B,768,17,17], pooled Mixed_7c [B,2048]); backward: the image gradient only."""
 
     @staticmethod
     def forward(ctx, image: Tensor, module, plan):
         image = _dev(image, "inception trunk")
-        B, dev = image.shape[0], image.device
-        st = _stream()
-        _, ws = _ws(0, image)
-        T: Dict[str, Tensor] = {"image": image}
-        argmax: Dict[int, Tensor] = {}
-        for i, op in enumerate(plan.ops):
-            dst = T.get(op.dst)
-            if dst is None:
-                t = plan.tensors[op.dst]
-                dst = T[op.dst] = torch.empty((B, t.C) if op.kind == "gap" else (B, t.C, t.H, t.W), device=dev)
-            src = T[op.src]
-            if op.kind == "conv":
-                d = _conv2d_desc(op, B)
-                bias, wk, _ = _trunk_layer(module, op, dev)
-                L.call("agan_conv2d_fwd", _p(src), _p(wk), _p(bias), _p(dst), byref(d), _p(conv2d_ktable(d, 0, dev)), L.ACT_RELU,
-                       ws, 0, st)
-            elif op.kind == "maxpool":
-                am = argmax[i] = torch.empty(B * op.C * op.OH * op.OW, dtype=torch.uint8, device=dev)
-                L.call("agan_maxpool3s2_fwd", _p(src), _p(dst), _p(am), B, op.C, op.H, op.W, op.out_c0, op.out_ctot, st)
-            elif op.kind == "avgpool":
-                L.call("agan_avgpool3s1_fwd", _p(src), _p(dst), B, op.C, op.H, op.W, st)
-            elif op.kind == "gap":
-                L.call("agan_global_avgpool_fwd", _p(src), _p(dst), B, op.C, op.H * op.W, st)
-            else:   # resize
-                L.call("agan_resize_bilinear_fwd", _p(src), _p(dst), B, op.C, op.H, op.W, op.OH, op.OW, st)
+        B, dev, st = image.shape[0], image.device, _stream()
+
+        def conv_fwd(i, op, src, dst):
+            d = _conv2d_desc(op, B)
+            bias, wk, _ = _trunk_layer(module, op, dev)
+            L.call("agan_conv2d_fwd", _p(src), _p(wk), _p(bias), _p(dst), byref(d), _p(conv2d_ktable(d, 0, dev)), L.ACT_RELU, None, 0, st)
+        T, argmax = _trunk_forward(image, plan, conv_fwd)
         ctx.module, ctx.plan, ctx.B = module, plan, B
         ctx.masks = {n: T[n] for n, t in plan.tensors.items() if t.relu}      # the ReLU outputs: masks of the backward
         ctx.argmax = argmax
@@ -1253,49 +1304,17 @@ class _InceptionTrunkFn(Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, g_feat: Optional[Tensor], g_pooled: Optional[Tensor]):
-        from ..networks.inception_plan import FEATURES, POOLED
         if not ctx.needs_input_grad[0]:
             return None, None, None
-        plan, B, masks = ctx.plan, ctx.B, ctx.masks
-        feat = masks[FEATURES]
-        dev, st = feat.device, _stream()
-        _, ws = _ws(0, feat)
-        G: Dict[str, Tensor] = {}
-        # the external gradient of the Mixed_6e output seeds its buffer (masked by its ReLU); Mixed_7a's ops then add
-        G[FEATURES] = torch.empty_like(feat)
-        if g_feat is None:
-            G[FEATURES].zero_()
-        else:
-            g_feat = _dev(g_feat, "trunk backward")
-            L.call("agan_relu_bwd", _p(feat), _p(g_feat), _p(G[FEATURES]), feat.numel(), 0, st)
-        G[POOLED] = torch.zeros(B, plan.tensors[POOLED].C, device=dev) if g_pooled is None else _dev(g_pooled, "trunk backward")
-        first_producer = {}
-        for i, op in enumerate(plan.ops):
-            first_producer.setdefault(op.dst, i)
-        for i in range(len(plan.ops) - 1, -1, -1):
-            op = plan.ops[i]
-            gy = G[op.dst] if first_producer[op.dst] != i else G.pop(op.dst)     # (the last reader of this gradient frees it)
-            gx = G.get(op.src)
-            if gx is None:
-                t = plan.tensors[op.src]
-                gx = G[op.src] = torch.empty(B, t.C, t.H, t.W, device=dev)
-            mask = masks.get(op.src)
-            acc = int(op.accumulate)
-            if op.kind == "conv":
-                d = _conv2d_desc(op, B)
-                _, _, wkd = _trunk_layer(ctx.module, op, dev)
-                L.call("agan_conv2d_dgrad", _p(gy), _p(wkd), _p(gx), byref(d), _p(conv2d_ktable(d, 1, dev)), _p(mask), acc, ws, 0, st)
-            elif op.kind == "maxpool":
-                L.call("agan_maxpool3s2_bwd", _p(gy), _p(ctx.argmax[i]), _p(mask), _p(gx), B, op.C, op.H, op.W, op.out_c0, op.out_ctot,
-                       acc, st)
-            elif op.kind == "avgpool":
-                L.call("agan_avgpool3s1_bwd", _p(gy), _p(mask), _p(gx), B, op.C, op.H, op.W, acc, st)
-            elif op.kind == "gap":
-                L.call("agan_global_avgpool_bwd", _p(gy), _p(mask), _p(gx), B, op.C, op.H * op.W, acc, st)
-            else:   # resize: the image is the first and only reader of nothing else -- a plain write
-                L.call("agan_resize_bilinear_bwd", _p(gy), _p(gx), B, op.C, op.H, op.W, op.OH, op.OW, st)
+        B, st = ctx.B, _stream()
+
+        def conv_bwd(i, op, gy, gx, mask, acc):
+            d = _conv2d_desc(op, B)
+            _, _, wkd = _trunk_layer(ctx.module, op, gx.device)
+            L.call("agan_conv2d_dgrad", _p(gy), _p(wkd), _p(gx), byref(d), _p(conv2d_ktable(d, 1, gx.device)), _p(mask), acc, None, 0, st)
+        gimg = _trunk_backward(ctx.plan, B, ctx.masks, ctx.argmax, g_feat, g_pooled, conv_bwd)
         ctx.masks = ctx.argmax = None
-        return G["image"], None, None
+        return gimg, None, None
 
 
 def inception_trunk(image: Tensor, module) -> Tuple[Tensor, Tensor]:
@@ -1304,6 +1323,131 @@ def inception_trunk(image: Tensor, module) -> Tuple[Tensor, Tensor]:
     from ..networks.inception_plan import build_plan
     plan = build_plan(image.shape[-2], image.shape[-1])
     return _InceptionTrunkFn.apply(image, module, plan)
+
+
+# ---- train mode: batch-statistics BatchNorm (CNNEncoder(backend="hip", hip_train=True)) ------------------------------------------
+# Each conv runs UNFOLDED (agan_conv2d_fwd, no bias, no activation) into a contiguous raw buffer; agan_bn_relu_slice_fwd takes the batch
+# statistics, updates the running ones and writes relu(BN(raw)) into the conv's slice of its destination.  The backward runs
+# agan_bn_slice_bwd from the slice of the block gradient (already masked by the ReLU) into a scratch buffer, then the unfolded data
+# gradient.  Trunk weights are frozen (no weight gradients); the image gradient is returned.  The unfolded packed weights are cached per
+# conv and direction, keyed on the weight's storage and version -- a cache of their own, apart from the eval fold.
+def _conv2d_raw_desc(op, B: int) -> "L.Conv2dDesc":
+    """the descriptor of a conv that writes all of a contiguous [B, Cout, OH, OW] buffer"""
+    d = _conv2d_desc(op, B)
+    d.out_c0, d.out_ctot = 0, op.Cout
+    return d
+
+
+def _trunk_train_weight(module, op, dgrad: int, device) -> Tensor:
+    """the unfolded conv weight of one conv of the plan, packed for one direction; re-packed when the weight changed"""
+    w = module.get_submodule(op.name).conv.weight
+    ver = (w.data_ptr(), w._version, str(device))
+    cache = module.__dict__.setdefault("_agan_trunk_train_w", {})
+    hit = cache.get((op.name, dgrad))
+    if hit is not None and hit[0] == ver:
+        return hit[1]
+    wk = conv2d_pack(_dev(w.detach(), f"trunk {op.name}"), _conv2d_raw_desc(op, 1), dgrad)
+    cache[(op.name, dgrad)] = (ver, wk)
+    return wk
+
+
+def _bn_buffer(t: Optional[Tensor], dtype, what: str) -> Tensor:
+    """a running-statistics buffer the kernel updates in place: it must already be a contiguous device tensor of `dtype`"""
+    if t is None or not t.is_cuda or t.dtype != dtype or not t.is_contiguous():
+        raise L.AganError(f"{what}: running statistics must be contiguous {dtype} device tensors")
+    return t
+
+
+class _InceptionTrunkTrainFn(Function):
+    """train-mode trunk: image [B,3,H,W] -> (Mixed_6e output, pooled Mixed_7c); the BatchNorm running statistics of `module` are
+    updated; backward: the image gradient only.  `save` False (no_grad, or an image without a gradient) keeps nothing for a backward
+    and reuses one raw buffer for every conv."""
+
+    @staticmethod
+    def forward(ctx, image: Tensor, module, plan, save: bool):
+        image = _dev(image, "inception trunk (train)")
+        B, dev, st = image.shape[0], image.device, _stream()
+        convs = plan.convs()
+        ws_n = max(L.load().agan_bn_relu_slice_fwd_ws_bytes(B, op.Cout, op.OH * op.OW) for op in convs)
+        wst, ws = _ws(ws_n, image)
+        raws: Dict[int, Tensor] = {}
+        stats: Dict[int, Tuple[Tensor, Tensor, Tensor]] = {}
+        bumped = []
+        if not save:
+            raw_scratch = torch.empty(max(B * op.Cout * op.OH * op.OW for op in convs), device=dev)
+            stat_scratch = torch.empty(2, max(op.Cout for op in convs), device=dev)
+
+        def conv_fwd(i, op, src, dst):
+            bn = module.get_submodule(op.name).bn
+            what = f"trunk {op.name}"
+            gamma, beta = _dev(bn.weight.detach(), what), _dev(bn.bias.detach(), what)
+            rm = _bn_buffer(bn.running_mean, torch.float32, what)
+            rv = _bn_buffer(bn.running_var, torch.float32, what)
+            nbt = _bn_buffer(bn.num_batches_tracked, torch.int64, what)
+            d = _conv2d_raw_desc(op, B)
+            HW = op.OH * op.OW
+            if save:
+                raw = raws[i] = torch.empty(B, op.Cout, op.OH, op.OW, device=dev)
+                mean, invstd = torch.empty(op.Cout, device=dev), torch.empty(op.Cout, device=dev)
+                stats[i] = (mean, invstd, gamma)
+            else:
+                raw, mean, invstd = raw_scratch[:B * op.Cout * HW], stat_scratch[0, :op.Cout], stat_scratch[1, :op.Cout]
+            L.call("agan_conv2d_fwd", _p(src), _p(_trunk_train_weight(module, op, 0, dev)), None, _p(raw), byref(d),
+                   _p(conv2d_ktable(d, 0, dev)), L.ACT_NONE, None, 0, st)
+            L.call("agan_bn_relu_slice_fwd", _p(raw), _p(gamma), _p(beta), _p(dst), op.out_c0, op.out_ctot, _p(mean), _p(invstd),
+                   _p(rm), _p(rv), _p(nbt), B, op.Cout, HW, float(bn.eps), float(bn.momentum), ws, ws_n, st)
+            bumped.extend((rm, rv, nbt))
+        T, argmax = _trunk_forward(image, plan, conv_fwd)
+        # the kernels wrote the running statistics behind autograd's back: bump their versions (the eval fold keys on them)
+        torch.autograd.graph.increment_version(bumped)
+        from ..networks.inception_plan import FEATURES, POOLED
+        ctx.plan, ctx.B, ctx.module = plan, B, module
+        if save:
+            # (the Mixed_6e output is also a mask: kept through save_for_backward, as an attribute it would tie the output to its own
+            # graph in a reference cycle that only the garbage collector frees)
+            ctx.masks = {n: T[n] for n, t in plan.tensors.items() if t.relu and n != FEATURES}
+            ctx.save_for_backward(T[FEATURES])
+            ctx.argmax, ctx.raws, ctx.stats = argmax, raws, stats
+        else:
+            ctx.masks = ctx.argmax = ctx.raws = ctx.stats = None
+        return T[FEATURES], T[POOLED]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_feat: Optional[Tensor], g_pooled: Optional[Tensor]):
+        if not ctx.needs_input_grad[0] or ctx.raws is None:
+            return None, None, None, None
+        from ..networks.inception_plan import FEATURES
+        B, st = ctx.B, _stream()
+        feat, = ctx.saved_tensors
+        masks = dict(ctx.masks, **{FEATURES: feat})
+        convs = ctx.plan.convs()
+        dev = feat.device
+        ws_n = max(L.load().agan_bn_slice_bwd_ws_bytes(B, op.Cout, op.OH * op.OW) for op in convs)
+        wst, ws = _ws(ws_n, feat)
+        dz = torch.empty(max(B * op.Cout * op.OH * op.OW for op in convs), device=dev)      # one scratch for every conv
+
+        def conv_bwd(i, op, gy, gx, mask, acc):
+            raw = ctx.raws.pop(i)
+            mean, invstd, gamma = ctx.stats.pop(i)
+            d = _conv2d_raw_desc(op, B)
+            L.call("agan_bn_slice_bwd", _p(raw), _p(gy), op.out_c0, op.out_ctot, _p(mean), _p(invstd), _p(gamma), _p(dz),
+                   B, op.Cout, op.OH * op.OW, ws, ws_n, st)
+            L.call("agan_conv2d_dgrad", _p(dz), _p(_trunk_train_weight(ctx.module, op, 1, dev)), _p(gx), byref(d),
+                   _p(conv2d_ktable(d, 1, dev)), _p(mask), acc, None, 0, st)
+        gimg = _trunk_backward(ctx.plan, B, masks, ctx.argmax, g_feat, g_pooled, conv_bwd)
+        ctx.masks = ctx.argmax = ctx.raws = ctx.stats = None
+        return gimg, None, None, None
+
+
+def inception_trunk_train(image: Tensor, module) -> Tuple[Tensor, Tensor]:
+    """Train-mode Inception-v3 trunk of `module` on the library's kernels: batch-statistics BatchNorm (the running statistics are
+    updated as torch's train-mode BatchNorm does), same outputs as inception_trunk, differentiable w.r.t. the image.  The trunk's
+    parameters must be frozen (no weight gradients)."""
+    from ..networks.inception_plan import build_plan
+    plan = build_plan(image.shape[-2], image.shape[-1])
+    save = torch.is_grad_enabled() and image.requires_grad
+    return _InceptionTrunkTrainFn.apply(image, module, plan, save)
 
 
 # --------------------------------------------------------------------------------------------------------------

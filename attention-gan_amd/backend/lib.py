@@ -128,6 +128,10 @@ _SIGNATURES = {
     "agan_resize_bilinear_fwd": (c_int, [_P, _P] + [c_int] * 6 + [_P]),
     "agan_resize_bilinear_bwd": (c_int, [_P, _P] + [c_int] * 6 + [_P]),
     "agan_relu_bwd": (c_int, [_P, _P, _P, c_size_t, c_int, _P]),
+    "agan_bn_relu_slice_fwd_ws_bytes": (c_size_t, [c_int] * 3),
+    "agan_bn_relu_slice_fwd": (c_int, [_P] * 4 + [c_int] * 2 + [_P] * 5 + [c_int] * 3 + [c_float] * 2 + [_P, c_size_t, _P]),
+    "agan_bn_slice_bwd_ws_bytes": (c_size_t, [c_int] * 3),
+    "agan_bn_slice_bwd": (c_int, [_P, _P, c_int, c_int, _P, _P, _P, _P] + [c_int] * 3 + [_P, c_size_t, _P]),
     "agan_embedding_fwd": (c_int, [_P, c_int, _P, _P] + [c_int] * 4 + [_P]),
     "agan_embedding_bwd": (c_int, [_P, c_int, _P, _P] + [c_int] * 4 + [_P]),
     "agan_lstm_fwd": (c_int, [_P] * 11 + [c_int] * 4 + [_P]),

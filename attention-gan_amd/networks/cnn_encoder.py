@@ -18,8 +18,12 @@ PyTorch-ROCm ops (MIOpen convolutions) on the same device/stream as the HIP path
   BatchNorm folded into its conv (weights + bias, ReLU epilogue), the layer plan of networks/inception_plan.py on the general 2-D
   conv, pool and resize kernels (include/agan.h: agan_conv2d_*, agan_maxpool3s2_* ...), fp32 in every precision mode; the heads on
   functional.conv2d / functional.linear.  In TRAIN mode (batch statistics, e.g. a DAMSM pretrain step) `backend="hip"` runs the
-  stock path below unchanged: train-mode BatchNorm of the trunk is not on the library.  `backend` is an attribute and can be
-  switched; the state_dict keys are the same for both.
+  stock path below unchanged, unless `hip_train=True` (an attribute too, default False): then the train-mode trunk runs on the
+  library as well (functional.inception_trunk_train: unfolded convs, batch-statistics BatchNorm + ReLU written into each branch's
+  channel slice, the running statistics updated as torch does; agan_bn_relu_slice_fwd / agan_bn_slice_bwd).  It needs a frozen trunk
+  (no weight gradients) and BatchNorms with a momentum and running statistics, and raises ValueError otherwise -- nothing falls back.
+  `hip_train` has no effect with backend="torch" or in eval mode.  `backend` is an attribute and can be switched; the state_dict
+  keys are the same for every setting.
 * `StandInImageEncoder(out_dim)` -- a deliberately tiny frozen map honouring only the contract (adaptive 17x17 average pool
   -> 1x1 projection; region mean -> linear).  bench.py's default: its FLOPs are negligible, i.e. the timed step is the hot
   path of SURVEY.md §8d (which prices the trunk separately); `bench.py --image-encoder inception` times the full trunk too.
@@ -169,10 +173,11 @@ class CNNEncoder(nn.Module):
 
     BACKENDS = ("torch", "hip")
 
-    def __init__(self, out_dim: int = 256, backend: str = "torch"):
+    def __init__(self, out_dim: int = 256, backend: str = "torch", hip_train: bool = False):
         super().__init__()
         self.out_dim = out_dim
         self.backend = backend
+        self.hip_train = hip_train
         self.Conv2d_1a_3x3 = _ConvBNReLU(3, 32, 3, 2)
         self.Conv2d_2a_3x3 = _ConvBNReLU(32, 32, 3)
         self.Conv2d_2b_3x3 = _ConvBNReLU(32, 64, 3, 1, 1)
@@ -209,15 +214,43 @@ class CNNEncoder(nn.Module):
             raise ValueError(f"CNNEncoder backend must be one of {self.BACKENDS}, got {value!r}")
         self._backend = value
 
+    @property
+    def hip_train(self) -> bool:
+        return self._hip_train
+
+    @hip_train.setter
+    def hip_train(self, value: bool) -> None:
+        if not isinstance(value, bool):
+            raise ValueError(f"CNNEncoder hip_train must be a bool, got {value!r}")
+        self._hip_train = value
+
     def forward(self, x: Tensor) -> Tuple[Tensor, Tensor]:
         if self._backend == "hip" and not self.training:
             return self._forward_hip(x)
+        if self._backend == "hip" and self._hip_train:
+            return self._forward_hip(x, train=True)
         return self._forward_torch(x)
 
-    def _forward_hip(self, x: Tensor) -> Tuple[Tensor, Tensor]:
-        """eval mode on the library: folded trunk (functional.inception_trunk) + the heads as a 1x1 conv and a linear layer"""
+    def _check_hip_train(self) -> None:
+        """what the train-mode hip trunk cannot do raises instead of falling back"""
+        for name, p in self.named_parameters():
+            if p.requires_grad and not name.startswith("emb_"):
+                raise ValueError(f"CNNEncoder(backend='hip', hip_train=True): trunk parameter {name} requires grad; the library has no "
+                                 f"weight gradient for the trunk's convs (freeze it, e.g. with requires_grad_(False))")
+        for name, m in self.named_modules():
+            if isinstance(m, nn.BatchNorm2d) and (m.momentum is None or not m.track_running_stats):
+                raise ValueError(f"CNNEncoder(backend='hip', hip_train=True): BatchNorm {name} needs a momentum and running statistics "
+                                 f"(momentum=None / track_running_stats=False are not on the library)")
+
+    def _forward_hip(self, x: Tensor, train: bool = False) -> Tuple[Tensor, Tensor]:
+        """on the library: the trunk (eval: folded, functional.inception_trunk; train: batch statistics,
+        functional.inception_trunk_train) + the heads as a 1x1 conv and a linear layer"""
         from ..backend import functional as AF
-        x6e, pooled = AF.inception_trunk(x, self)
+        if train:
+            self._check_hip_train()
+            x6e, pooled = AF.inception_trunk_train(x, self)
+        else:
+            x6e, pooled = AF.inception_trunk(x, self)
         cache = self.__dict__.setdefault("_agan_head_cache", ({}, {}))
         features = AF.conv2d(x6e, self.emb_features.weight, None, "same", cache[0])
         return features, AF.linear(pooled, self.emb_cnn_code.weight, self.emb_cnn_code.bias, cache[1])

@@ -593,8 +593,9 @@ class DAMSMTrainStep(ModelTrainer):
     """One batch of DAMSMTrainer.pretrain_damsm (pretrain_damsm.py:114-134): image encoder on the 256x256 image, text encoder
     on the captions, words + sentence loss (HIP kernels), clip_grad_norm_(RNN, 0.25), one Adam(lr 2e-3, betas (0.5, 0.999))
     over the RNN parameters and the image encoder's trainable heads.  The encoders are the caller's modules: by default stock PyTorch-ROCm
-    ones; `RNNEncoder(..., backend="hip")` runs the text encoder's forward and backward-through-time on the library's kernels (train
-    mode: the image encoder's hip trunk is eval-only, CNNEncoder's train mode is stock)."""
+    ones; `RNNEncoder(..., backend="hip")` runs the text encoder's forward and backward-through-time on the library's kernels, and
+    `CNNEncoder(..., backend="hip", hip_train=True)` the image encoder's train-mode trunk (batch-statistics BatchNorm, running
+    statistics updated; with backend="hip" alone CNNEncoder's train mode is stock)."""
 
     def __init__(self, rnn: Module, cnn: Module, lr: float = 2e-3, rnn_grad_clip: float = 0.25, gamma1: float = 4.0,
                  gamma2: float = 5.0, gamma3: float = 10.0, wlambda: float = 5.0, slambda: float = 5.0):

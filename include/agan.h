@@ -33,7 +33,8 @@ extern "C" {
 /* Added within 101 without changing any existing argument list or enum value (a binding written against the earlier 101 header keeps
  * working unchanged): the general 2-D conv (agan_conv2d_*), AGAN_PACK_DGRAD_3x3S2, AGAN_ACT_RELU and the pools / bilinear resize of the
  * Inception-v3 image-encoder trunk (agan_maxpool3s2_*, agan_avgpool3s1_*, agan_global_avgpool_*, agan_resize_bilinear_*, agan_relu_bwd);
- * the embedding gather and the LSTM recurrence of the caption encoder (agan_embedding_*, agan_lstm_*). */
+ * the embedding gather and the LSTM recurrence of the caption encoder (agan_embedding_*, agan_lstm_*); the train-mode BatchNorm of the
+ * trunk on channel slices (agan_bn_relu_slice_fwd, agan_bn_slice_bwd). */
 
 enum {
     AGAN_OK = 0,
@@ -462,6 +463,27 @@ int agan_global_avgpool_bwd(const float* dy, const float* relu_mask, float* dx, 
 int agan_resize_bilinear_fwd(const float* x, float* y, int B, int C, int IH, int IW, int OH, int OW, void* stream);
 int agan_resize_bilinear_bwd(const float* dy, float* dx, int B, int C, int IH, int IW, int OH, int OW, void* stream);
 int agan_relu_bwd(const float* y, const float* dy, float* dx, size_t n, int accumulate, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Train-mode BatchNorm of the trunk (csrc/bn_slice.hip; CNNEncoder(backend="hip", hip_train=True)): the BatchNorm + ReLU of one conv
+ * whose output feeds a channel slice of a block output.  fp32, per-channel sums in fp64 in a fixed order, no atomics.
+ *   agan_bn_relu_slice_fwd: x is the contiguous raw conv output [B, C, HW].  Batch mean and biased variance per channel ->
+ *     mean[C], invstd[C] = 1/sqrt(var + eps) (for the backward); if running_mean / running_var are non-NULL (together) they are
+ *     updated as torch does (running = (1-momentum)*running + momentum*stat, unbiased variance n/(n-1)), and
+ *     ++*num_batches_tracked if that is non-NULL.  Writes relu(gamma*(x-mean)*invstd + beta) into channels [out_c0, out_c0 + C) of
+ *     a [B, out_ctot, HW] tensor.  B*HW <= 8192 is one launch (no workspace); larger ones agan_bn_stats + an apply pass.
+ *   agan_bn_slice_bwd: the batch-statistics data gradient dx = gamma*invstd*(dy - mean(dy) - xhat*mean(dy*xhat)), xhat =
+ *     (x-mean)*invstd, with dy read from channels [dout_c0, dout_c0 + C) of a [B, dout_ctot, HW] tensor and dx [B, C, HW]
+ *     contiguous.  No activation (the caller masks dy) and no gamma / beta gradients.
+ * Both return AGAN_EINVAL before any device work for a missing pointer, B, C or HW < 1, a negative c0 or c0 + C > ctot.
+ * ---------------------------------------------------------------------------------------------- */
+size_t agan_bn_relu_slice_fwd_ws_bytes(int B, int C, int HW);
+int agan_bn_relu_slice_fwd(const float* x, const float* gamma, const float* beta, float* out, int out_c0, int out_ctot, float* mean,
+                           float* invstd, float* running_mean, float* running_var, int64_t* num_batches_tracked, int B, int C, int HW,
+                           float eps, float momentum, void* ws, size_t ws_bytes, void* stream);
+size_t agan_bn_slice_bwd_ws_bytes(int B, int C, int HW);
+int agan_bn_slice_bwd(const float* x, const float* dout, int dout_c0, int dout_ctot, const float* mean, const float* invstd,
+                      const float* gamma, float* dx, int B, int C, int HW, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Caption encoder (csrc/lstm.hip; networks/rnn_encoder.py, backend="hip"), fp32 in every precision mode.
