@@ -645,18 +645,119 @@ class _ConvFn(Function):
         return dx, dw, db, None, None, None, None, None, None, None
 
 
-def conv_fuses_activation(act: int, cout: int) -> bool:
-    """can conv2d apply `act` in its epilogue? (LeakyReLU on the MFMA paths; include/agan.h: agan_conv_gather)"""
-    return act == L.ACT_LRELU and cout > 4
+# ---- the trainable general conv (include/agan.h: agan_conv2d_train_*): every (kernel, stride, padding) Layers.conv can return ----
+_ANY_DESCS = {}
+
+
+def conv_any_desc(B: int, Cin: int, H: int, W: int, Cout: int, k, stride, padding):
+    """-> (descriptor, observer geometry, workspace bytes of forward / data gradient / weight gradient) of a general conv, cached
+    like conv_geoms.  Raises outside the library's domain (K 1..5, stride 1..3, padding 0..3 per axis): there is no fallback."""
+    key = (B, Cin, H, W, Cout, tuple(k), tuple(stride), tuple(padding))
+    hit = _ANY_DESCS.get(key)
+    if hit is not None:
+        return hit
+    (kh, kw), (sh, sw), (ph, pw) = k, stride, padding
+    oh, ow = (H + 2 * ph - kh) // sh + 1, (W + 2 * pw - kw) // sw + 1
+    d = L.Conv2dDesc(B, Cin, H, W, Cout, oh, ow, kh, kw, sh, sw, ph, pw, 0, Cin, 0, Cout)
+    lib = L.load()
+    if not lib.agan_conv2d_train_supported(byref(d)):
+        raise L.AganError(f"conv k={k} s={stride} p={padding} on {Cin}x{H}x{W}: {lib.agan_last_error().decode()}")
+    g = _geom(B, Cin, H, W, Cout, oh, ow, kh, kw, 1, sh, 1, (-ph, -pw))       # what a launch observer is shown
+    hit = _ANY_DESCS[key] = (d, g, tuple(lib.agan_conv2d_train_ws_bytes(byref(d), i) for i in range(3)))
+    return hit
+
+
+class _ConvAnyFn(Function):
+    """conv2d(kind="any"): forward, data gradient and weight gradient on the general fp32 MFMA engine (csrc/conv_any.hip).
+
+    fp32 products and fp32 tensors in every precision mode.  Under 16-bit activation storage this conv READS AND WRITES fp32: a
+    16-bit input (or incoming gradient) is widened on the way in (_dev), the output and the input gradient are fp32 -- autograd
+    casts the latter back to the input's type."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, weight: Tensor, bias: Optional[Tensor], stride, padding, wdst, bdst):
+        ctx.x_dtype = x.dtype
+        x = _dev(x, "conv input")
+        w = _dev(weight.detach(), "conv weight")
+        B, Cin, H, W = x.shape
+        Cout, Cin_w, kh, kw = w.shape
+        if Cin != Cin_w:
+            raise L.AganError(f"conv: input has {Cin} channels, weight {tuple(w.shape)}")
+        d, g, nbytes = conv_any_desc(B, Cin, H, W, Cout, (kh, kw), stride, padding)
+        b = _dev(bias.detach(), "conv bias") if bias is not None else None
+        out = torch.empty((B, Cout, d.OH, d.OW), dtype=torch.float32, device=x.device)
+        ws, wsp = _ws(nbytes[0], x)
+        obs = _OBSERVER[0]
+        if obs is not None:
+            obs.begin("any", "fwd", g, 4, 4)
+        L.call("agan_conv2d_train_fwd", _p(x), _p(w), _p(b), _p(out), byref(d), wsp, nbytes[0], _stream())
+        if obs is not None:
+            obs.end()
+        ctx.save_for_backward(x, w)
+        ctx.stride, ctx.padding, ctx.has_bias, ctx.wdst, ctx.bdst = stride, padding, bias is not None, wdst, bdst
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy: Tensor):
+        x, w = ctx.saved_tensors
+        dy = _dev(dy, "conv grad")
+        B, Cin, H, W = x.shape
+        Cout, _, kh, kw = w.shape
+        d, g, nbytes = conv_any_desc(B, Cin, H, W, Cout, (kh, kw), ctx.stride, ctx.padding)
+        dx = dw = db = None
+        want_w, want_b = ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
+        obs = _OBSERVER[0]
+        side = None
+        if _WGRAD_SIDE[0] and want_w and ctx.wdst is not None and (not want_b or ctx.bdst is not None):
+            side = _fork_side_stream()                 # dy is ready on the current stream at this point
+            x.record_stream(side)
+            dy.record_stream(side)
+        with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
+            if want_w:
+                dwbuf, wacc, dw = _grad_out(ctx.wdst, w.shape, x)
+                ws, wsp = _ws(nbytes[2], x)
+                if obs is not None:
+                    obs.begin("any", "wgrad", g, 4, 4)
+                L.call("agan_conv2d_train_wgrad", _p(x), _p(dy), _p(dwbuf), byref(d), wacc, wsp, nbytes[2], _stream())
+                if obs is not None:
+                    obs.end()
+            if want_b:
+                dbbuf, bacc, db = _grad_out(ctx.bdst, (Cout,), x)
+                L.call("agan_bias_grad", _p(dy), _p(dbbuf), B, Cout, dy.shape[2] * dy.shape[3], bacc, _stream())
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+            ws, wsp = _ws(nbytes[1], x)
+            if obs is not None:
+                obs.begin("any", "dgrad", g, 4, 4)
+            L.call("agan_conv2d_train_dgrad", _p(dy), _p(w), _p(dx), byref(d), 0, wsp, nbytes[1], _stream())
+            if obs is not None:
+                obs.end()
+            if ctx.x_dtype != torch.float32:
+                dx = dx.to(ctx.x_dtype)
+        return dx, dw, db, None, None, None, None
+
+
+def conv_fuses_activation(act: int, cout: int, kind: Optional[str] = None) -> bool:
+    """can conv2d apply `act` in its epilogue? (LeakyReLU on the MFMA paths; include/agan.h: agan_conv_gather).  Never for a conv
+    of kind "any": the general engine has no activation epilogue."""
+    return act == L.ACT_LRELU and cout > 4 and kind != "any"
 
 
 def conv2d(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None, kind: str = "same", cache: Optional[dict] = None,
            wdst=None, bdst=None, act: int = 0, handoff_out: Optional[ActHandoff] = None,
-           handoff_in: Optional[ActHandoff] = None) -> Tensor:
-    """conv forward with autograd (dgrad + wgrad kernels).  kind: 'same' | 'down' | 'up' (conv_geoms).
+           handoff_in: Optional[ActHandoff] = None, stride=(1, 1), padding=(0, 0)) -> Tensor:
+    """conv forward with autograd (dgrad + wgrad kernels).  kind: 'same' | 'down' | 'up' (conv_geoms) or 'any'.
     wdst / bdst: optional flat-gradient destinations of weight / bias (grad_dst(param)).
     act: ACT_LRELU applies the activation in the conv epilogue (see conv_fuses_activation).
-    handoff_out / handoff_in: one ActHandoff shared by a fused conv+LeakyReLU and the single conv consuming its output."""
+    handoff_out / handoff_in: one ActHandoff shared by a fused conv+LeakyReLU and the single conv consuming its output.
+    kind 'any': the general trainable conv with the module's `stride` and `padding` (pairs); per axis kernel 1..5, stride 1..3,
+    padding 0..3.  fp32 products in every precision mode; under 16-bit activation storage it reads and writes fp32, casting on the
+    way in.  No fused activation and no handoff."""
+    if kind == "any":
+        if act != L.ACT_NONE or handoff_out is not None:
+            raise L.AganError("conv2d(kind='any') has no fused activation: run HF.activation / HF.bn_act after it")
+        return _ConvAnyFn.apply(x, weight, bias, tuple(stride), tuple(padding), wdst, bdst)
     return _ConvFn.apply(x, weight, bias, kind, cache, wdst, bdst, act, handoff_out, handoff_in)
 
 

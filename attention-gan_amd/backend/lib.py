@@ -119,6 +119,12 @@ _SIGNATURES = {
     "agan_conv2d_ktable": (c_int, [POINTER(Conv2dDesc), c_int, _P, _P]),
     "agan_conv2d_fwd": (c_int, [_P, _P, _P, _P, POINTER(Conv2dDesc), _P, c_int, _P, c_size_t, _P]),
     "agan_conv2d_dgrad": (c_int, [_P, _P, _P, POINTER(Conv2dDesc), _P, _P, c_int, _P, c_size_t, _P]),
+    "agan_conv2d_train_supported": (c_int, [POINTER(Conv2dDesc)]),
+    "agan_conv2d_train_slabs": (c_int, [POINTER(Conv2dDesc)]),
+    "agan_conv2d_train_ws_bytes": (c_size_t, [POINTER(Conv2dDesc), c_int]),
+    "agan_conv2d_train_fwd": (c_int, [_P, _P, _P, _P, POINTER(Conv2dDesc), _P, c_size_t, _P]),
+    "agan_conv2d_train_dgrad": (c_int, [_P, _P, _P, POINTER(Conv2dDesc), c_int, _P, c_size_t, _P]),
+    "agan_conv2d_train_wgrad": (c_int, [_P, _P, _P, POINTER(Conv2dDesc), c_int, _P, c_size_t, _P]),
     "agan_maxpool3s2_fwd": (c_int, [_P, _P, _P] + [c_int] * 6 + [_P]),
     "agan_maxpool3s2_bwd": (c_int, [_P, _P, _P, _P] + [c_int] * 7 + [_P]),
     "agan_avgpool3s1_fwd": (c_int, [_P, _P] + [c_int] * 4 + [_P]),

@@ -906,6 +906,11 @@ static inline void timer_end(hipStream_t st, int split) {
     }
     g_timer_start = g_timer_stop = nullptr;
 }
+// the same bracket for the main kernel of an engine in another file (conv_any.hip)
+namespace agan { namespace conv {
+void timed_begin(hipStream_t st) { timer_begin(st); }
+void timed_end(hipStream_t st, int split) { timer_end(st, split); }
+} }
 
 // ================================================================================================
 // routing: the one place that decides which kernel a conv call runs on

@@ -19,6 +19,9 @@ extern thread_local const void* g_noted_kernel;
         ::agan::conv::g_noted_kernel = reinterpret_cast<const void*>(kernel);      \
         hipLaunchKernelGGL(kernel, __VA_ARGS__);                                   \
     } while (0)
+// bracket of the measurement hook around the main kernel of a call (defined in conv.hip; `split`: partial-sum slabs it wrote)
+void timed_begin(hipStream_t st);
+void timed_end(hipStream_t st, int split);
 
 
 // n / d for n < 2^31 by multiply-high (Granlund-Montgomery round-up form): 2 VALU ops instead of a ~40-instruction sequence

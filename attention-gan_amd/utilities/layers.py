@@ -30,6 +30,8 @@ class HipConv2d(nn.Conv2d):
                 kind = "same"
             elif stride == 2 and k == 4 and pad == 1:
                 kind = "down"
+            elif 1 <= k <= 5 and 1 <= stride <= 3 and 0 <= pad <= 3:
+                kind = "any"         # the general trainable conv (include/agan.h: agan_conv2d_train_*)
             else:
                 raise NotImplementedError(f"conv k={k} s={stride} p={pad} is not on the AttnGAN hot path")
         self.kind = kind
@@ -38,6 +40,10 @@ class HipConv2d(nn.Conv2d):
     def forward(self, x: Tensor, act: int = L.ACT_NONE, handoff_out=None, handoff_in=None) -> Tensor:
         """`act` (only where HF.conv_fuses_activation allows it) applies the following activation in the conv epilogue;
         the handoffs link such a conv to its single consumer (HF.ActHandoff)."""
+        if self.kind == "any":       # no fused activation, no handoff (FusedChain.run never asks for one)
+            return HF.conv2d(x, self.weight, self.bias, "any", None, HF.grad_dst(self.weight),
+                             HF.grad_dst(self.bias) if self.bias is not None else None, act, handoff_out, None,
+                             self.stride, self.padding)
         return HF.conv2d(x, self.weight, self.bias, self.kind, self._packed, HF.grad_dst(self.weight),
                          HF.grad_dst(self.bias) if self.bias is not None else None, act, handoff_out, handoff_in)
 
@@ -110,7 +116,7 @@ class FusedChain(nn.Module):
         handoff = None
         for i, st in enumerate(self._stages):
             conv = getattr(self, st.conv)
-            if st.bn is None and HF.conv_fuses_activation(st.act, conv.out_channels):
+            if st.bn is None and HF.conv_fuses_activation(st.act, conv.out_channels, conv.kind):
                 # conv + LeakyReLU in one kernel (no BatchNorm in between); if a conv of this chain is its only consumer, that
                 # conv's dgrad epilogue does the activation backward as well
                 handoff = HF.ActHandoff() if i < last else None

@@ -34,7 +34,8 @@ extern "C" {
  * working unchanged): the general 2-D conv (agan_conv2d_*), AGAN_PACK_DGRAD_3x3S2, AGAN_ACT_RELU and the pools / bilinear resize of the
  * Inception-v3 image-encoder trunk (agan_maxpool3s2_*, agan_avgpool3s1_*, agan_global_avgpool_*, agan_resize_bilinear_*, agan_relu_bwd);
  * the embedding gather and the LSTM recurrence of the caption encoder (agan_embedding_*, agan_lstm_*); the train-mode BatchNorm of the
- * trunk on channel slices (agan_bn_relu_slice_fwd, agan_bn_slice_bwd). */
+ * trunk on channel slices (agan_bn_relu_slice_fwd, agan_bn_slice_bwd); the trainable general 2-D conv behind Layers.conv
+ * (agan_conv2d_train_*: forward, data gradient and weight gradient of any small geometry). */
 
 enum {
     AGAN_OK = 0,
@@ -439,6 +440,37 @@ int agan_conv2d_fwd(const float* x, const void* wk, const float* bias, float* y,
                     void* ws, size_t ws_bytes, void* stream);
 int agan_conv2d_dgrad(const float* dy, const void* wk, float* dx, const agan_conv2d_desc* d, const int32_t* ktable, const float* relu_mask,
                       int accumulate, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Trainable general 2-D convolution (csrc/conv_any.hip): what `Layers.conv(in_channels, out_channels, in_hw, out_hw)` can return and
+ * the tuned kinds above do not take.  Same descriptor and formula as agan_conv2d_fwd (no activation), with all three directions:
+ *
+ *   y [b, out_c0 + n, oy, ox]   = bias[n] + sum_{c, r, s} x[b, in_c0 + c, oy*SH + r - PH, ox*SW + s - PW] * w[n][c][r][s]
+ *   dx[b, in_c0 + c, iy, ix]  (+)= sum over the (n, r, s, oy, ox) whose window position (oy*SH + r - PH, ox*SW + s - PW) is (iy, ix)
+ *   dw[n][c][r][s]            (+)= sum_{b, oy, ox} dy[b, out_c0 + n, oy, ox] * x[b, in_c0 + c, oy*SH + r - PH, ox*SW + s - PW]
+ *
+ * Domain, per axis independently: K in 1..5 (KH*KW <= 25), S in 1..3, P in 0..3 -- P >= K included: an output pixel whose window
+ * lies wholly in the padding is the bias (or zero); OH, OW as F.conv2d computes them; channel slices on both sides as above; every
+ * tensor below 2^30 elements.  Anything else is AGAN_EINVAL with a message and no launch (agan_conv2d_train_supported: 1 / 0).
+ * The existing agan_conv2d_* entry points answer exactly as before.
+ *   - fp32 operands and v_mfma_f32_32x32x2_f32 products in EVERY precision mode; no atomics; every split sum is added in index
+ *     order, so two runs give the same bits;
+ *   - w is the plain OIHW fp32 weight (the call transposes it into its workspace); dw is OIHW fp32; bias may be NULL;
+ *   - direction 0 / 1 / 2 = forward / data gradient / weight gradient selects the workspace size; the workspace is 16-byte aligned;
+ *   - data gradient: dx pixels no window reaches (a residue class without a tap when K < S, trailing rows / columns when
+ *     (I + 2P - K) % S != 0) are written as zero; with accumulate != 0 every pixel gets dx += gradient (those: + 0);
+ *   - weight gradient: the range B*OH*OW is cut into agan_conv2d_train_slabs(d) slabs whose partial results go to the workspace and
+ *     are added in slab order; accumulate != 0: dw += gradient.  The bias gradient is agan_bias_grad.
+ * ---------------------------------------------------------------------------------------------- */
+int agan_conv2d_train_supported(const agan_conv2d_desc* d);
+int agan_conv2d_train_slabs(const agan_conv2d_desc* d);                 /* slabs of the weight gradient, or AGAN_EINVAL */
+size_t agan_conv2d_train_ws_bytes(const agan_conv2d_desc* d, int direction);   /* 0 for a descriptor outside the domain */
+int agan_conv2d_train_fwd(const float* x, const float* w, const float* bias, float* y, const agan_conv2d_desc* d, void* ws, size_t ws_bytes,
+                          void* stream);
+int agan_conv2d_train_dgrad(const float* dy, const float* w, float* dx, const agan_conv2d_desc* d, int accumulate, void* ws, size_t ws_bytes,
+                            void* stream);
+int agan_conv2d_train_wgrad(const float* x, const float* dy, float* dw, const agan_conv2d_desc* d, int accumulate, void* ws, size_t ws_bytes,
+                            void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Pools and resize of the trunk (csrc/pool_resize.hip), NCHW fp32.  Every backward is a gather: each input pixel sums, in a fixed
