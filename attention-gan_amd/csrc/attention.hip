@@ -10,10 +10,6 @@
 
 using namespace agan;
 
-#ifndef AGAN_ATTN_ABLATE
-#define AGAN_ATTN_ABLATE 0
-#endif
-
 namespace {
 
 constexpr int kMaxC = 64;   // LDS budget for the projected words: kMaxC * TMAX floats
@@ -244,20 +240,12 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const void* __restrict__ 
     #pragma unroll
                 for (int t = 0; t < TMAX; ++t) s += ds[t] * pj[c][t];
                 if (live) st1<DT>(dimages, base0 + (size_t)(c) * HW, s);
-    #if AGAN_ATTN_ABLATE != 1
                 float part[TMAX];
     #pragma unroll
                 for (int t = 0; t < TMAX; ++t) part[t] = dvc[j] * a[t] + ivc[j] * ds[t];
                 int t_own;
-    #if AGAN_ATTN_ABLATE == 2
-                float r = 0.f; t_own = lane & (TMAX - 1);
-    #pragma unroll
-                for (int t = 0; t < TMAX; ++t) r += part[t];
-    #else
                 const float r = wave_sum_scatter<TMAX>(part, lane, t_own);       // TMAX + 1 shuffles per channel, not 6 * TMAX
-    #endif
                 if ((lane & (64 / TMAX - 1)) == 0) acc[wave][c][t_own] = r;
-    #endif
             }
         }
 }

@@ -48,18 +48,9 @@ __global__ __launch_bounds__(256) void ktable_kernel(int2* __restrict__ tab, int
 // ================================================================================================
 // forward / dgrad gather kernel
 // ================================================================================================
-// Build-time tuning / ablation switches (defaults are the shipped configuration; measurements in DESIGN.md §4):
-//   AGAN_GATHER_BK     K tile depth;   AGAN_GATHER_WAVES   occupancy target of __launch_bounds__;
-//   AGAN_ABLATE=1|2|3  drop the global loads | + the LDS stores | + the barrier of the K loop (wrong results: timing only)
-#ifndef AGAN_XCD_REMAP
-#define AGAN_XCD_REMAP 1
-#endif
-#ifndef AGAN_GATHER_BK
-#define AGAN_GATHER_BK 16
-#endif
-#ifndef AGAN_GATHER_WAVES
-#define AGAN_GATHER_WAVES 3
-#endif
+// Tuned values (the K-loop ablations and the sweeps that chose them: DESIGN.md §4):
+constexpr int kGatherBK = 16;       // K tile depth
+constexpr int kGatherWaves = 3;     // occupancy target of __launch_bounds__
 // ODT: storage type of `out` and of `lrelu_mask` (AGAN_DT_*; fp32 arithmetic either way -- a 16-bit output is the data gradient or
 // the first-layer output of a network that keeps its activations in 16 bits: rounded once here instead of by a cast kernel)
 // GEN: the general 2-D conv of agan_conv2d_fwd / agan_conv2d_dgrad -- per-axis stride and offset (g.SX, g.OX*), up to 25 taps,
@@ -67,12 +58,12 @@ __global__ __launch_bounds__(256) void ktable_kernel(int2* __restrict__ tab, int
 // dropped, and the epilogue bias -> ReLU (g.relu), x ReLU'(mask) (lrelu_mask is then a ReLU mask), += out (g.accumulate).  Only
 // ever launched unsplit with fp32 output.  GEN = false compiles to the kernel the other conv calls have always run.
 template <int BM, int BN, int WM, int WN, int ODT = AGAN_DT_F32, bool GEN = false>
-__global__ __launch_bounds__(256, AGAN_GATHER_WAVES) void conv_gather_f32_kernel(const float* __restrict__ in, const float* __restrict__ wk,
+__global__ __launch_bounds__(256, kGatherWaves) void conv_gather_f32_kernel(const float* __restrict__ in, const float* __restrict__ wk,
                                                                const float* __restrict__ bias, void* __restrict__ out_v,
                                                                const int2* __restrict__ ktab, const Geom g, const int ksplit,
                                                                const int kchunk, const size_t slab, const int act,
                                                                const void* __restrict__ lrelu_mask) {
-    constexpr int BK = AGAN_GATHER_BK;
+    constexpr int BK = kGatherBK;
     constexpr int NG = 256 / BM;       // wave-uniform k groups for the pixel-major A loads
     constexpr int AK = BK / NG;        // k rows per thread per tile
     constexpr int NB4 = BK * BN / 4;   // float4s in a weight tile
@@ -97,7 +88,6 @@ __global__ __launch_bounds__(256, AGAN_GATHER_WAVES) void conv_gather_f32_kernel
     // each XCD takes a contiguous run of pixel tiles with all their channel tiles.  Measured on the 64->128 3x3 layer at
     // 128x128: 318 -> 109 MB fetched per launch (algorithmic 101 MB).
     int mt, nt, cls, split;
-#if AGAN_XCD_REMAP
     {   // F = (((K split) * mtiles + pixel tile) * classes + parity class) * ntiles + channel tile: the parity classes of a pixel
         // tile (upsample conv, stride-2 dgrad) read the same input window, K splits read different channels
         const int ncls = gridDim.z / ksplit, mtiles = gridDim.x, ntiles = gridDim.y;
@@ -106,10 +96,6 @@ __global__ __launch_bounds__(256, AGAN_GATHER_WAVES) void conv_gather_f32_kernel
         cls = F % ncls;  F /= ncls;
         mt = F % mtiles; split = F / mtiles;
     }
-#else
-    mt = blockIdx.x; nt = blockIdx.y;
-    cls = blockIdx.z / ksplit; split = blockIdx.z - cls * ksplit;
-#endif
     const int py = cls / g.OS, px = cls - py * g.OS;
     const int m0 = mt * BM, n0 = nt * BN;
     const int kbeg = split * kchunk, kend = min(g.K, kbeg + kchunk);
@@ -206,9 +192,7 @@ __global__ __launch_bounds__(256, AGAN_GATHER_WAVES) void conv_gather_f32_kernel
     // FULL = steady state (no conditionals, so the compiler's waitcnt bookkeeping stays exact across iterations)
     auto step = [&](auto full, auto cur, auto nxt, int kt, int buf) {
         constexpr bool FULL = decltype(full)::value;
-#if !defined(AGAN_ABLATE) || AGAN_ABLATE < 1
         if (FULL || kt + 2 < nkt) load_tile(cur, kt + 2);
-#endif
         // operand fragments are read one k-step ahead of the MFMAs that consume them (LDS latency off the critical path)
         float av[2][TM], bv[2][TN];
 #pragma unroll
@@ -233,12 +217,8 @@ __global__ __launch_bounds__(256, AGAN_GATHER_WAVES) void conv_gather_f32_kernel
             __builtin_amdgcn_sched_group_barrier(0x100, TM + TN, 0);
             __builtin_amdgcn_sched_group_barrier(0x008, TM * TN, 0);
         }
-#if !defined(AGAN_ABLATE) || AGAN_ABLATE < 2
         if (FULL || kt + 1 < nkt) store_tile(nxt, buf ^ 1);
-#endif
-#if !defined(AGAN_ABLATE) || AGAN_ABLATE < 3
         __syncthreads();
-#endif
     };
 
     if (nkt > 0) load_tile(S0{}, 0);
@@ -488,12 +468,12 @@ void launch_gather(const float* in, const float* wk, const float* bias, void* ds
                            p.kchunk, p.slab, act, lrelu_mask);
 }
 
-// the general 2-D conv (agan_conv2d_fwd / agan_conv2d_dgrad): one unsplit launch, fp32 output, K tile AGAN_GATHER_BK
+// the general 2-D conv (agan_conv2d_fwd / agan_conv2d_dgrad): one unsplit launch, fp32 output, K tile kGatherBK
 static void launch_gather_2d(const float* in, const float* wk, const float* bias, float* out, const int2* ktab, const Geom& g,
                              const float* relu_mask, hipStream_t st) {
     const int bn = g.Cout >= 96 ? 128 : (g.Cout >= 48 ? 64 : 32);
     dim3 grid(cdiv(g.Mtot, 128), cdiv(g.Cout, bn), g.OS * g.OS);
-    const int kchunk = cdiv(g.K, AGAN_GATHER_BK) * AGAN_GATHER_BK;
+    const int kchunk = cdiv(g.K, kGatherBK) * kGatherBK;
     if (bn == 128)
         AGAN_LAUNCH((conv_gather_f32_kernel<128, 128, 2, 2, AGAN_DT_F32, true>), grid, dim3(256), 0, st, in, wk, bias, (void*)out, ktab, g, 1,
                     kchunk, (size_t)0, (int)AGAN_ACT_NONE, (const void*)relu_mask);
@@ -525,7 +505,6 @@ __global__ __launch_bounds__(256) void conv_wgrad_f32_kernel(const float* __rest
     // F = (pixel chunk z, cout tile, k tile), so all tiles of a chunk run on one XCD (the 64-channel 3x3 layers have 9 k tiles
     // per chunk: in plain id order they hit 8 different L2s and dY came over the fabric 5-6x)
     int it_, jt_, cls, split;
-#if AGAN_XCD_REMAP
     {   // F = (((pixel split) * classes + parity class) * jtiles + cout tile) * itiles + k tile
         const int ncls = gridDim.z / psplit, itiles = gridDim.x, jtiles = gridDim.y;
         int F = xcd_contiguous(linear_block_id(), itiles * jtiles * (int)gridDim.z);
@@ -533,10 +512,6 @@ __global__ __launch_bounds__(256) void conv_wgrad_f32_kernel(const float* __rest
         jt_ = F % jtiles; F /= jtiles;
         cls = F % ncls;   split = F / ncls;
     }
-#else
-    it_ = blockIdx.x; jt_ = blockIdx.y;
-    cls = blockIdx.z / psplit; split = blockIdx.z - cls * psplit;
-#endif
     const int py = cls / g.OS, px = cls - py * g.OS;
     const int i0 = it_ * BI, j0 = jt_ * BJ;
     const int pbeg = split * pchunk, pend = min(g.Mtot, pbeg + pchunk);
@@ -1010,8 +985,7 @@ static WgradRoute route_wgrad(const agan_conv_geom* gg, int pack_mode, int prec,
     const bool up = pack_mode == AGAN_PACK_UP_FWD, x16 = x_dtype != AGAN_DT_F32, y16 = dy_dtype != AGAN_DT_F32;
     // The mode.  Besides the geometries the patch kernels do not take:
     //   * AGAN_PREC_BF16X6 -- fp32-grade by definition, so it may use whichever fp32-grade kernel is fastest.  Its own six-product patch
-    //     kernel is not (three planes of two tensors: 10 vs 6.5 ms per step against the fp32 MFMA kernel; -DAGAN_BF16X6_PATCH_WGRAD=1
-    //     builds it in).  Round 3: the two-plane fp16 split (AGAN_PREC_F16X3: 22-bit products, the same full-size parity) is 1.35-2.2x
+    //     kernel is not (three planes of two tensors: 10 vs 6.5 ms per step against the fp32 MFMA kernel).  Round 3: the two-plane fp16 split (AGAN_PREC_F16X3: 22-bit products, the same full-size parity) is 1.35-2.2x
     //     faster than the fp32 kernel on every layer, so bf16x6 weight gradients run there -- the caller supplies the amax slots of x
     //     and dy exactly as in AGAN_PREC_F16X3;
     //   * the folded upsample conv (4 classes of 2x2 taps) keeps its mode only where the row-resident kernel takes it as the conv3x3 on
@@ -1019,9 +993,7 @@ static WgradRoute route_wgrad(const agan_conv_geom* gg, int pack_mode, int prec,
     //     EVERY mode (0.61 / 0.52 vs 0.49 ms at 64x128 -> 64x256; 16 short reductions per tile) -- fp32 products are at least as accurate.
     if (prec_planes(prec) > 0 && patch_supported(g)) {
         r.mode = prec;
-#ifndef AGAN_BF16X6_PATCH_WGRAD
         if (prec == AGAN_PREC_BF16X6) r.mode = AGAN_PREC_F16X3;
-#endif
         if (up && !plan_rows_wgrad(g, r.mode, false, false, true).ok) r.mode = AGAN_PREC_F32;
     }
     // 16-bit storage: a 16-bit x into the <= 4-output-channel fp32 kernel, or the one-plane modes' own type on either side

@@ -66,42 +66,16 @@ template <> struct GKTraits<2> { static constexpr int R = 4, S = 4, IS = 2, CHS 
 // column-parity classes of 64 lattice points from ONE staged patch.  Its accumulator fragments come in pairs (class px = 0, 1 of the
 // same 32 lattice points), so a lane holds two ADJACENT output pixels and the epilogue writes whole contiguous rows -- as separate
 // class launches every store touched every second pixel (2-byte stores at a 4-byte stride) and the patch was staged twice.
-#ifndef AGAN_P16_OCC
-#define AGAN_P16_OCC 2
-#endif
-#ifndef AGAN_P16_WD
-#define AGAN_P16_WD 0
-#endif
-// Diagnostic builds only (-DAGAN_P16_TIMING, never shipped: profiles/r04_p16_timing.txt): s_memtime stamps per workgroup at kernel entry,
-// after the prologue's barrier, after the K loop and at exit, into a __device__ array that agan_debug_p16_stamps() copies out.
-#ifdef AGAN_P16_TIMING
-__device__ unsigned long long g_p16_stamps[16384 * 4];
-#define AGAN_P16_STAMP(i) do { if (threadIdx.x == 0 && linear_block_id() < 16384) g_p16_stamps[linear_block_id() * 4 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define AGAN_P16_STAMP(i) do { } while (0)
-#endif
-// -DAGAN_P16_ABLATE=n (diagnostic builds): 1 no patch loads, 2 no weight loads, 3 item writes to the trash slot, 4 no epilogue,
-// 5 no item transposes / writes in the K loop, 6 no fragment reads in the K loop, 7 = 5 + 6
-#ifndef AGAN_P16_ABLATE
-#define AGAN_P16_ABLATE 0
-#endif
-// s_setprio 1 around each k-step's MFMA burst (experiment switch)
-#ifndef AGAN_P16_PRIO
-#define AGAN_P16_PRIO 0
-#endif
-#ifndef AGAN_P16_STAGGER
-#define AGAN_P16_STAGGER 0
-#endif
-#ifndef AGAN_P16_PIN
-#define AGAN_P16_PIN 0
-#endif
+// (Round 4 measured this kernel with ablations and per-workgroup time stamps and tried staggered workgroups, s_setprio around the MFMA bursts and a
+// pinned first read group: nothing was faster than this form -- DESIGN.md §4 "Round 4", profiles/r04_p16_analysis.txt.)
+constexpr int kP16Occ = 2;      // workgroups per CU of the WC 1 forms
 // WC / LPX (round 4): WC weight (cout) fragments per wave and 2^LPX lattice points per workgroup.  The round-3 tile (WC 1, LPX 7: each wave one
 // 32-channel fragment x 128 pixels) issues 5 fragment loads per 4 MFMAs and re-reads the packed weights once per 128 pixels: it is the L2 -> L1 path
 // that saturates (340 B per k of weights + patch per 32 K MACs = 96 FLOP/B against the chip's ~72 FLOP/B of L2 bandwidth at the dense MFMA rate).
 // WC 2 gives a wave a 64-channel x 128-pixel register tile (128 accumulator registers, ONE wave per SIMD): 6 fragment loads per 8 MFMAs, half the LDS
 // reads and half the vector-memory instructions per MFMA, and -- as 128 channels x 256 pixels (LPX 8) -- half the weight bytes per FLOP.
 template <int ET, int GK, int BN, bool IN16, bool OUT16, int NI, bool PX2 = false, int WC = 1, int LPX = 7>
-__global__ __launch_bounds__(256, (WC == 2 ? 1 : AGAN_P16_OCC)) void conv_p16_kernel(const void* __restrict__ in, const unsigned short* __restrict__ wk,
+__global__ __launch_bounds__(256, (WC == 2 ? 1 : kP16Occ)) void conv_p16_kernel(const void* __restrict__ in, const unsigned short* __restrict__ wk,
                                                           const float* __restrict__ bias, void* __restrict__ out, const Geom g,
                                                           const P16Plan pp, const int act, const void* __restrict__ lrelu_mask) {
     using T = GKTraits<GK>;
@@ -116,12 +90,8 @@ __global__ __launch_bounds__(256, (WC == 2 ? 1 : AGAN_P16_OCC)) void conv_p16_ke
     // before them: the ring depth is therefore also the number of k-steps the patch loads get before anything waits on them.
     // (measured, round 3: a ring as deep as the whole stage -- 64-72 VGPRs -- was 0-25 % SLOWER than 8-9 k-steps: the kernel is bound
     // by the texture-address path, 57 % busy, of which the weight fragments are two thirds, not by one exposed latency)
-#ifndef AGAN_P16_WD_FULL
-#define AGAN_P16_WD_FULL 0
-#endif
-    constexpr int WD = AGAN_P16_WD ? (SPS == 18 ? (AGAN_P16_WD == 4 ? 3 : AGAN_P16_WD) : AGAN_P16_WD)
-                                   : (WC == 2 ? (SPS == 18 ? 6 : 4)      // (WC 2: two fragments per slot and 256 MFMA cycles per k-step)
-                                              : (PX2 ? 4 : ((AGAN_P16_WD_FULL && NI == 1) ? SPS : (SPS == 18 ? 9 : 8))));     // (PX2: two fragments per slot)
+    constexpr int WD = WC == 2 ? (SPS == 18 ? 6 : 4)      // (WC 2: two fragments per slot and 256 MFMA cycles per k-step)
+                               : (PX2 ? 4 : (SPS == 18 ? 9 : 8));     // (PX2: two fragments per slot)
     constexpr int NFRAG = PX2 ? 4 : (1 << (LPX - 5));   // 32-pixel fragments per workgroup tile
     constexpr int WN = BN / (32 * WC), WM = 4 / WN, TM = NFRAG / WM;
     static_assert(WN >= 1 && WN <= 4 && WM * WN == 4 && TM >= 1 && TM * WM == NFRAG, "wave grid");
@@ -135,14 +105,6 @@ __global__ __launch_bounds__(256, (WC == 2 ? 1 : AGAN_P16_OCC)) void conv_p16_ke
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const int buf_bytes = pp.buf_bytes;
 
-#if AGAN_P16_STAGGER
-    // experiment: de-phase the two workgroups of a CU -- the second-round-robin half of the first 512 workgroups starts late
-    if (linear_block_id() >= 256 && linear_block_id() < 512) {
-#pragma unroll 1
-        for (int i = 0; i < AGAN_P16_STAGGER; ++i) __builtin_amdgcn_s_sleep(127);
-    }
-#endif
-    AGAN_P16_STAMP(0);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wn = wave % WN, wm = wave / WN;
@@ -205,7 +167,7 @@ __global__ __launch_bounds__(256, (WC == 2 ? 1 : AGAN_P16_OCC)) void conv_p16_ke
         const int c0 = chunk * CHS;
 #pragma unroll
         for (int i = 0; i < NI; ++i) {
-            const unsigned voff = (AGAN_P16_ABLATE != 1 && c0 + it_oct[i] * 8 < g.Cin && it_oct[i] < CHS / 8) ? it_voff[i] : kOOB;
+            const unsigned voff = (c0 + it_oct[i] * 8 < g.Cin && it_oct[i] < CHS / 8) ? it_voff[i] : kOOB;
 #pragma unroll
             for (int c = 0; c < 8; ++c) blk[i][c] = ld16(rin, voff, (unsigned)((c0 + c) * ihw) * (unsigned)ESZ);
         }
@@ -249,7 +211,7 @@ __global__ __launch_bounds__(256, (WC == 2 ? 1 : AGAN_P16_OCC)) void conv_p16_ke
     u32x4 wf[WD][NWF];
     auto load_w = [&](int slot, int q) {
 #pragma unroll
-        for (int c = 0; c < NWF; ++c) wf[slot][c] = ld16(rwk, AGAN_P16_ABLATE == 2 ? kOOB : wlane[c], (unsigned)min(q, pp.wsteps - 1) * wstep);
+        for (int c = 0; c < NWF; ++c) wf[slot][c] = ld16(rwk, wlane[c], (unsigned)min(q, pp.wsteps - 1) * wstep);
     };
 
     // The first stage's patch and the first weight fragments are requested HERE, before the ~250 instructions of operand addressing below
@@ -298,7 +260,6 @@ __global__ __launch_bounds__(256, (WC == 2 ? 1 : AGAN_P16_OCC)) void conv_p16_ke
 #pragma unroll
         for (int w = 0; w < NWR; ++w) store_piece(w, lds + (stage_beg & 1) * buf_bytes);
         lds_barrier();
-        AGAN_P16_STAMP(1);
         for (int stage = stage_beg; stage < stage_end; ++stage) {
             const bool more = stage + 1 < stage_end;
             const unsigned char* cur = lds + (stage & 1) * buf_bytes;
@@ -311,13 +272,6 @@ __global__ __launch_bounds__(256, (WC == 2 ? 1 : AGAN_P16_OCC)) void conv_p16_ke
             // group of its own, step 0's reads above were taken as the FIRST read group and every later group slid back by one: the
             // compiled loop read each fragment right in front of the MFMA that consumes it (lgkmcnt wait per MFMA, the whole LDS latency
             // exposed in every k-step; round-4 disassembly + s_memtime stamps: 410 cycles per pair of k-steps for 256 of MFMA)
-#if AGAN_P16_PIN
-            __builtin_amdgcn_sched_group_barrier(0x100, TM, 0);
-#endif
-            if (AGAN_P16_ABLATE == 6 || AGAN_P16_ABLATE == 7) {
-#pragma unroll
-                for (int m = 0; m < TM; ++m) af[1][m] = af[0][m];
-            }
 #pragma unroll
             for (int u = 0; u < SPS; ++u) {
                 u32x4 w[NWF];
@@ -328,21 +282,15 @@ __global__ __launch_bounds__(256, (WC == 2 ? 1 : AGAN_P16_OCC)) void conv_p16_ke
                     if (u2 < SPS) load_w(u % WD, wq_of(stage, u2));
                     else load_w(u % WD, wq_of(more ? stage + 1 : stage, u2 - SPS));
                 }
-                if (u + 1 < SPS && AGAN_P16_ABLATE != 6 && AGAN_P16_ABLATE != 7) {
+                if (u + 1 < SPS) {
 #pragma unroll
                     for (int m = 0; m < TM; ++m)
                         af[(u + 1) & 1][m] = *reinterpret_cast<const u32x4*>(cur + lbase[m] + tapoff[tap_of(u + 1)] + choff_of(u + 1));
                 }
-#if AGAN_P16_PRIO
-                __builtin_amdgcn_s_setprio(1);
-#endif
 #pragma unroll
                 for (int m = 0; m < TM; ++m)
 #pragma unroll
                     for (int c = 0; c < WC; ++c) acc[c][m] = mfma16<ET>(w[PX2 ? (m & 1) : c], af[u & 1][m], acc[c][m]);
-#if AGAN_P16_PRIO
-                __builtin_amdgcn_s_setprio(0);
-#endif
                 if (WC == 1) {
                     __builtin_amdgcn_sched_group_barrier(0x100, TM, 0);      // next step's LDS reads first ...
                     __builtin_amdgcn_sched_group_barrier(0x008, TM, 0);      // ... then this step's MFMAs
@@ -353,7 +301,7 @@ __global__ __launch_bounds__(256, (WC == 2 ? 1 : AGAN_P16_OCC)) void conv_p16_ke
                         __builtin_amdgcn_sched_group_barrier(0x008, WC, 0);
                     }
                 }
-                if (u >= U0 && more && AGAN_P16_ABLATE != 5 && AGAN_P16_ABLATE != 7) {
+                if (u >= U0 && more) {
 #pragma unroll
                     for (int k = 0; k < WPS; ++k)
                         if ((u - U0) * WPS + k < NWR) store_piece((u - U0) * WPS + k, nxt);
@@ -363,8 +311,6 @@ __global__ __launch_bounds__(256, (WC == 2 ? 1 : AGAN_P16_OCC)) void conv_p16_ke
         }
     }
 
-    AGAN_P16_STAMP(2);
-    if (AGAN_P16_ABLATE == 4) return;
     // ---- epilogue: D[cout][pixel]; a register holds 32 consecutive pixels of one output channel ----
     const size_t ohw = (size_t)g.OH * g.OW;
     const bool split_out = ksplit > 1;                  // partial sums go to fp32 slabs; the slab sum applies bias / activation / rounding
@@ -387,7 +333,7 @@ __global__ __launch_bounds__(256, (WC == 2 ? 1 : AGAN_P16_OCC)) void conv_p16_ke
         if (!add_bias && !lrelu) {
             // the path every layer of the step takes (BatchNorm follows: no bias, no activation here): ONE conversion per two values and the
             // two 16-bit halves stored as they are (ds_write_b16 / ds_write_b16_d16_hi) -- 1.5 instructions per value instead of ~7 plus a
-            // branch in the generic form below (the epilogue was 17 % of a workgroup's life: s_memtime stamps, profiles/r04_p16_timing.txt)
+            // branch in the generic form below (the epilogue was 17 % of a workgroup's life: s_memtime stamps, profiles/r04_p16_analysis.txt)
 #pragma unroll
             for (int c = 0; c < WC; ++c) {
                 const int nwl = (wn * WC + c) * 32;
@@ -434,7 +380,6 @@ __global__ __launch_bounds__(256, (WC == 2 ? 1 : AGAN_P16_OCC)) void conv_p16_ke
             const unsigned vo = ok ? (unsigned)(((b * g.Cout + n0 + n) * g.OH + yq) * g.OW + xq) * 2u : kOOB;
             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, v), rout, vo, 0, 0);
         }
-        AGAN_P16_STAMP(3);
         return;
     }
     if (PX2) {
@@ -483,7 +428,6 @@ __global__ __launch_bounds__(256, (WC == 2 ? 1 : AGAN_P16_OCC)) void conv_p16_ke
                 }
             }
         }
-        AGAN_P16_STAMP(3);
         return;
     }
 #pragma unroll
@@ -520,7 +464,6 @@ __global__ __launch_bounds__(256, (WC == 2 ? 1 : AGAN_P16_OCC)) void conv_p16_ke
             }
         }
     }
-    AGAN_P16_STAMP(3);
 }
 
 template <int ET, int GK, int BN, bool IN16, bool OUT16, int WC = 1, int LPX = 7>
@@ -555,19 +498,14 @@ void launch_px2(const void* in, const void* wk, const float* bias, void* dst, co
 template <int ET, int GK, int BN, int WC, int LPX>
 void launch_io(const void* in, const void* wk, const float* bias, void* dst, const Geom& g, const P16Plan& p, int act, const void* mask,
                hipStream_t st, bool in16, bool out16) {
-#ifdef AGAN_P16_FAST_BUILD      // (experiment builds: bf16 with 16-bit storage both sides only -- 20 s instead of 150)
-    if (ET == 0 && in16 && out16) launch_ni<0, GK, BN, true, true, WC, LPX>(in, wk, bias, dst, g, p, act, mask, st);
-#else
     if (in16 && out16) launch_ni<ET, GK, BN, true, true, WC, LPX>(in, wk, bias, dst, g, p, act, mask, st);
     else if (in16) launch_ni<ET, GK, BN, true, false, WC, LPX>(in, wk, bias, dst, g, p, act, mask, st);
     else if (out16) launch_ni<ET, GK, BN, false, true, WC, LPX>(in, wk, bias, dst, g, p, act, mask, st);
     else launch_ni<ET, GK, BN, false, false, WC, LPX>(in, wk, bias, dst, g, p, act, mask, st);
-#endif
 }
 template <int ET, int GK, int BN>
 void launch_dt(const void* in, const void* wk, const float* bias, void* dst, const Geom& g, const P16Plan& p, int act, const void* mask,
                hipStream_t st, bool in16, bool out16) {
-#ifndef AGAN_P16_FAST_BUILD
     if constexpr (GK == 1 && BN >= 64 && BN <= 128) {
         if (p.px2) {
             if (in16 && out16) launch_px2<ET, BN, true, true>(in, wk, bias, dst, g, p, act, mask, st);
@@ -577,11 +515,6 @@ void launch_dt(const void* in, const void* wk, const float* bias, void* dst, con
             return;
         }
     }
-#else
-    if constexpr (GK == 1 && BN >= 64 && BN <= 128) {
-        if (p.px2 && ET == 0) { launch_px2<0, BN, true, true>(in, wk, bias, dst, g, p, act, mask, st); return; }
-    }
-#endif
     // the register-tile forms (round 4): 64 channels x 128 pixels per wave
     if constexpr (BN == 128) {
         if (p.wc == 2) { launch_io<ET, GK, 128, 2, 8>(in, wk, bias, dst, g, p, act, mask, st, in16, out16); return; }      // 128 channels x 256 pixels
@@ -710,12 +643,3 @@ void launch_p16_gather(const void* in, const void* wk, const float* bias, void* 
 
 }  // namespace conv
 }  // namespace agan
-
-#ifdef AGAN_P16_TIMING
-extern "C" int agan_debug_p16_stamps(unsigned long long* host, int nblocks) {
-    if (hipMemcpyFromSymbol(host, HIP_SYMBOL(g_p16_stamps), sizeof(unsigned long long) * 4 * (size_t)nblocks) != hipSuccess) return -1;
-    void* dev = nullptr;
-    if (hipGetSymbolAddress(&dev, HIP_SYMBOL(g_p16_stamps)) != hipSuccess) return -1;
-    return hipMemset(dev, 0, sizeof(unsigned long long) * 4 * 16384) == hipSuccess ? 0 : -1;      // cleared for the next read
-}
-#endif

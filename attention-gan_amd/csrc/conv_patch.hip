@@ -76,15 +76,7 @@ __global__ __launch_bounds__(256, 2) void conv_patch_kernel2(const float* __rest
     // only TM MFMAs (128 cycles): two steps ahead (the depth the split modes use, whose k-steps are 3-6x longer) left every k-step
     // waiting ~300 cycles for its L2 hit -- MFMA-busy 11-18 % in round 2.  The depth divides the k-steps per stage (8 or 18), so
     // slot indices stay compile-time constants across stages.
-#ifndef AGAN_PATCH_WD1
-#define AGAN_PATCH_WD1 0
-#endif
-#ifndef AGAN_PATCH_WDS
-#define AGAN_PATCH_WDS 0
-#endif
-    constexpr int WD = (NPL == 1 && HS == 2) ? (AGAN_PATCH_WD1 ? AGAN_PATCH_WD1 : (NT == 9 ? 6 : 4))
-                                             : ((AGAN_PATCH_WDS && NPL == 2) ? (NT == 9 ? AGAN_PATCH_WDS * 3 : AGAN_PATCH_WDS * 2)
-                                                                             : ((AGAN_PATCH_WDS && NPL == 3 && NT == 9) ? 3 : 2));
+    constexpr int WD = (NPL == 1 && HS == 2) ? (NT == 9 ? 6 : 4) : 2;
     static_assert(WD == 2 || SPS % WD == 0, "ring depth must divide the k-steps per stage");
     extern __shared__ __attribute__((aligned(16))) unsigned char patch2[];
     const int buf_bytes = NPL * plane_bytes;
@@ -235,9 +227,7 @@ __global__ __launch_bounds__(256, 2) void conv_patch_kernel2(const float* __rest
             const Stage ns = more ? advance(cs) : cs;
             const unsigned char* cur = patch2 + (stage & 1) * buf_bytes;
             unsigned char* nxt = patch2 + ((stage + 1) & 1) * buf_bytes;
-#if !defined(AGAN_PATCH_ABLATE) || AGAN_PATCH_ABLATE != 2
             if (more) load_patch(ns);
-#endif
             // pixel fragments are read ONE k-step ahead of the MFMAs that consume them (LDS latency and bank conflicts off the
             // critical path); sched_group_barrier keeps that order in the emitted code
             u32x4 af[2][TM][NPL];
@@ -253,16 +243,10 @@ __global__ __launch_bounds__(256, 2) void conv_patch_kernel2(const float* __rest
                 for (int p = 0; p < NPL; ++p) w[p] = wf[u % WD][p];
                 {   // weights WD k-steps ahead (possibly in the next stage; past the last stage: a harmless repeat)
                     const int u2 = u + WD;
-#if !defined(AGAN_PATCH_ABLATE) || AGAN_PATCH_ABLATE != 3
                     if (u2 < SPS) load_w(u % WD, qof(cs, u2 / HS, u2 % HS));
                     else load_w(u % WD, qof(ns, (u2 - SPS) / HS, (u2 - SPS) % HS));
-#endif
                 }
-#if defined(AGAN_PATCH_ABLATE) && AGAN_PATCH_ABLATE == 5
-                if (false) {
-#else
                 if (u + 1 < SPS) {
-#endif
                     const int t1 = (u + 1) / HS, h1 = (u + 1) % HS;
 #pragma unroll
                     for (int m = 0; m < TM; ++m)
@@ -270,45 +254,17 @@ __global__ __launch_bounds__(256, 2) void conv_patch_kernel2(const float* __rest
                         for (int p = 0; p < NPL; ++p)
                             af[(u + 1) & 1][m][p] = *reinterpret_cast<const u32x4*>(cur + p * plane_bytes + lbase[m] + (unsigned)(pp.tappos[t1] * PB) + h1 * 32);
                 }
-#if defined(AGAN_PATCH_ABLATE) && AGAN_PATCH_ABLATE == 5
-#pragma unroll
-                for (int m = 0; m < TM; ++m) acc[m] = mfma_split<ET, NPL>(w, af[0][m], acc[m]);
-#elif defined(AGAN_PATCH_ABLATE) && AGAN_PATCH_ABLATE == 6
-                // interleave the tiles' product chains: consecutive MFMAs never depend on each other
-                if (NPL == 3) {
-#pragma unroll
-                    for (int m = 0; m < TM; ++m) acc[m] = mfma16<0>(w[2], af[u & 1][m][0], acc[m]);
-#pragma unroll
-                    for (int m = 0; m < TM; ++m) acc[m] = mfma16<0>(w[0], af[u & 1][m][2], acc[m]);
-#pragma unroll
-                    for (int m = 0; m < TM; ++m) acc[m] = mfma16<0>(w[1], af[u & 1][m][1], acc[m]);
-#pragma unroll
-                    for (int m = 0; m < TM; ++m) acc[m] = mfma16<0>(w[1], af[u & 1][m][0], acc[m]);
-#pragma unroll
-                    for (int m = 0; m < TM; ++m) acc[m] = mfma16<0>(w[0], af[u & 1][m][1], acc[m]);
-#pragma unroll
-                    for (int m = 0; m < TM; ++m) acc[m] = mfma16<0>(w[0], af[u & 1][m][0], acc[m]);
-                } else {
-#pragma unroll
-                    for (int m = 0; m < TM; ++m) acc[m] = mfma_split<ET, NPL>(w, af[u & 1][m], acc[m]);
-                }
-#else
 #pragma unroll
                 for (int m = 0; m < TM; ++m) acc[m] = mfma_split<ET, NPL>(w, af[u & 1][m], acc[m]);
-#endif
                 __builtin_amdgcn_sched_group_barrier(0x100, TM * NPL, 0);                                  // next step's LDS reads first ...
                 __builtin_amdgcn_sched_group_barrier(0x008, TM * (NPL == 1 ? 1 : (NPL == 2 ? 3 : 6)), 0);   // ... then this step's MFMAs
-#if !defined(AGAN_PATCH_ABLATE) || AGAN_PATCH_ABLATE != 1
                 if (u >= U0 && more) store_item(u - U0, nxt);      // next stage's patch, one item per k-step, behind the MFMAs
-#endif
             }
             if (WD == 2 && (SPS & 1)) {        // an odd number of k-steps per stage flips the parity of the two-slot weight ring: swap it back
 #pragma unroll
                 for (int p = 0; p < NPL; ++p) { const u32x4 tmp = wf[0][p]; wf[0][p] = wf[1][p]; wf[1][p] = tmp; }
             }
-#if !defined(AGAN_PATCH_ABLATE) || AGAN_PATCH_ABLATE != 4
             lds_barrier();
-#endif
             cs = ns;
         }
     }
@@ -690,21 +646,9 @@ __global__ __launch_bounds__(256) void conv_patch_wgrad_kernel(const void* __res
 #pragma unroll
             for (int p = 0; p < NPL; ++p) bb[p] = ds_read_tr8(xs + p * kWgPlane, xo[0] + toff[t], xo[1] + toff[t]);
         };
-#ifdef AGAN_WG_TIMING
-        long long tph[6] = {0, 0, 0, 0, 0, 0};
-#define AGAN_TICK(k) do { const long long now_ = clock64(); tph[k] += now_ - tlast; tlast = now_; } while (0)
-#else
-#define AGAN_TICK(k) do { } while (0)
-#endif
         for (int mt = tile_beg; mt < tile_end; ++mt) {
-#ifdef AGAN_WG_TIMING
-            long long tlast = clock64();
-#endif
             const bool more = mt + 1 < tile_end;
-#if !defined(AGAN_WG_ABLATE) || AGAN_WG_ABLATE != 1
             if (more) { if (B16) load_tile16(mt + 1); else load_tile(mt + 1, 0); }
-#endif
-            AGAN_TICK(0);
             // (opaque per tile: otherwise all 8 x TPW x 2 fragment addresses of the unrolled loop are hoisted out of the tile loop and
             //  held in VGPRs next to the 72-104 staging registers -- recomputing them costs a few dozen VALU adds per tile)
             asm volatile("" : "+v"(xc_tile));
@@ -721,16 +665,11 @@ __global__ __launch_bounds__(256) void conv_patch_wgrad_kernel(const void* __res
             read_a(0, a[0]);
 #pragma unroll
             for (int q = 0; q < G; ++q) read_b(xo[0], q, bf[0][q]);
-#if defined(AGAN_WG_ABLATE) && AGAN_WG_ABLATE == 3
-            if (mt == tile_beg)
-#endif
 #pragma unroll
             for (int kk = 0; kk < nsteps; ++kk) {
 #pragma unroll
                 for (int tg = 0; tg < NG; ++tg) {
-#if !defined(AGAN_WG_ABLATE) || AGAN_WG_ABLATE != 1
                     if (!B16 && kk == nsteps / 2 && tg == 0 && more) load_tile(mt + 1, 1);
-#endif
                     const int cur = (kk * NG + tg) & 1, nxt = cur ^ 1;
                     const bool last = (kk + 1 == nsteps) && (tg + 1 == NG);
                     const bool newk = (tg + 1 == NG);                         // the next item starts the next k-step
@@ -749,30 +688,12 @@ __global__ __launch_bounds__(256) void conv_patch_wgrad_kernel(const void* __res
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
-            AGAN_TICK(1);
             __syncthreads();
-            AGAN_TICK(2);
             if (more) {
-#ifdef AGAN_WG_TIMING
-#pragma unroll
-                for (int i = 0; i < kItems; ++i) staged_wait(xr[i]);
-#pragma unroll
-                for (int i = 0; i < C::kYItems; ++i) staged_wait(yr[i]);
-                AGAN_TICK(3);
-#endif
-#if !defined(AGAN_WG_ABLATE) || AGAN_WG_ABLATE != 2
                 if (B16) store_tile16(mt + 1); else store_tile();
-#endif
-                AGAN_TICK(4);
                 __syncthreads();
-                AGAN_TICK(5);
             }
         }
-#ifdef AGAN_WG_TIMING
-        if (blockIdx.x == 0 && blockIdx.y == 1 && blockIdx.z == 3 && tid == 64)
-            printf("wg timing (cycles over %d tiles): issue %lld kloop %lld bar1 %lld loadwait %lld convert+store %lld bar2 %lld\n", tile_end - tile_beg,
-                   tph[0], tph[1], tph[2], tph[3], tph[4], tph[5]);
-#endif
     }
 
     // ---- D[cout][channel of the chunk] per tap -> dst[split][cls][cout][kprime], kprime = ((chunk*NPH + ph)*NT + tap)*32 + ci ----

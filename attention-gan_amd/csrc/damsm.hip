@@ -11,17 +11,9 @@
 
 using namespace agan;
 
-#ifndef AGAN_PAIR_UNROLL_N
-#define AGAN_PAIR_UNROLL_N 4
-#endif
-#define AGAN_PRAGMA_(x) _Pragma(#x)
-#define AGAN_PRAGMA(x) AGAN_PRAGMA_(x)
-#define AGAN_PAIR_UNROLL AGAN_PRAGMA(unroll AGAN_PAIR_UNROLL_N)
-// (the d loops of the MFMA reductions below carry no unroll count: with a runtime trip count and a convergent instruction inside, the compiler refuses
-//  a counted unroll -- the pragma they used to carry only produced three "loop not unrolled" warnings per build)
-#ifndef AGAN_PAIR_MFMA_WAVES
-#define AGAN_PAIR_MFMA_WAVES 4
-#endif
+// (the d / region loops of the thread-per-row kernels are unrolled by 4; the d loops of the MFMA reductions carry no unroll count: with a runtime trip
+//  count and a convergent instruction inside, the compiler refuses a counted unroll -- the pragma they used to carry only produced three "loop not
+//  unrolled" warnings per build)
 
 namespace {
 
@@ -70,7 +62,7 @@ __device__ __forceinline__ void pair_forward(PairSmem<TMAX, DR>& sm, const float
 #pragma unroll
     for (int w = 0; w < TMAX; ++w) a1[w] = 0.f;
     if (rlive) {
-AGAN_PAIR_UNROLL
+#pragma unroll 4
         for (int d = 0; d < D; ++d) {
             const float fv = fj[(size_t)d * S + r];
 #pragma unroll
@@ -117,14 +109,9 @@ AGAN_PAIR_UNROLL
         float acc[TMAX];
 #pragma unroll
         for (int w = 0; w < TMAX; ++w) acc[w] = 0.f;
-        #ifdef AGAN_PAIR_NO_T
-        const float* fr = fj + (size_t)tid * S;
-        const int fs = 1;
-#else
         const float* fr = fjT ? fjT + tid : fj + (size_t)tid * S;
         const int fs = fjT ? D : 1;
-#endif
-AGAN_PAIR_UNROLL
+#pragma unroll 4
         for (int q = 0; q < S; ++q) {
             const float fv = fr[(size_t)q * fs];
 #pragma unroll
@@ -353,7 +340,8 @@ __global__ __launch_bounds__(kNT) void words_pair_fwd_mfma_kernel(const float* _
     }
 }
 
-__global__ __launch_bounds__(kNT) __attribute__((amdgpu_waves_per_eu(AGAN_PAIR_MFMA_WAVES))) void words_pair_bwd_mfma_kernel(
+constexpr int kPairMfmaWaves = 4;   // waves per SIMD the compiler budgets registers for
+__global__ __launch_bounds__(kNT) __attribute__((amdgpu_waves_per_eu(kPairMfmaWaves))) void words_pair_bwd_mfma_kernel(
     const float* __restrict__ feat, const float* __restrict__ featT, const float* __restrict__ wemb, const int64_t* __restrict__ lens,
     const float* __restrict__ dS, const float* __restrict__ dloss, float gamma1, float gamma2, float gamma3, float* __restrict__ part_f,
     float* __restrict__ part_w, int B, int D, int T, int S) {
@@ -621,7 +609,7 @@ __global__ __launch_bounds__(kNT) __attribute__((amdgpu_waves_per_eu(TMAX <= 12 
 #pragma unroll
     for (int w = 0; w < TMAX; ++w) { da2[w] = 0.f; a2r[w] = rlive ? sm.a2[r][w] : 0.f; }
     if (rlive) {
-AGAN_PAIR_UNROLL
+#pragma unroll 4
         for (int d = 0; d < D; ++d) {
             const float fv = fj[(size_t)d * S + r];
 #pragma unroll
@@ -672,14 +660,9 @@ AGAN_PAIR_UNROLL
     __syncthreads();
     // --- thread d: de[d][w] += sum_r ds[r][w] f[d][r];  dwemb[i][d][w] += de ---
     if (tid < D) {
-#ifdef AGAN_PAIR_NO_T
-        const float* fr = fj + (size_t)tid * S;
-        const int fs = 1;
-#else
         const float* fr = fjT + tid;
         const int fs = D;
-#endif
-AGAN_PAIR_UNROLL
+#pragma unroll 4
         for (int q = 0; q < S; ++q) {
             const float fv = fr[(size_t)q * fs];
 #pragma unroll

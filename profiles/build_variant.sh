@@ -1,24 +1,33 @@
 #!/bin/bash
-# usage: bash profiles/build_variant.sh NAME "-DFLAG ..." [file.hip ...]
-# Builds attention-gan_amd/csrc/variants/libagan_NAME.so: the shipped objects with the listed sources (default conv_p16.hip) recompiled
-# under the extra flags -- diagnostic / ablation builds for `AGAN_LIB=.../libagan_NAME.so python profiles/conv_micro.py ...` (never shipped).
-set -e
+# usage: bash profiles/build_variant.sh NAME "EXTRA FLAGS" [file.hip ...]
+# A/B builds of edited kernels.  Builds attention-gan_amd/csrc/variants/libagan_NAME.so: the shipped objects with the listed sources (default
+# conv_p16.hip) recompiled as they stand in the tree, EXTRA FLAGS (may be "") appended -- to time an edited kernel against the shipped library in
+# one process each, `AGAN_LIB=.../variants/libagan_NAME.so python profiles/conv_micro.py ...` (never shipped).
+# The source list, the compile and link lines and the per-file flags are csrc/Makefile's own (`make -n` prints its recipes).
+set -e -o pipefail
 NAME=$1; FLAGS=$2; shift 2 || true
-SRCS=${@:-conv_p16.hip}
+VARIANT_SRCS=${@:-conv_p16.hip}
 cd "$(dirname "$0")/../attention-gan_amd/csrc"
+SRCS=$(sed -n 's/^SRCS := //p' Makefile)
 make -j8 > /dev/null   # the shared objects must be current (headers change struct layouts)
 mkdir -p variants
-OBJS=""
-for o in conv conv_patch conv_p16 conv_wgrows conv_wino conv_small bn_act attention damsm heads comm; do
-  if echo " $SRCS " | grep -q " $o.hip "; then
-    EXTRA=""; [ "$o" = conv_small ] && EXTRA="-fno-slp-vectorize"      # (the shipped per-file flags: csrc/Makefile)
-    /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-function -Xclang -target-feature -Xclang -packed-fp32-ops $EXTRA $FLAGS -c $o.hip -o variants/${o}_$NAME.o \
-        2> >(grep -v "is not a recognized feature for this target" >&2)
-    OBJS="$OBJS variants/${o}_$NAME.o"
-  else
-    OBJS="$OBJS $o.o"
-  fi
+RECIPES=$(make -n -B libagan_hip.so)
+LINK=$(tail -n 1 <<< "$RECIPES")
+LINK=${LINK/-o libagan_hip.so/-o variants/libagan_$NAME.so}
+for s in $VARIANT_SRCS; do
+  o=${s%.hip}
+  echo " $SRCS " | grep -q " $s " || { echo "$s is not in the Makefile's SRCS" >&2; exit 1; }
+  COMPILE=$(grep -- " -c $s -o $o.o" <<< "$RECIPES")
+  # (hipcc names a compilation unit's device symbols after a hash of its whole command line, `-o` included: the variant is compiled under the
+  #  Makefile's own object name, the shipped object set aside meanwhile, so that an unchanged source with no extra flags gives the shipped code object)
+  mv $o.o variants/$o.shipped.o
+  trap "mv variants/$o.shipped.o $o.o" EXIT
+  eval "${COMPILE/ -o $o.o/ $FLAGS -o $o.o}"
+  mv $o.o variants/${o}_$NAME.o
+  mv variants/$o.shipped.o $o.o
+  trap - EXIT
+  LINK=${LINK/ $o.o/ variants/${o}_$NAME.o}
 done
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o variants/libagan_$NAME.so $OBJS -ldl
+eval "$LINK"
 rm -f variants/*_$NAME.o
 echo built variants/libagan_$NAME.so
