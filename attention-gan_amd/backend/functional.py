@@ -1644,3 +1644,48 @@ def lstm(xg, whh, bhh, lens: Tensor, save: bool) -> Tuple[Tensor, Tensor]:
     for x, w, b in zip(xg, whh, bhh):
         args += [x, w, b]
     return _LSTMFn.apply(lens, save, *args)
+
+
+def image_prep(planes, rows: Optional[Tensor], flip: Optional[Tensor], out=None):
+    """Batch preparation from resident uint8 images in ONE launch (include/agan.h: agan_image_prep).
+
+    planes: 1..3 entries, each a uint8 device tensor [n_src, C, H, W] (direct plane) or, after the first, an (H, W) pair: a plane
+    resampled from plane 0 (exactly / 2 or / 4, antialiased bilinear).  rows: int32 device [B] (None = 0..B-1), flip: uint8 device [B]
+    (None = no mirror).  out: the fp32 [B, C, H, W] tensors to write (None = new ones).  Returns the list of outputs: images in
+    [-1, 1], bit-identical to data.batches.scale_255_to_1 on direct planes.  No autograd: images are inputs."""
+    planes = list(planes)
+    src0 = planes[0] if planes else None
+    if not isinstance(src0, Tensor):
+        raise L.AganError("image_prep: plane 0 must be a uint8 tensor [n_src, C, H, W]")
+    for t, what, dtype in ((src0, "plane 0", torch.uint8), (rows, "rows", torch.int32), (flip, "flip", torch.uint8)):
+        if t is not None and not t.is_cuda:
+            raise L.AganError(f"image_prep {what}: tensor is on {t.device}; the AttnGAN HIP path runs on an MI355X only (no CPU fallback)")
+        if t is not None and (t.dtype != dtype or not t.is_contiguous()):
+            raise L.AganError(f"image_prep {what}: expected a contiguous {dtype} tensor, got {t.dtype}")
+    if src0.dim() != 4:
+        raise L.AganError(f"image_prep plane 0: expected [n_src, C, H, W], got {tuple(src0.shape)}")
+    n_src, C = int(src0.shape[0]), int(src0.shape[1])
+    B = int(rows.numel()) if rows is not None else (int(out[0].shape[0]) if out is not None else n_src)
+    if flip is not None and int(flip.numel()) != B:
+        raise L.AganError(f"image_prep flip: {int(flip.numel())} entries for a batch of {B}")
+    if out is not None and len(out) != len(planes):
+        raise L.AganError(f"image_prep out: {len(out)} tensors for {len(planes)} planes")
+    arr = (L.ImagePlane * max(1, len(planes)))()
+    outs = []
+    for i, p in enumerate(planes):
+        if isinstance(p, Tensor):
+            if p.device != src0.device or p.dtype != torch.uint8 or not p.is_contiguous() or p.dim() != 4 or tuple(p.shape[:2]) != (n_src, C):
+                raise L.AganError(f"image_prep plane {i}: expected a contiguous uint8 [{n_src}, {C}, H, W] tensor on {src0.device}")
+            H, W = int(p.shape[2]), int(p.shape[3])
+            arr[i].src = p.data_ptr()
+        else:
+            H, W = (int(v) for v in p)
+            arr[i].src = None
+        shape = (B, C, H, W)
+        o = torch.empty(shape, device=src0.device) if out is None else out[i]
+        if o.device != src0.device or o.dtype != torch.float32 or not o.is_contiguous() or tuple(o.shape) != shape:
+            raise L.AganError(f"image_prep out[{i}]: expected a contiguous float32 {shape} tensor on {src0.device}")
+        arr[i].dst, arr[i].H, arr[i].W = o.data_ptr(), H, W
+        outs.append(o)
+    L.call("agan_image_prep", arr, len(planes), _p(rows), _p(flip), B, C, n_src, _stream())
+    return outs

@@ -36,6 +36,11 @@ class Conv2dDesc(Structure):
                                        "in_c0", "in_ctot", "out_c0", "out_ctot")]
 
 
+class ImagePlane(Structure):
+    """struct agan_image_plane (agan_image_prep: src NULL = derived from plane 0)."""
+    _fields_ = [("src", c_void_p), ("dst", c_void_p), ("H", c_int32), ("W", c_int32)]
+
+
 _P = c_void_p
 _SIGNATURES = {
     # name: (restype, argtypes)
@@ -143,6 +148,7 @@ _SIGNATURES = {
     "agan_lstm_fwd": (c_int, [_P] * 11 + [c_int] * 4 + [_P]),
     "agan_lstm_bwd": (c_int, [_P] * 9 + [c_int] * 4 + [_P]),
     "agan_lstm_wgrad": (c_int, [_P] * 5 + [c_int] * 4 + [_P]),
+    "agan_image_prep": (c_int, [POINTER(ImagePlane), c_int, _P, _P, c_int, c_int, c_int, _P]),
     "agan_adam_step": (c_int, [_P, _P, _P, _P, c_size_t, _P, c_double, c_double, c_double, c_double, c_float, _P]),
 }
 

@@ -35,7 +35,8 @@ extern "C" {
  * Inception-v3 image-encoder trunk (agan_maxpool3s2_*, agan_avgpool3s1_*, agan_global_avgpool_*, agan_resize_bilinear_*, agan_relu_bwd);
  * the embedding gather and the LSTM recurrence of the caption encoder (agan_embedding_*, agan_lstm_*); the train-mode BatchNorm of the
  * trunk on channel slices (agan_bn_relu_slice_fwd, agan_bn_slice_bwd); the trainable general 2-D conv behind Layers.conv
- * (agan_conv2d_train_*: forward, data gradient and weight gradient of any small geometry). */
+ * (agan_conv2d_train_*: forward, data gradient and weight gradient of any small geometry); the batch preparation from device-resident
+ * uint8 shards (agan_image_prep). */
 
 enum {
     AGAN_OK = 0,
@@ -542,6 +543,32 @@ int agan_lstm_fwd(const float* xg0, const float* xg1, const float* whh0, const f
 int agan_lstm_bwd(const float* dout, const float* dhN, const float* whh0, const float* whh1, const float* gates, const float* cells,
                   const int32_t* lens, float* dg0, float* dg1, int B, int T, int H, int D, void* stream);
 int agan_lstm_wgrad(const float* dg0, const float* dg1, const float* out, float* dwhh, float* dbhh, int B, int T, int H, int D, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Batch preparation from device-resident uint8 shards (csrc/batch_prep.hip; data/batches.py: DeviceShardBatches).  A shard's uint8
+ * images stay in device memory; ONE launch gathers a batch's rows, mirrors the samples that ask for it and writes the fp32 images in
+ * [-1, 1] at up to three resolutions.  `planes` is a HOST array of n_planes (1..3) entries, read before the call returns; rows
+ * [B] int32 and flip [B] uint8 are device arrays (rows NULL = 0..B-1, flip NULL = no mirror); every dst is [B, C, H, W] fp32.
+ *   Direct plane (src != NULL; plane 0 always is): src is [n_src, C, H, W] uint8 and
+ *     dst[b, c, y, x] = (float(src[rows[b], c, y, x']) - 127.5f) / 127.5f,  x' = W-1-x where flip[b], else x
+ *     -- bit-identical to the reference's scale_255_to_1 (one IEEE division per pixel, no reciprocal multiply).
+ *   Derived plane (src == NULL, plane 1 or 2): resampled from plane 0, whose size must be exactly 2x or 4x this plane's on both axes,
+ *     with the antialiased bilinear (triangle) filter of torch.nn.functional.interpolate(mode="bilinear", antialias=True,
+ *     align_corners=False): per axis, output o takes taps 2o-1 .. 2o+2 with weights [1 3 3 1] / 8 (factor 2) or 4o-2 .. 4o+5 with
+ *     weights [1 3 5 7 7 5 3 1] / 32 (factor 4); taps outside the image are dropped and the rest renormalised by their sum (torch's
+ *     float64 CPU result agrees with these weights to 1e-12: tests/test_host_device_batches.py).  The weighted byte sum is an exact
+ *     integer num over an integer den, and the output is the single division (2 num - 255 den) / (255 den), every term below 2^24:
+ *     the correctly rounded fp32 of the exact value.  The mirror is applied to the source (by the filter's symmetry, the same as
+ *     mirroring the result).  Plane 0 may be at most 3072 (factor 4) / 6144 (factor 2) pixels wide for a derived plane.
+ *   A rows[b] outside [0, n_src) writes zeros for sample b in every plane and reads nothing (the rule of agan_embedding_fwd).
+ * One launch for all planes, no allocation, no synchronisation, no atomics: graph-capturable and run-to-run identical.  AGAN_EINVAL
+ * before any launch for n_planes outside 1..3, a plane 0 without src, a derived plane that is not plane 0 / 2 or / 4, a non-positive B,
+ * C, H, W or n_src, a missing dst, or a plane of 2^31 elements or more.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct agan_image_plane { const uint8_t* src; float* dst; int32_t H, W; } agan_image_plane;
+int agan_image_prep(const agan_image_plane* planes /* host array */, int n_planes /* 1..3 */,
+                    const int32_t* rows /* device [B], NULL = 0..B-1 */, const uint8_t* flip /* device [B], NULL = none */,
+                    int B, int C, int n_src, void* stream);
 
 #ifdef __cplusplus
 }
