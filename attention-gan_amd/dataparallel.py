@@ -10,6 +10,7 @@ point-to-point (7 links x ~153 GB/s per GPU), so few large messages beat many sm
 """
 from __future__ import annotations
 
+import contextlib
 import os
 from typing import List, Optional
 
@@ -39,25 +40,6 @@ def any_rank(flag: bool, group=None, device=None) -> bool:
     t = torch.tensor([1 if flag else 0], dtype=torch.int32, device=dev)
     dist.all_reduce(t, op=dist.ReduceOp.MAX, group=group)
     return bool(int(t.item()))
-
-
-@torch.no_grad()
-def sync_buffers_(module: torch.nn.Module, group=None) -> None:
-    """Average the floating-point buffers (BatchNorm running statistics) over the replicas, in place; integer buffers
-    (num_batches_tracked) are identical on every rank by construction.  Called before a checkpoint is written."""
-    w = world_size(group)
-    if w == 1:
-        return
-    bufs = [b for b in module.buffers() if b.is_floating_point()]
-    if not bufs:
-        return
-    flat = torch.cat([b.reshape(-1) for b in bufs])
-    dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=group)
-    flat.div_(w)
-    o = 0
-    for b in bufs:
-        b.copy_(flat[o:o + b.numel()].view_as(b))
-        o += b.numel()
 
 
 @torch.no_grad()
@@ -285,19 +267,26 @@ class GradBuckets:
             HF.join_all_side_streams(self.comm_stream)          # weight gradients forked onto side streams
             if self.direct is not None:
                 chunk.record_stream(self.comm_stream)
-                self.direct.all_reduce_(chunk, self.comm_stream, self.bf16)      # joined in finish() through the comm stream
+            elif os.environ.get("AGAN_DP_STUB") == "1":        # (measurement knob: the stream choreography without the collective)
                 return
-            if os.environ.get("AGAN_DP_STUB") == "1":          # (measurement knob: the stream choreography without the collective)
-                return
-            with torch.cuda.stream(self.comm_stream):
-                if self.bf16:
-                    all_reduce_bf16_(chunk, self.group)       # several ops, all on the comm stream; joined through it in finish()
-                else:
-                    self._handles.append(dist.all_reduce(chunk, op=dist.ReduceOp.SUM, group=self.group, async_op=True))
-        elif self.bf16:
-            all_reduce_bf16_(chunk, self.group)
-        else:
-            self._handles.append(dist.all_reduce(chunk, op=dist.ReduceOp.SUM, group=self.group, async_op=True))
+        self._send(chunk, self._handles)
+
+    def _send(self, chunk: torch.Tensor, handles: List) -> None:
+        """SUM all-reduce of one chunk of the flat gradient buffer by whatever moves the buckets (`mode`), on the comm stream if there
+        is one (the caller has made it wait for the gradients); an async handle is appended to `handles`.  Joined by _join()."""
+        if self.direct is not None:
+            self.direct.all_reduce_(chunk, self.comm_stream, self.bf16)      # joined through the comm stream
+            return
+        with torch.cuda.stream(self.comm_stream) if self.comm_stream is not None else contextlib.nullcontext():
+            if self.bf16:
+                all_reduce_bf16_(chunk, self.group)           # several ops, all on the comm stream; joined through it
+            else:
+                handles.append(dist.all_reduce(chunk, op=dist.ReduceOp.SUM, group=self.group, async_op=True))
+
+    @property
+    def scale(self) -> float:
+        """what the optimiser must multiply the exchanged (summed) gradient by: 1/world_size"""
+        return 1.0 / self.world if self.active else 1.0
 
     def exchange_all(self) -> float:
         """Exchange EVERY bucket now, after the backward has completed on the current stream (no hooks, no overlap with this
@@ -305,27 +294,15 @@ class GradBuckets:
         where the backward is a replayed HIP graph and Python hooks never run.  The collectives go out on the comm stream in bucket
         order; the current stream waits for them.  Returns the scale the optimiser must apply (1/world_size)."""
         if not self.active:
-            return 1.0
+            return self.scale
         cur = torch.cuda.current_stream() if self.opt.flat.is_cuda else None
-        handles = []
+        handles: List = []
         if self.comm_stream is not None:
             self.comm_stream.wait_stream(cur)
         for s, e in self.bounds:
-            chunk = self.opt.grad[s:e]
-            if self.direct is not None:
-                self.direct.all_reduce_(chunk, self.comm_stream, self.bf16)
-            elif self.comm_stream is not None:
-                with torch.cuda.stream(self.comm_stream):
-                    if self.bf16:
-                        all_reduce_bf16_(chunk, self.group)
-                    else:
-                        handles.append(dist.all_reduce(chunk, op=dist.ReduceOp.SUM, group=self.group, async_op=True))
-            elif self.bf16:
-                all_reduce_bf16_(chunk, self.group)
-            else:
-                handles.append(dist.all_reduce(chunk, op=dist.ReduceOp.SUM, group=self.group, async_op=True))
+            self._send(self.opt.grad[s:e], handles)
         self._join(cur, handles)
-        return 1.0 / self.world
+        return self.scale
 
     @property
     def mode(self) -> str:
@@ -363,7 +340,7 @@ class GradBuckets:
     def finish(self) -> float:
         """Join outstanding exchanges; returns the scale the optimiser must apply (1/world_size)."""
         if not self.active:
-            return 1.0
+            return self.scale
         # buckets whose parameters received no gradient this backward (unused params) are reduced too so that
         # every rank issues the same collectives
         for b, left in enumerate(self._pending):
@@ -372,4 +349,4 @@ class GradBuckets:
                 self._launch(b)
         self._join(torch.cuda.current_stream() if self.opt.flat.is_cuda else None, self._handles)
         self._handles, self._armed = [], False
-        return 1.0 / self.world
+        return self.scale

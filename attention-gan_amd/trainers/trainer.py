@@ -2,6 +2,7 @@
 train.py:109-151 as a reusable object (`GanTrainStep`) with flat-buffer Adam and overlapped gradient all-reduce."""
 from __future__ import annotations
 
+import collections
 import contextlib
 import math
 import os
@@ -128,6 +129,18 @@ class ModelTrainer:
                 print(f'FAILED: Module {name}... weights at path {path} were not found')
 
 
+# what the generator's forward leaves for the rest of the step
+_Forward = collections.namedtuple("_Forward", "labels mask fakes attn mu logvar")
+
+
+def _forked(streams, i: int, main):
+    """Context for work on discriminator i's stream, which first waits for `main`; without streams, the current one as it is."""
+    if streams is None:
+        return contextlib.nullcontext()
+    streams[i].wait_stream(main)
+    return torch.cuda.stream(streams[i])
+
+
 class GanTrainStep(ModelTrainer):
     """One batch of GanTrainer.train_gan (train.py:109-151): three discriminator updates, then one generator update.
 
@@ -202,6 +215,36 @@ class GanTrainStep(ModelTrainer):
             HF.set_wgrad_side_stream(prev_side)
 
     def _step(self, word_embs, sent_embs, lengths, class_ids, real_imgs, noise, eps) -> Dict[str, Tensor]:
+        fw = self._gen_forward(word_embs, sent_embs, lengths, noise, eps)
+        out: Dict[str, Tensor] = {}
+        # ---- discriminator updates (train.py:123-130) ----
+        # The three updates are independent of each other (each D has its own weights, optimiser and images), so each runs on
+        # its own HIP stream: the deep 4x4/8x8 layers of one discriminator (tiny grids) overlap the wide early layers of another.
+        # Autograd replays each backward on the stream its forward ran on.
+        main = torch.cuda.current_stream() if fw.fakes[0].is_cuda else None
+        streams = self._d_streams(len(self.Ds), fw.fakes[0].device) if (main is not None and self.overlap_discriminators) else None
+        if streams is not None:
+            for st in streams:                      # discriminator weight gradients run on the (otherwise idle) main stream
+                HF.set_side_stream_for(st, main)
+        for i in self.d_order:
+            with _forked(streams, i, main):
+                self._d_backward(i, fw, real_imgs, out, arm=True)
+                self._apply(f"D{i}", self.d_opts[i], self.d_buckets[i].finish())
+        if streams is not None:
+            for st in streams:
+                main.wait_stream(st)
+        # ---- generator update (train.py:132-151) ----
+        self._g_backward(fw, word_embs, sent_embs, lengths, class_ids, out, streams, arm=True)
+        self._apply("G", self.g_opt, self.g_buckets.finish())
+        # loss histories stay device tensors: no .item() host sync inside the step (reference syncs at train.py:130,144-145)
+        self.d_losses.append(out[f"d_loss{len(self.Ds) - 1}"])
+        self.g_losses.append(out[f"g_loss{len(self.Ds) - 1}"])
+        if "w_loss" in out:
+            self.damsm_losses.append(out["w_loss"] + out["s_loss"])
+        return self._results(fw, out)
+
+    # -- the phases of the step: _step() runs them eagerly, capture_segments() records each into a graph of its own --------
+    def _gen_forward(self, word_embs, sent_embs, lengths, noise, eps) -> "_Forward":
         b = word_embs.shape[0]
         labels = self._make_match_labels(b)
         mask = self._make_mask(lengths, word_embs.shape[2])
@@ -209,88 +252,81 @@ class GanTrainStep(ModelTrainer):
             noise = torch.randn(b, self.G.z_dim, dtype=torch.float32, device=word_embs.device, generator=self.rng)
         if eps is None:
             eps = torch.randn(b, self.G.cond_dim, dtype=torch.float32, device=word_embs.device, generator=self.rng)
-        fakes, _attn, mu, logvar = self.G(noise, sent_embs, word_embs, mask, eps)
-        out: Dict[str, Tensor] = {}
-        # ---- discriminator updates (train.py:123-130) ----
-        # The three updates are independent of each other (each D has its own weights, optimiser and images), so each runs on
-        # its own HIP stream: the deep 4x4/8x8 layers of one discriminator (tiny grids) overlap the wide early layers of another.
-        # Autograd replays each backward on the stream its forward ran on.
-        main = torch.cuda.current_stream() if fakes[0].is_cuda else None
-        streams = self._d_streams(len(self.Ds), fakes[0].device) if (main is not None and self.overlap_discriminators) else None
-        if streams is not None:
-            for st in streams:                      # discriminator weight gradients run on the (otherwise idle) main stream
-                HF.set_side_stream_for(st, main)
-        for i in self.d_order:
-            d, opt, bk = self.Ds[i], self.d_opts[i], self.d_buckets[i]
-            if streams is not None:
-                streams[i].wait_stream(main)
-                ctx = torch.cuda.stream(streams[i])
-            else:
-                ctx = contextlib.nullcontext()
-            with ctx:
-                opt.zero_grad()
-                bk.arm()
-                loss = self.disc_loss.get_loss(d, fakes[i].detach(), real_imgs[i])
-                loss.backward()
-                scale = bk.finish()
-                if self.on_gradients is not None:
-                    opt.join_and_rebind()
-                    self.on_gradients(f"D{i}", opt)
-                opt.step(scale)
-                out[f"d_loss{i}"] = loss.detach()
-        if streams is not None:
-            for st in streams:
-                main.wait_stream(st)
-        # ---- generator update (train.py:132-151) ----
+        return _Forward(labels, mask, *self.G(noise, sent_embs, word_embs, mask, eps))
+
+    def _d_backward(self, i: int, fw: "_Forward", real_imgs, out: Dict[str, Tensor], arm: bool = False) -> None:
+        """Discriminator i's gradients on the current stream; `arm`: its buckets exchange them from the backward's hooks."""
+        self.d_opts[i].zero_grad()
+        if arm:
+            self.d_buckets[i].arm()
+        loss = self.disc_loss.get_loss(self.Ds[i], fw.fakes[i].detach(), real_imgs[i])
+        loss.backward()
+        out[f"d_loss{i}"] = loss.detach()
+
+    def _g_backward(self, fw: "_Forward", word_embs, sent_embs, lengths, class_ids, out: Dict[str, Tensor],
+                    streams: Optional[List] = None, arm: bool = False) -> None:
+        """The generator's gradients through the frozen discriminators.  With `streams` (one per discriminator) the adversarial
+        terms fan out over them and are joined on the current stream; without, everything runs on the current stream."""
         self.g_opt.zero_grad()
-        self.g_buckets.arm()
+        if arm:
+            self.g_buckets.arm()
+        main = torch.cuda.current_stream() if streams is not None else None
         for d in self.Ds:
             d.requires_grad_(False)
-        # adversarial terms: one stream per discriminator again (forward here, autograd replays the dgrad chains on the same
-        # streams); the DAMSM branch (image encoder + words/sentence loss) rides on the last discriminator's stream
-        terms = []
-        for i, d in enumerate(self.Ds):
+        try:
+            # adversarial terms: one stream per discriminator again (forward here, autograd replays the dgrad chains on the same
+            # streams); the DAMSM branch (image encoder + words/sentence loss) rides on the last discriminator's stream
+            terms = []
+            for i, d in enumerate(self.Ds):
+                with _forked(streams, i, main):
+                    gl = self.gen_loss.get_loss(d, fw.fakes[i])
+                    terms.append(gl)
+                    out[f"g_loss{i}"] = gl.detach()
+                    if i == len(self.Ds) - 1 and self.image_encoder is not None:
+                        regions, code = self.image_encoder(fw.fakes[i])
+                        wl, _ = self.words_loss.get_loss(regions, word_embs, fw.labels, lengths, class_ids)
+                        sl = self.sent_loss.get_loss(code, sent_embs, fw.labels, class_ids)
+                        terms += [wl, sl]
+                        out["w_loss"], out["s_loss"] = wl.detach(), sl.detach()
             if streams is not None:
-                streams[i].wait_stream(main)
-                ctx = torch.cuda.stream(streams[i])
-            else:
-                ctx = contextlib.nullcontext()
-            with ctx:
-                gl = self.gen_loss.get_loss(d, fakes[i])
-                terms.append(gl)
-                out[f"g_loss{i}"] = gl.detach()
-                if i == len(self.Ds) - 1 and self.image_encoder is not None:
-                    regions, code = self.image_encoder(fakes[i])
-                    wl, _ = self.words_loss.get_loss(regions, word_embs, labels, lengths, class_ids)
-                    sl = self.sent_loss.get_loss(code, sent_embs, labels, class_ids)
-                    terms += [wl, sl]
-                    out["w_loss"], out["s_loss"] = wl.detach(), sl.detach()
-        if streams is not None:
-            for st in streams:
-                main.wait_stream(st)
-        total = terms[0]
-        for t in terms[1:]:
-            total = total + t
-        kl = KL_loss(mu, logvar)
-        total = total + kl
-        out["kl"], out["g_total"] = kl.detach(), total.detach()
-        total.backward()
-        for d in self.Ds:
-            d.requires_grad_(True)
-        scale = self.g_buckets.finish()
+                for st in streams:
+                    main.wait_stream(st)
+            total = terms[0]
+            for t in terms[1:]:
+                total = total + t
+            kl = KL_loss(fw.mu, fw.logvar)
+            total = total + kl
+            out["kl"], out["g_total"] = kl.detach(), total.detach()
+            total.backward()
+        finally:
+            for d in self.Ds:
+                d.requires_grad_(True)
+
+    def _apply(self, tag: str, opt: FlatAdam, scale: float) -> None:
         if self.on_gradients is not None:
-            self.g_opt.join_and_rebind()
-            self.on_gradients("G", self.g_opt)
-        self.g_opt.step(scale)
-        # loss histories stay device tensors: no .item() host sync inside the step (reference syncs at train.py:130,144-145)
-        self.d_losses.append(out[f"d_loss{len(self.Ds) - 1}"])
-        self.g_losses.append(out[f"g_loss{len(self.Ds) - 1}"])
-        if "w_loss" in out:
-            self.damsm_losses.append(out["w_loss"] + out["s_loss"])
-        out["fake_imgs"] = [f.detach() for f in fakes]
-        out["attn_maps"] = [a.detach() for a in _attn]
-        out["mu"], out["logvar"] = mu.detach(), logvar.detach()
+            opt.join_and_rebind()
+            self.on_gradients(tag, opt)
+        opt.step(scale)
+
+    @staticmethod
+    def _results(fw: "_Forward", out: Dict[str, Tensor]) -> Dict[str, Tensor]:
+        out["fake_imgs"] = [f.detach() for f in fw.fakes]
+        out["attn_maps"] = [a.detach() for a in fw.attn]
+        out["mu"], out["logvar"] = fw.mu.detach(), fw.logvar.detach()
         return out
+
+    def _warm_up(self, who: str, word_embs, sent_embs, lengths, real_imgs, warmup: int, noise, eps) -> None:
+        """What both captures do first: `warmup` real train steps off the default stream, then the host-side tables."""
+        if not (isinstance(lengths, Tensor) and lengths.is_cuda and lengths.dtype == torch.int64):
+            raise ValueError(f"{who}(): lengths must be an int64 device tensor")
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):                      # warm-up off the default stream: tables, caches, allocator pools
+            for _ in range(max(1, warmup)):
+                self.step(word_embs, sent_embs, lengths, None, real_imgs, noise, eps)
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        HF.build_pack_tables()                             # the batched re-pack's job tables: host work, not capturable
 
     # -- whole-step HIP graph ----------------------------------------------------------------------------------------
     def capture(self, word_embs: Tensor, sent_embs: Tensor, lengths: Tensor, real_imgs: Sequence[Tensor], warmup: int = 2,
@@ -304,16 +340,7 @@ class GanTrainStep(ModelTrainer):
         training steps.  Single-process only: with world_size > 1 run the eager `step()`."""
         if self.g_buckets.active:
             raise RuntimeError("capture(): the all-reduce path is not captured; use step() under torch.distributed")
-        if not (isinstance(lengths, Tensor) and lengths.is_cuda and lengths.dtype == torch.int64):
-            raise ValueError("capture(): lengths must be an int64 device tensor")
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):                      # warm-up off the default stream: tables, caches, allocator pools
-            for _ in range(max(1, warmup)):
-                self.step(word_embs, sent_embs, lengths, None, real_imgs, noise, eps)
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        HF.build_pack_tables()                             # the batched re-pack's job tables: host work, not capturable
+        self._warm_up("capture", word_embs, sent_embs, lengths, real_imgs, warmup, noise, eps)
         graph = torch.cuda.CUDAGraph()
         if self.rng.device.type == "cuda":
             graph.register_generator_state(self.rng)       # noise / eps draws inside the graph advance this generator on replay
@@ -337,16 +364,7 @@ class GanTrainStep(ModelTrainer):
         first -- and nothing overlaps the generator's 28 MB.  The arguments become static input buffers exactly as for capture();
         the graphs share one memory pool and must be replayed in capture order (SegmentedStep.replay does).  Results are
         bit-identical to the eager step (tests/test_gpu_dataparallel.py, one-rank `nccl` rehearsal)."""
-        if not (isinstance(lengths, Tensor) and lengths.is_cuda and lengths.dtype == torch.int64):
-            raise ValueError("capture_segments(): lengths must be an int64 device tensor")
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):                      # warm-up off the default stream: tables, caches, allocator pools
-            for _ in range(max(1, warmup)):
-                self.step(word_embs, sent_embs, lengths, None, real_imgs, noise, eps)
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        HF.build_pack_tables()
+        self._warm_up("capture_segments", word_embs, sent_embs, lengths, real_imgs, warmup, noise, eps)
         # memory pools: graphs that share a pool must never run concurrently (a later capture re-uses the temporaries an earlier one
         # freed).  The three discriminator updates replay CONCURRENTLY on their own streams, so each gets a private pool for its two
         # graphs; the generator's graphs, which run alone, share one.
@@ -356,10 +374,7 @@ class GanTrainStep(ModelTrainer):
         # capture turns into "operation not permitted when stream is capturing" in THAT thread and kills the process (seen once in
         # the one-rank nccl rehearsal, round 3)
         mode = "thread_local"
-        dev = word_embs.device
-        n = len(self.Ds)
         seg = SegmentedStep(self)
-        b = word_embs.shape[0]
         buckets = [self.g_buckets] + self.d_buckets
         armed = [bk._armed for bk in buckets]
         for bk in buckets:
@@ -371,63 +386,31 @@ class GanTrainStep(ModelTrainer):
             if self.rng.device.type == "cuda":
                 g0.register_generator_state(self.rng)
             with torch.cuda.graph(g0, pool=pool, capture_error_mode=mode):
-                HF.amax_begin_step(dev)
-                labels = self._make_match_labels(b)
-                mask = self._make_mask(lengths, word_embs.shape[2])
-                z = noise if noise is not None else torch.randn(b, self.G.z_dim, dtype=torch.float32, device=dev, generator=self.rng)
-                e = eps if eps is not None else torch.randn(b, self.G.cond_dim, dtype=torch.float32, device=dev, generator=self.rng)
-                fakes, attn, mu, logvar = self.G(z, sent_embs, word_embs, mask, e)
+                HF.amax_begin_step(word_embs.device)
+                fw = self._gen_forward(word_embs, sent_embs, lengths, noise, eps)
             seg.gen_forward = g0
             out: Dict[str, Tensor] = {}
             # ---- discriminator updates: backward graph, (exchange), Adam graph ----
             for i in self.d_order:
-                d, opt = self.Ds[i], self.d_opts[i]
+                opt = self.d_opts[i]
                 gb = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(gb, pool=d_pools[i], capture_error_mode=mode):
-                    opt.zero_grad()
-                    loss = self.disc_loss.get_loss(d, fakes[i].detach(), real_imgs[i])
-                    loss.backward()
+                    self._d_backward(i, fw, real_imgs, out)
                     opt.join_and_rebind()
-                    out[f"d_loss{i}"] = loss.detach()
                 ga = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(ga, pool=d_pools[i], capture_error_mode=mode):
-                    opt.step(1.0 / self.d_buckets[i].world if self.d_buckets[i].active else 1.0)
+                    opt.step(self.d_buckets[i].scale)
                 seg.d_backward[i], seg.d_adam[i] = gb, ga
-            # ---- generator update ----
+            # ---- generator update: one stream, no class ids (as in the warm-up steps) ----
             gg = torch.cuda.CUDAGraph()
             with torch.cuda.graph(gg, pool=pool, capture_error_mode=mode):
-                self.g_opt.zero_grad()
-                for d in self.Ds:
-                    d.requires_grad_(False)
-                terms = []
-                for i, d in enumerate(self.Ds):
-                    gl = self.gen_loss.get_loss(d, fakes[i])
-                    terms.append(gl)
-                    out[f"g_loss{i}"] = gl.detach()
-                    if i == n - 1 and self.image_encoder is not None:
-                        regions, code = self.image_encoder(fakes[i])
-                        wl, _ = self.words_loss.get_loss(regions, word_embs, labels, lengths, None)
-                        sl = self.sent_loss.get_loss(code, sent_embs, labels, None)
-                        terms += [wl, sl]
-                        out["w_loss"], out["s_loss"] = wl.detach(), sl.detach()
-                total = terms[0]
-                for t in terms[1:]:
-                    total = total + t
-                kl = KL_loss(mu, logvar)
-                total = total + kl
-                out["kl"], out["g_total"] = kl.detach(), total.detach()
-                total.backward()
-                for d in self.Ds:
-                    d.requires_grad_(True)
+                self._g_backward(fw, word_embs, sent_embs, lengths, None, out)
                 self.g_opt.join_and_rebind()
             gadam = torch.cuda.CUDAGraph()
             with torch.cuda.graph(gadam, pool=pool, capture_error_mode=mode):
-                self.g_opt.step(1.0 / self.g_buckets.world if self.g_buckets.active else 1.0)
+                self.g_opt.step(self.g_buckets.scale)
             seg.g_backward, seg.g_adam = gg, gadam
-            out["fake_imgs"] = [f.detach() for f in fakes]
-            out["attn_maps"] = [a.detach() for a in attn]
-            out["mu"], out["logvar"] = mu.detach(), logvar.detach()
-            seg.out = out
+            seg.out = self._results(fw, out)
         finally:
             HF.set_wgrad_side_stream(prev_side)
             for bk, a in zip(buckets, armed):
@@ -575,9 +558,7 @@ class SegmentedStep:
         self.gen_forward.replay()
         streams = t._d_streams(len(t.Ds), next(t.G.parameters()).device)
         for i in t.d_order:                                # largest discriminator first: its exchange travels under the others' graphs
-            st = streams[i]
-            st.wait_stream(main)
-            with torch.cuda.stream(st):
+            with _forked(streams, i, main):
                 self.d_backward[i].replay()
                 t.d_buckets[i].exchange_all()              # on the comm stream, behind this stream; this stream waits for it
                 self.d_adam[i].replay()

@@ -276,8 +276,10 @@ def _segmented_worker(port, q, force_dp):
         for _ in range(2):
             out = seg.replay()
         torch.cuda.synchronize()
+        scalars = {k: float(v) for k, v in out.items() if isinstance(v, torch.Tensor) and v.dim() == 0}
         q.put(({k: v.detach().cpu().numpy() for k, v in G.state_dict().items()},
-               [{k: v.detach().cpu().numpy() for k, v in d.state_dict().items()} for d in Ds], float(out["g_total"]), float(out["d_loss2"])))
+               [{k: v.detach().cpu().numpy() for k, v in d.state_dict().items()} for d in Ds], float(out["g_total"]), float(out["d_loss2"]),
+               scalars, sorted(out), out["fake_imgs"][0].detach().cpu().numpy()))
     finally:
         if force_dp:
             import torch.distributed as dist
@@ -295,7 +297,7 @@ def test_segmented_graphs_equal_eager_steps(force_dp):
     q = ctx.Queue()
     p = ctx.Process(target=_segmented_worker, args=(free_port(), q, force_dp))
     p.start()
-    (g_sd, d_sds, g_total, d_loss2), = collect_from_children(q, [p])
+    (g_sd, d_sds, g_total, d_loss2, scalars, keys, fake0), = collect_from_children(q, [p])
     p.join(60)
     assert p.exitcode == 0
     dev = torch.device("cuda", 0)
@@ -306,6 +308,12 @@ def test_segmented_graphs_equal_eager_steps(force_dp):
         out = step.step(words, sent, lens, None, reals, noise, eps)
     torch.cuda.synchronize()
     assert float(out["g_total"]) == g_total and float(out["d_loss2"]) == d_loss2
+    assert set(out) == set(keys)                                      # replay() and step() hand back the same entries
+    eager = {k: float(v) for k, v in out.items() if isinstance(v, torch.Tensor) and v.dim() == 0}
+    assert set(eager) == set(scalars)
+    for k, v in eager.items():                                        # every scalar loss, not only the two above
+        assert v == scalars[k], k
+    assert np.array_equal(out["fake_imgs"][0].detach().cpu().numpy(), fake0)
     for k, v in G.state_dict().items():
         assert np.array_equal(v.detach().cpu().numpy(), g_sd[k]), k
     for d, sd in zip(Ds, d_sds):

@@ -546,9 +546,10 @@ def test_hip_graph_replay_equals_eager_steps():
             for _ in range(3):                                  # capture itself does not execute: 1 warm-up + 2 replays = 3 steps
                 out = st.step(d["words"], d["sent"], lens, None, d["reals"], d["noise"], d["eps"])
         torch.cuda.synchronize()
-        return st, {k: v.clone() for k, v in out.items() if isinstance(v, torch.Tensor) and v.dim() == 0}
-    a, oa = run(False)
-    b, ob = run(True)
+        return st, {k: v.clone() for k, v in out.items() if isinstance(v, torch.Tensor) and v.dim() == 0}, set(out)
+    a, oa, ka = run(False)
+    b, ob, kb = run(True)
+    assert ka == kb                                              # replay() and step() hand back the same entries
     assert int(a.g_opt.step_state[0]) == int(b.g_opt.step_state[0]) == 3
     # same kernels, same order per stream, no atomics: replay and eager agree bit for bit
     for k in oa:
