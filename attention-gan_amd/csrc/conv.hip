@@ -1162,7 +1162,13 @@ double agan_conv_executed_fraction(const agan_conv_geom* g, int prec, int wgrad,
         return route_wgrad(g, AGAN_PACK_FWD, prec, AGAN_DT_F32, AGAN_DT_F32).path == WgradPath::winograd ? 16.0 / 36.0 : 1.0;
     const GatherRoute r = route_gather(g, prec, AGAN_DT_F32, AGAN_DT_F32, !plain_epilogue);
     if (r.path != GatherPath::winograd) return 1.0;
-    return r.wino.s2 == 0 ? 16.0 / 36.0 : (r.wino.s2 == 1 ? 36.0 / 64.0 : 9.0 / 16.0);
+    switch (r.wino.kind) {
+    case WinoKind::conv4x4_s2: return 36.0 / 64.0;
+    case WinoKind::dgrad2x2_class: return 9.0 / 16.0;
+    case WinoKind::conv3x3:
+    case WinoKind::conv3x3_half: break;
+    }
+    return 16.0 / 36.0;
 }
 
 static const int kDtypes[] = {AGAN_DT_F32, AGAN_DT_BF16, AGAN_DT_F16};

@@ -346,9 +346,16 @@ struct RowsPlan {
     size_t slab, ws_bytes;
     FastDiv dXRT, dXR, dNBY;
 };
-// ---- Winograd F(2x2, 3x3) for the fp32 conv3x3 stride-1 gathers (conv_wino.hip) ----------------------------------------------------
+// ---- Winograd for the fp32 conv3x3 stride-1 and conv4x4 stride-2 gathers (conv_wino.hip) ----------------------------------------------------
+enum class WinoKind : int {
+    conv3x3,            // conv3x3 stride 1, forward or data gradient: F(2x2, 3x3), one workgroup per CU (conv_wino_f32_kernel)
+    conv3x3_half,       // the same as 32 tiles x 64 channels, half the positions per wave, two workgroups per CU (conv_wino_h_f32_kernel)
+    conv4x4_s2,         // conv4x4 stride 2 forward: polyphase F(2x2, 2x2) (conv_wino_s2_f32_kernel)
+    dgrad2x2_class,     // its data gradient: F(2x2, 2x2) per output parity class (conv_wino_cls_f32_kernel)
+};
 struct WinoPlan {
-    int ok, s2, hmode;                  // hmode: conv3x3 as 32 tiles x 64 channels, half the positions per wave, two workgroups per CU;  s2: conv4x4 stride 2 (polyphase F(2x2, 2x2)) instead of conv3x3 stride 1 (F(2x2, 3x3))
+    int ok;
+    WinoKind kind;
     int txl, tyl;                       // log2 of the tile block's columns / rows (2x2-output tiles); images per block = 32 >> (txl + tyl)
     int blocks_x, blocks_y, blocks_b, mtiles;
     int nf, ntiles;                     // cout fragments per workgroup (4: 128 channels, 2: 64), cout tiles

@@ -58,214 +58,350 @@ __global__ __launch_bounds__(256) void wino_weight_transform_kernel(const float*
     }
 }
 
-// NFW = cout fragments per workgroup: 4 (128 output channels x 32 tiles) or 2 (64 output channels x 64 tiles).  Wave w owns cout fragment
-// w % NFW of tile group w / NFW and ALL 16 transform positions of it (16 accumulator fragments = 256 registers, one wave per SIMD): a lane
-// then holds the whole 4 x 4 product of its (tile, output channel) and the output transform never leaves its registers.  (The first
-// version gave every wave one nu of all cout fragments: the nu-direction of the output transform went through 64 KB of LDS and four
-// barriers per workgroup -- with one workgroup per CU that epilogue and the prologue were a third of its time.)
-template <int NFW>
-__global__ __launch_bounds__(256, 1) void conv_wino_f32_kernel(const float* __restrict__ x, const float* __restrict__ U, float* __restrict__ out,
-                                                               const Geom g, const WinoPlan wp) {
-    constexpr int NTG = 4 / NFW;                                   // 32-tile groups per workgroup
-    constexpr int NTL = 32 * NTG;                                  // tiles per workgroup
-    constexpr int LT = NTG == 1 ? 5 : 6;                           // log2 of that
-    constexpr int NI = NTG == 1 ? 7 : 11;                          // raw staging values per thread and chunk
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int fw = w % NFW, tg = w / NFW;
-    const int l31 = lane & 31, lh = lane >> 5;
-    int mt, nt;
-    {
-        const int F = xcd_contiguous(linear_block_id(), wp.mtiles * wp.ntiles);
-        nt = F % wp.ntiles; mt = F / wp.ntiles;
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The gather kernels are ONE program in four variants (WinoKind).  A workgroup owns a block of 32 or 64 Winograd tiles x some output
+// channels and walks the input channels a chunk at a time; per chunk every wave runs `stages` groups of 4 MFMAs, and everything else the
+// chunk needs stands between those groups (WinoGather::accumulate).  What differs between the variants is in this record, which
+// plan_wino reads for its sizes and limits and the kernels read for theirs: one place to change.
+struct WinoTraits {
+    int step, extra, origin;    // raw patch of a block of T tiles per dimension: step * T + extra rows / columns from input row step * t0 + origin (class form: + py / px)
+    int cch;                    // input channels per chunk
+    int planes, classes;        // transformed-weight planes [plane][Cin / 8][Nld][8] in the workspace; grid entries per block that share them out (parity classes)
+    int stages, nacc;           // 4-MFMA stages per chunk and wave; accumulator fragments per wave
+    int vfrags;                 // V fragments [tile][8 channels] per chunk = stages of all the waves of a cout fragment
+    int pieces;                 // input-transform pieces per 32-tile group and chunk
+    int ni32, ni64;             // raw staging values per thread and chunk, 32- / 64-tile blocks (0: that block size is not built)
+    int lds_cap;                // dynamic LDS the kernel may ask for (80 KB: two workgroups per CU)
+    int s_u_second, s_raw_load, s_u_next, s_transform, s_raw_store;      // slots of the chunk loop: the stage in front of whose MFMAs each piece of other work stands
+    bool mulshift;              // item -> (row, column) of the staging map by multiply-shift (WinoPlan::mpc / mpr) instead of % and /: exact only for
+                                //   items < 2048 and divisors <= 18, i.e. the 32-tile 3x3 blocks; the others stage up to 21 * 256 items with divisors up to 34
+    bool store1_late;           // prologue: chunk 1's patch is loaded after chunk 0's is stored and stored after the first transform (one register set)
+};
+constexpr WinoTraits wino_traits(WinoKind k) {
+    WinoTraits t{};
+    t.origin = -1; t.classes = 1; t.lds_cap = 160 * 1024; t.s_u_second = 0; t.s_raw_load = 1;
+    switch (k) {
+    case WinoKind::conv3x3:             // F(2x2, 3x3), a wave = all 16 positions of one cout fragment
+        t.step = 2; t.extra = 2; t.cch = 8; t.planes = 16; t.stages = 16; t.nacc = 16; t.vfrags = 16; t.pieces = 4; t.ni32 = 7; t.ni64 = 11;
+        t.s_u_next = 8; t.s_transform = 1; t.s_raw_store = 14;
+        break;
+    case WinoKind::conv3x3_half:        // the same, a wave = half the positions; 32-tile blocks only
+        t.step = 2; t.extra = 2; t.cch = 8; t.planes = 16; t.stages = 8; t.nacc = 8; t.vfrags = 16; t.pieces = 4; t.ni32 = 7;
+        t.s_u_next = 4; t.s_transform = 1; t.s_raw_store = 6; t.lds_cap = 80 * 1024; t.mulshift = true;
+        break;
+    case WinoKind::conv4x4_s2:          // four phases of F(2x2, 2x2): 36 (phase, position) planes into 9 accumulators; built for 128-channel tiles
+        t.step = 4; t.extra = 2; t.cch = 8; t.planes = 36; t.stages = 36; t.nacc = 9; t.vfrags = 36; t.pieces = 4; t.ni32 = 21;
+        t.s_u_next = 18; t.s_transform = 2; t.s_raw_store = 32; t.store1_late = true;
+        break;
+    case WinoKind::dgrad2x2_class:      // F(2x2, 2x2) per parity class, 16 channels per chunk: stage = (position, 8-channel half); 128-channel tiles
+        t.step = 2; t.extra = 1; t.cch = 16; t.planes = 36; t.classes = 4; t.stages = 18; t.nacc = 9; t.vfrags = 18; t.pieces = 2; t.ni32 = 11;
+        t.s_u_next = 9; t.s_transform = 2; t.s_raw_store = 15; t.store1_late = true;
+        break;
     }
-    const int n0 = nt * (NFW * 32);
-    const int txl = wp.txl, tyl = wp.tyl;                           // log2 of the tile block's columns / rows; images = NTL >> (txl + tyl)
-    const int TX = 1 << txl, TY = 1 << tyl;
-    const int bxi = mt % wp.blocks_x, byi = (mt / wp.blocks_x) % wp.blocks_y, bbi = mt / (wp.blocks_x * wp.blocks_y);
-    const int tx0 = bxi << txl, ty0 = byi << tyl, tb0 = bbi << (LT - txl - tyl);
-    const int ihw = g.IH * g.IW, ohw = g.OH * g.OW;
-    const int PR = 2 * TY + 2, PC = 2 * TX + 2;                     // raw patch rows / columns per image
-    const int PCP = wp.pcp;                                        // row pitch (floats)
-    float* const raw = reinterpret_cast<float*>(lds);                               // [2 buffers][tb][8 ci][PR][PCP]
-    const int RAWBUF = wp.raw_bytes >> 2;                                           // floats per raw buffer
-    float* const V = reinterpret_cast<float*>(lds + 2 * wp.raw_bytes);              // [2 buffers][16 pos][NTL tiles][8 ci]
-    constexpr int VBUF = 16 * NTL * 8;
-    const __amdgpu_buffer_rsrc_t rx = make_rsrc(x, (size_t)g.B * g.Cin * ihw * sizeof(float));
-    const __amdgpu_buffer_rsrc_t rU = make_rsrc(U, (size_t)16 * (g.Cin >> 3) * g.Nld * 8 * sizeof(float));
-    const int nch = g.Cin >> 3;
+    return t;
+}
 
-    // ---- raw staging items: (image, channel, row, column), column fastest ----
-    unsigned it_lds[NI];
-    int it_off[NI];                       // element offset of (b, ci, row, col) relative to channel chunk 0, or -1
+// F(2x2, 2x2) input transform B^T d B of the 3x3 patch at src, every D-th row (pitch `pcp` floats) and column, B^T = [[1,-1,0],[0,1,0],[0,-1,1]]:
+// nine values, `pp` floats apart from o on
+template <int D>
+__device__ __forceinline__ void wino_input_f22(const float* src, int pcp, float* o, int pp) {
+    float t[3][3];
 #pragma unroll
-    for (int i = 0; i < NI; ++i) {
-        const int e = tid + i * 256;
-        const int col = e % PC, t1 = e / PC;
-        const int row = t1 % PR, t2 = t1 / PR;
-        const int ci = t2 & 7, tb = t2 >> 3;
-        const int b = tb0 + tb, iy = 2 * ty0 - 1 + row, ix = 2 * tx0 - 1 + col;
-        const bool ok = (e < wp.raw_items) & (b < g.B) & ((unsigned)iy < (unsigned)g.IH) & ((unsigned)ix < (unsigned)g.IW);
-        it_off[i] = ok ? (b * g.Cin + ci) * ihw + iy * g.IW + ix : -1;
-        it_lds[i] = (unsigned)(((tb * 8 + ci) * PR + row) * PCP + col);
+    for (int j = 0; j < 3; ++j) {
+        const float d0 = src[D * j], d1 = src[D * pcp + D * j], d2 = src[2 * D * pcp + D * j];
+        t[0][j] = d0 - d1; t[1][j] = d1; t[2][j] = d2 - d1;
     }
-    float rawv[NI];
-    auto load_raw = [&](int ch, float (&rv)[NI]) {
 #pragma unroll
-        for (int i = 0; i < NI; ++i)
-            rv[i] = buf_load_s(rx, it_off[i] >= 0 ? (unsigned)it_off[i] * 4u : kOOB, (unsigned)(ch * 8 * ihw) * 4u);
-    };
-    auto store_raw = [&](int ch, const float (&rv)[NI]) {      // chunk ch's patch -> raw buffer ch & 1
-        float* const rb = raw + (ch & 1) * RAWBUF;
-#pragma unroll
-        for (int i = 0; i < NI; ++i)
-            if (tid + i * 256 < wp.raw_items) rb[it_lds[i]] = rv[i];
-    };
-    // ---- input transform: thread (tile tt = (tid >> 3) + 32 k, channel ci = tid & 7) ----
-    const int tci = tid & 7;
-    auto transform = [&](float* Vb) {                          // (the prologue's: chunk 0, raw buffer 0)
-#pragma unroll
-        for (int k = 0; k < NTG; ++k) {
-            const int tt = (tid >> 3) + 32 * k;
-            const int ttx = tt & (TX - 1), tty = (tt >> txl) & (TY - 1), ttb = tt >> (txl + tyl);
-            const float* const tsrc = raw + ((ttb * 8 + tci) * PR + 2 * tty) * PCP + 2 * ttx;
-            float d[4][4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const float2 a = *reinterpret_cast<const float2*>(tsrc + i * PCP), b = *reinterpret_cast<const float2*>(tsrc + i * PCP + 2);
-                d[i][0] = a.x; d[i][1] = a.y; d[i][2] = b.x; d[i][3] = b.y;
-            }
-            // t = B^T d: rows (d0 - d2, d1 + d2, d2 - d1, d1 - d3); v = t B: columns likewise
-            float t[4][4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                t[0][j] = d[0][j] - d[2][j];
-                t[1][j] = d[1][j] + d[2][j];
-                t[2][j] = d[2][j] - d[1][j];
-                t[3][j] = d[1][j] - d[3][j];
-            }
-#pragma unroll
-            for (int xi = 0; xi < 4; ++xi) {
-                const float v0 = t[xi][0] - t[xi][2], v1 = t[xi][1] + t[xi][2], v2 = t[xi][2] - t[xi][1], v3 = t[xi][1] - t[xi][3];
-                Vb[((xi * 4 + 0) * NTL + tt) * 8 + tci] = v0;
-                Vb[((xi * 4 + 1) * NTL + tt) * 8 + tci] = v1;
-                Vb[((xi * 4 + 2) * NTL + tt) * 8 + tci] = v2;
-                Vb[((xi * 4 + 3) * NTL + tt) * 8 + tci] = v3;
-            }
-        }
-    };
-    // ---- transformed weights: this wave's cout fragment, 16 bytes (channels 4 * lh ..) per lane and position; half a chunk's positions
-    //      (8) at a time, so that two register sets of 8 fragments suffice ----
-    const unsigned ulane = (unsigned)(min(n0 + fw * 32 + l31, g.Nld - 1) * 32 + lh * 16);      // (rows past Cout are zero in U)
-    auto load_u = [&](int ch, int half, u32x4 (&uf)[8]) {
-#pragma unroll
-        for (int q = 0; q < 8; ++q)
-            uf[q] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                rU, ulane, (unsigned)(((half * 8 + q) * nch + min(ch, nch - 1)) * g.Nld) * 32u, 0));
-    };
-
-    f32x16 acc[16];
-#pragma unroll
-    for (int q = 0; q < 16; ++q)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[q][r] = 0.f;
-
-    u32x4 ua[8], ub[8];                  // weights of positions 0..7 / 8..15: each set is reloaded while the other one's products run
-    // transform of the next chunk, in 4 * NTG pieces (one output row xi of one tile group each) that ride between the MFMA groups
-    float td[NTG][4][4];
-    auto transform_piece = [&](const float* rb, float* Vb, int pi) {
-        const int k = pi >> 2, xi = pi & 3;
-        const int tt = (tid >> 3) + 32 * k;
-        if (xi == 0) {
-            const int ttx = tt & (TX - 1), tty = (tt >> txl) & (TY - 1), ttb = tt >> (txl + tyl);
-            const float* const tsrc = rb + ((ttb * 8 + tci) * PR + 2 * tty) * PCP + 2 * ttx;
-            float d[4][4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const float2 a = *reinterpret_cast<const float2*>(tsrc + i * PCP), b = *reinterpret_cast<const float2*>(tsrc + i * PCP + 2);
-                d[i][0] = a.x; d[i][1] = a.y; d[i][2] = b.x; d[i][3] = b.y;
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {                       // t = B^T d
-                td[k][0][j] = d[0][j] - d[2][j];
-                td[k][1][j] = d[1][j] + d[2][j];
-                td[k][2][j] = d[2][j] - d[1][j];
-                td[k][3][j] = d[1][j] - d[3][j];
-            }
-        }
-        const float v0 = td[k][xi][0] - td[k][xi][2], v1 = td[k][xi][1] + td[k][xi][2], v2 = td[k][xi][2] - td[k][xi][1], v3 = td[k][xi][1] - td[k][xi][3];
-        Vb[((xi * 4 + 0) * NTL + tt) * 8 + tci] = v0;
-        Vb[((xi * 4 + 1) * NTL + tt) * 8 + tci] = v1;
-        Vb[((xi * 4 + 2) * NTL + tt) * 8 + tci] = v2;
-        Vb[((xi * 4 + 3) * NTL + tt) * 8 + tci] = v3;
-    };
-    {   // prologue: the patches of chunks 0 and 1 in flight together, chunk 0 transformed
-        float rawv1[NI];
-        load_raw(0, rawv);
-        if (nch > 1) load_raw(1, rawv1);
-        load_u(0, 0, ua);
-        store_raw(0, rawv);
-        if (nch > 1) store_raw(1, rawv1);
-        lds_barrier_w();
-        transform(V);
-        lds_barrier_w();
+    for (int xi = 0; xi < 3; ++xi) {
+        o[(xi * 3 + 0) * pp] = t[xi][0] - t[xi][1]; o[(xi * 3 + 1) * pp] = t[xi][1]; o[(xi * 3 + 2) * pp] = t[xi][2] - t[xi][1];
     }
-    for (int ch = 0; ch < nch; ++ch) {
-        const float* Vc = V + (ch & 1) * VBUF;
-        float* Vn = V + ((ch + 1) & 1) * VBUF;
-        const float* rn = raw + ((ch + 1) & 1) * RAWBUF;      // the raw patch of chunk ch + 1: in LDS since the last barrier
-        const bool more = ch + 1 < nch;
-        // 16 stages, one per transform position: [V fragment of the NEXT stage] [a piece of the other work] [this stage's 4 MFMAs = 256
-        // cycles of the matrix pipe].  The wave issues in order, so whatever must hide behind the MFMAs has to stand between them in
-        // program order; sched_barrier pins the stages.  Other work of chunk ch: the input transform of chunk ch + 1 (stages 1 .. 4 NTG),
-        // the global loads of chunk ch + 2's raw patch (stage 1) and its LDS stores (stage 14, into the buffer chunk ch's patch has left),
-        // the weight fragments (stages 0 and 8).  ONE barrier per chunk.
-        const unsigned vlane = (unsigned)((tg * 32 + l31) * 8 + lh * 4);
-        u32x4 vf[2];
-        vf[0] = *reinterpret_cast<const u32x4*>(Vc + vlane);
-#pragma unroll
-        for (int pos = 0; pos < 16; ++pos) {
-            if (pos + 1 < 16) vf[(pos + 1) & 1] = *reinterpret_cast<const u32x4*>(Vc + (pos + 1) * NTL * 8 + vlane);
-            if (pos == 0) load_u(ch, 1, ub);                  // second half of this chunk's weights
-            if (pos == 1 && ch + 2 < nch) load_raw(ch + 2, rawv);
-            if (pos == 8) load_u(ch + 1, 0, ua);              // first half of the next chunk's (past the end: a harmless repeat)
-            if (more && pos >= 1 && pos <= 4 * NTG) transform_piece(rn, Vn, pos - 1);
-            if (pos == 14 && ch + 2 < nch) store_raw(ch + 2, rawv);
-            const u32x4 uf = pos < 8 ? ua[pos & 7] : ub[pos & 7];
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                acc[pos] = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(uf[j]), __uint_as_float(vf[pos & 1][j]), acc[pos], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        lds_barrier_w();                                      // V of chunk ch + 1 and the raw patch of chunk ch + 2 are complete; every wave is done with chunk ch
-    }
+}
 
-    // ---- output transform, in registers: Y = A^T M A with M[xi][nu] = acc[xi * 4 + nu], A^T = [[1, 1, 1, 0], [0, 1, -1, -1]] ----
-    const int lt = tg * 32 + l31;
-    const int tx = lt & (TX - 1), ty = (lt >> txl) & (TY - 1), tb = lt >> (txl + tyl);
-    const int b = tb0 + tb, oy = 2 * (ty0 + ty), ox = 2 * (tx0 + tx);
-    const bool pvalid = (b < g.B) & (oy < g.OH) & (ox < g.OW);
-    const __amdgpu_buffer_rsrc_t ro = make_rsrc(out, (size_t)g.B * g.Cout * ohw * sizeof(float));
-    const int nw = n0 + fw * 32;
-    typedef float f32x2_ __attribute__((ext_vector_type(2)));
-    typedef unsigned u32x2_ __attribute__((ext_vector_type(2)));
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
+// output transform Y = A^T M A of register r of the accumulators M[xi][nu] = acc[xi * N + nu]: y = {y00, y01, y10, y11}.
+// 16 accumulators: A^T = [[1, 1, 1, 0], [0, 1, -1, -1]] (F(2x2, 3x3)); 9: A^T = [[1, 1, 0], [0, 1, 1]] (F(2x2, 2x2))
+template <int NACC>
+__device__ __forceinline__ void wino_output_2x2(const f32x16 (&acc)[NACC], int r, float (&y)[4]) {
+    if constexpr (NACC == 16) {
         float c0[4], c1[4];
 #pragma unroll
         for (int nu = 0; nu < 4; ++nu) {
             c0[nu] = acc[0 + nu][r] + acc[4 + nu][r] + acc[8 + nu][r];
             c1[nu] = acc[4 + nu][r] - acc[8 + nu][r] - acc[12 + nu][r];
         }
-        const float y00 = c0[0] + c0[1] + c0[2], y01 = c0[1] - c0[2] - c0[3];
-        const float y10 = c1[0] + c1[1] + c1[2], y11 = c1[1] - c1[2] - c1[3];
-        const int n = nw + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        const bool ok = pvalid & (n < g.Cout);
-        const unsigned off = (unsigned)((b * g.Cout + n) * ohw + oy * g.OW + ox) * 4u;
-        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2_, f32x2_{y00, y01}), ro, ok ? off : kOOB, 0, 0);
-        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2_, f32x2_{y10, y11}), ro, ok ? off + (unsigned)g.OW * 4u : kOOB, 0, 0);
+        y[0] = c0[0] + c0[1] + c0[2]; y[1] = c0[1] - c0[2] - c0[3];
+        y[2] = c1[0] + c1[1] + c1[2]; y[3] = c1[1] - c1[2] - c1[3];
+    } else {
+        static_assert(NACC == 9, "F(2x2, 3x3) or F(2x2, 2x2)");
+        float c0[3], c1[3];
+#pragma unroll
+        for (int nu = 0; nu < 3; ++nu) {
+            c0[nu] = acc[nu][r] + acc[3 + nu][r];
+            c1[nu] = acc[3 + nu][r] + acc[6 + nu][r];
+        }
+        y[0] = c0[0] + c0[1]; y[1] = c0[1] + c0[2];
+        y[2] = c1[0] + c1[1]; y[3] = c1[1] + c1[2];
     }
+}
+
+// The state and the pieces of one gather workgroup; NTG = 32-tile groups per workgroup (tiles = 32 NTG, cout fragments = 4 / NTG).
+// Wave w owns cout fragment fw and ALL positions of tile group tg (16 / 9 accumulator fragments, one wave per SIMD): a lane then holds the
+// whole product of its (tile, output channel) and the output transform never leaves its registers.  (The first version gave every wave
+// one nu of all cout fragments: the nu-direction of the output transform went through 64 KB of LDS and four barriers per workgroup -- with
+// one workgroup per CU that epilogue and the prologue were a third of its time.)  The half form splits the positions over the wave pair
+// (fw, hh) instead: see conv_wino_h_f32_kernel.
+template <WinoKind K, int NTG>
+struct WinoGather {
+    static constexpr WinoTraits T = wino_traits(K);
+    static constexpr bool kHalf = K == WinoKind::conv3x3_half, kS2 = K == WinoKind::conv4x4_s2, kCls = K == WinoKind::dgrad2x2_class;
+    static constexpr bool k3x3 = T.nacc != 9;
+    static constexpr int NFW = kHalf ? 2 : 4 / NTG;                // cout fragments per workgroup
+    static constexpr int NTL = 32 * NTG, LT = NTG == 1 ? 5 : 6;    // tiles per workgroup, log2 of that
+    static constexpr int NI = NTG == 1 ? T.ni32 : T.ni64;          // raw staging values per thread and chunk
+    static constexpr int CCH = T.cch, C8 = T.cch / 8;              // channels / channel octets per chunk
+    static constexpr int S = T.stages, SH = T.stages / 2, NACC = T.nacc;
+    static constexpr int NPIECE = T.pieces * NTG;
+    static constexpr int VBUF = T.vfrags * NTL * 8;                // floats per V buffer
+    static constexpr int STEP = T.step;
+    static_assert(NI > 0, "this block size of the variant is not built: plan_wino must not route to it");
+    static_assert(T.s_u_next == SH && T.s_transform + NPIECE <= S && T.s_raw_store < S, "slots of the chunk loop");
+
+    const Geom& g;
+    const WinoPlan& wp;
+    int tid, lane, w, fw, tg, hh, l31, lh;
+    int mt, nt, ks, py, px;               // ks: which part of the input channels (stride 2: partial sums to slab ks);  (py, px): parity class
+    int n0, txl, tyl, TX, TY, tx0, ty0, tb0, ihw, ohw, PR, PC, PCP, RAWBUF;
+    float *raw, *V;                       // LDS: raw [2 buffers][tb][CCH ci][PR][PCP];  V [2 buffers][vfrags (x C8: position)][NTL tiles][8 (CCH) ci]
+    __amdgpu_buffer_rsrc_t rx, rU;
+    int nch8, c_beg, nch;                 // channel octets of the layer; this workgroup's chunks: c_beg .. c_beg + nch
+    int iy0, ix0;                         // first input row / column of the block's raw patch
+
+    // (Scalars only: the register arrays of a kernel -- staging maps, patch values, weights, accumulators -- are locals of accumulate and of
+    //  the kernels, each on its own, so that the compiler sees every one of them as registers from the start.)
+    // ---- block and lane decode ----
+    __device__ __forceinline__ WinoGather(const float* x, const float* U, const Geom& g_, const WinoPlan& wp_) : g(g_), wp(wp_) {
+        extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+        tid = threadIdx.x; lane = tid & 63;
+        w = __builtin_amdgcn_readfirstlane(tid >> 6);
+        fw = w % NFW; tg = kHalf ? 0 : w / NFW; hh = kHalf ? w / NFW : 0;
+        l31 = lane & 31; lh = lane >> 5;
+        ks = py = px = 0;
+        {
+            int F = xcd_contiguous(linear_block_id(), wp.mtiles * wp.ntiles * (kS2 ? wp.ksplit : T.classes));
+            nt = F % wp.ntiles; F /= wp.ntiles;
+            if constexpr (kS2) { mt = F % wp.mtiles; ks = F / wp.mtiles; }
+            else if constexpr (kCls) { py = (F & 3) >> 1; px = F & 1; mt = F >> 2; }       // (the four classes of a block read the same dy patch: neighbours)
+            else mt = F;
+        }
+        n0 = nt * (NFW * 32);
+        txl = wp.txl; tyl = wp.tyl;                                 // log2 of the tile block's columns / rows; images = NTL >> (txl + tyl)
+        TX = 1 << txl; TY = 1 << tyl;
+        const int bxi = mt % wp.blocks_x, byi = (mt / wp.blocks_x) % wp.blocks_y, bbi = mt / (wp.blocks_x * wp.blocks_y);
+        tx0 = bxi << txl; ty0 = byi << tyl; tb0 = bbi << (LT - txl - tyl);
+        ihw = g.IH * g.IW; ohw = g.OH * g.OW;
+        PR = STEP * TY + T.extra; PC = STEP * TX + T.extra;       // raw patch rows / columns per image
+        PCP = wp.pcp;                                              // row pitch (floats)
+        raw = reinterpret_cast<float*>(lds);
+        RAWBUF = wp.raw_bytes >> 2;                                // floats per raw buffer
+        V = reinterpret_cast<float*>(lds + 2 * wp.raw_bytes);
+        nch8 = g.Cin >> 3;
+        if constexpr (kS2) { c_beg = ks * wp.chunks_per_split; nch = min(nch8, c_beg + wp.chunks_per_split) - c_beg; }
+        else { c_beg = 0; nch = g.Cin >> (CCH == 8 ? 3 : 4); }
+        constexpr int PPC = T.planes / T.classes;                  // weight planes of one class
+        rx = make_rsrc(x, (size_t)g.B * g.Cin * ihw * sizeof(float));
+        rU = make_rsrc(U + (size_t)(py * 2 + px) * PPC * nch8 * g.Nld * 8, (size_t)PPC * nch8 * g.Nld * 8 * sizeof(float));
+        iy0 = STEP * ty0 + T.origin + py; ix0 = STEP * tx0 + T.origin + px;
+    }
+
+    // ---- raw staging items: (image, channel, row, column), column fastest.  it_off: element offset of (b, ci, row, col) relative to channel
+    //      chunk 0, or -1;  it_lds: float offset in a raw buffer ----
+    __device__ __forceinline__ void stage_items(int (&it_off)[NI], unsigned (&it_lds)[NI]) const {
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            const int e = tid + i * 256;
+            int col, row, t2;                                      // t2 = (image of the block, channel of the chunk)
+            if constexpr (T.mulshift) {                            // e / d = (e * ceil(65536 / d)) >> 16: two VALU instructions instead of the ~12 of a
+                const int t1 = (int)(__umul24(e, wp.mpc) >> 16);   // general division; 24-bit multiplies are full rate
+                col = e - (int)__umul24(t1, PC);
+                t2 = (int)(__umul24(t1, wp.mpr) >> 16); row = t1 - (int)__umul24(t2, PR);
+            } else {
+                col = e % PC; const int t1 = e / PC;
+                row = t1 % PR; t2 = t1 / PR;
+            }
+            const int ci = t2 & (CCH - 1), b = tb0 + (t2 >> (CCH == 8 ? 3 : 4)), iy = iy0 + row, ix = ix0 + col;
+            const bool ok = (e < wp.raw_items) & (b < g.B) & ((unsigned)iy < (unsigned)g.IH) & ((unsigned)ix < (unsigned)g.IW);
+            if constexpr (T.mulshift) {
+                it_off[i] = ok ? (int)__umul24(b * g.Cin + ci, ihw) + iy * g.IW + ix : -1;
+                it_lds[i] = (unsigned)((int)__umul24(__umul24(t2, PR) + row, PCP) + col);
+            } else {
+                it_off[i] = ok ? (b * g.Cin + ci) * ihw + iy * g.IW + ix : -1;
+                it_lds[i] = (unsigned)((t2 * PR + row) * PCP + col);
+            }
+        }
+    }
+
+    __device__ __forceinline__ void load_raw(const int (&it_off)[NI], int ch, float (&rv)[NI]) const {
+#pragma unroll
+        for (int i = 0; i < NI; ++i)
+            rv[i] = buf_load_s(rx, it_off[i] >= 0 ? (unsigned)it_off[i] * 4u : kOOB, (unsigned)((c_beg + ch) * CCH * ihw) * 4u);
+    }
+    __device__ __forceinline__ void store_raw(const unsigned (&it_lds)[NI], int ch, const float (&rv)[NI]) const {      // chunk ch's patch -> raw buffer ch & 1
+        float* const rb = raw + (ch & 1) * RAWBUF;
+#pragma unroll
+        for (int i = 0; i < NI; ++i)
+            if (tid + i * 256 < wp.raw_items) rb[it_lds[i]] = rv[i];
+    }
+    // half a chunk's stages at a time, so that two register sets of SH fragments suffice.  Stage s of wave half hh: plane hh * S + s / C8,
+    // channel octet s % C8 of the chunk (past the last chunk: a harmless repeat of it)
+    __device__ __forceinline__ void load_u(int ch, int half, u32x4 (&uf)[SH]) const {
+        // this wave's cout fragment of U: 16 bytes (channels 4 * lh ..) per lane and plane  (rows past Cout are zero in U)
+        const unsigned ulane = (unsigned)(min(n0 + fw * 32 + l31, g.Nld - 1) * 32 + lh * 16);
+#pragma unroll
+        for (int q = 0; q < SH; ++q) {
+            const int s = half * SH + q;
+            uf[q] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
+                rU, ulane, (unsigned)(((hh * S + s / C8) * nch8 + (c_beg + min(ch, nch - 1)) * C8 + s % C8) * g.Nld) * 32u, 0));
+        }
+    }
+
+    // ---- input transform of the raw patch rb into Vb, piece pi of NPIECE: thread (tile tt = (tid >> 3) + 32 k, channel tid & 7 (+ 8)).
+    //      F(2x2, 3x3): one output row xi of tile group k (t = B^T d at xi = 0: rows (d0 - d2, d1 + d2, d2 - d1, d1 - d3); v = t B: columns
+    //      likewise; td keeps t between the pieces);  stride 2: one phase (p, q) -- every second row / column of the tile's 6 x 6 pixels;
+    //      class form: one channel half ----
+    __device__ __forceinline__ void transform_piece(const float* rb, float* Vb, int pi, float (&td)[NTG][4][4]) const {
+        const int k = pi / T.pieces, sub = pi % T.pieces;
+        const int tt = (tid >> 3) + 32 * k, ci = (tid & 7) + (kCls ? 8 * sub : 0);
+        const int p = kS2 ? sub >> 1 : 0, q = kS2 ? sub & 1 : 0;
+        if (!k3x3 || sub == 0) {
+            const int ttx = tt & (TX - 1), tty = (tt >> txl) & (TY - 1), ttb = tt >> (txl + tyl);
+            const float* const src = rb + ((ttb * CCH + ci) * PR + STEP * tty + p) * PCP + STEP * ttx + q;
+            if constexpr (k3x3) {
+                float d[4][4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const float2 a = *reinterpret_cast<const float2*>(src + i * PCP), b = *reinterpret_cast<const float2*>(src + i * PCP + 2);
+                    d[i][0] = a.x; d[i][1] = a.y; d[i][2] = b.x; d[i][3] = b.y;
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    td[k][0][j] = d[0][j] - d[2][j];
+                    td[k][1][j] = d[1][j] + d[2][j];
+                    td[k][2][j] = d[2][j] - d[1][j];
+                    td[k][3][j] = d[1][j] - d[3][j];
+                }
+            } else if constexpr (kS2) wino_input_f22<2>(src, PCP, Vb + (sub * 9 * NTL + tt) * 8 + ci, NTL * 8);
+            else wino_input_f22<1>(src, PCP, Vb + tt * 16 + ci, NTL * 16);
+        }
+        if constexpr (k3x3) {
+            const float (&t)[4] = td[k][sub];
+            float* const o = Vb + (sub * 4 * NTL + tt) * 8 + ci;
+            o[0] = t[0] - t[2]; o[NTL * 8] = t[1] + t[2]; o[2 * NTL * 8] = t[2] - t[1]; o[3 * NTL * 8] = t[1] - t[3];
+        }
+    }
+
+    // ---- acc = this wave's products over the workgroup's input channels ----
+    __device__ __forceinline__ void accumulate(f32x16 (&acc)[NACC]) const {
+        int it_off[NI];
+        unsigned it_lds[NI];
+        stage_items(it_off, it_lds);
+        float rawv[NI];
+        float td[NTG][4][4];
+        u32x4 ua[SH], ub[SH];             // weights of the first / second half of the stages: each set is reloaded while the other one's products run
+#pragma unroll
+        for (int q = 0; q < NACC; ++q)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[q][r] = 0.f;
+        {   // prologue: the patches of chunks 0 and 1 on their way, chunk 0 transformed, the first weights loaded
+            float rawv1[NI];
+            load_raw(it_off, 0, rawv);
+            if (!T.store1_late && nch > 1) load_raw(it_off, 1, rawv1);
+            load_u(0, 0, ua);
+            store_raw(it_lds, 0, rawv);
+            if (nch > 1) {
+                if constexpr (T.store1_late) load_raw(it_off, 1, rawv);
+                else store_raw(it_lds, 1, rawv1);
+            }
+            lds_barrier_w();
+#pragma unroll
+            for (int pi = 0; pi < NPIECE; ++pi) transform_piece(raw, V, pi, td);
+            if (T.store1_late && nch > 1) store_raw(it_lds, 1, rawv);
+            lds_barrier_w();
+        }
+        // S stages per chunk: [V fragment of the NEXT stage] [a piece of the other work] [this stage's 4 MFMAs = 256 cycles of the matrix
+        // pipe].  The wave issues in order, so whatever must hide behind the MFMAs has to stand between them in program order;
+        // sched_barrier pins the stages.  Other work of chunk ch, at the slots of WinoTraits: the second half of its weights and the first
+        // half of the next chunk's, the global loads of chunk ch + 2's raw patch and, late, their LDS stores (into the buffer chunk ch's
+        // patch has left), the input transform of chunk ch + 1 piece by piece.  ONE barrier per chunk.
+        // (unroll 1: the body is one pinned schedule -- left alone, the compiler peels the last chunk off the loop: every MFMA twice in the code)
+#pragma unroll 1
+        for (int ch = 0; ch < nch; ++ch) {
+            const float* Vc = V + (ch & 1) * VBUF;
+            float* Vn = V + ((ch + 1) & 1) * VBUF;
+            const float* rn = raw + ((ch + 1) & 1) * RAWBUF;      // the raw patch of chunk ch + 1: in LDS since the last barrier
+            const bool more = ch + 1 < nch;
+            // stage st reads V fragment hh * S + st: position st / C8 (pitch NTL * CCH), channel octet st % C8, and feeds accumulator st / C8
+            // (stride 2: st % 9 -- the four phases share the nine)
+            const unsigned vlane = (unsigned)(hh * S * NTL * 8 + (tg * 32 + l31) * CCH + lh * 4);
+            u32x4 vf[2];
+            vf[0] = *reinterpret_cast<const u32x4*>(Vc + vlane);
+#pragma unroll
+            for (int st = 0; st < S; ++st) {
+                if (st + 1 < S) vf[(st + 1) & 1] = *reinterpret_cast<const u32x4*>(Vc + ((st + 1) / C8) * NTL * CCH + ((st + 1) % C8) * 8 + vlane);
+                if (st == T.s_u_second) load_u(ch, 1, ub);
+                if (st == T.s_raw_load && ch + 2 < nch) load_raw(it_off, ch + 2, rawv);
+                if (st == T.s_u_next) load_u(ch + 1, 0, ua);
+                if (more && st >= T.s_transform && st < T.s_transform + NPIECE) transform_piece(rn, Vn, st - T.s_transform, td);
+                if (st == T.s_raw_store && ch + 2 < nch) store_raw(it_lds, ch + 2, rawv);
+                const u32x4 uf = st < SH ? ua[st % SH] : ub[st % SH];
+                const int a = kS2 ? st % NACC : st / C8;
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    acc[a] = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(uf[j]), __uint_as_float(vf[st & 1][j]), acc[a], 0, 0, 0);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            lds_barrier_w();                                      // V of chunk ch + 1 and the raw patch of chunk ch + 2 are complete; every wave is done with chunk ch
+        }
+    }
+
+    // ---- output transform in registers, 2 x 2 pixels per lane and register: two 8-byte stores; class form: lattice point (yq, xq) -> pixel
+    //      (2 yq + py, 2 xq + px), the four outputs lie two pixels apart (scalar stores) ----
+    __device__ __forceinline__ void epilogue(const f32x16 (&acc)[NACC], float* out) const {
+        typedef float f32x2_ __attribute__((ext_vector_type(2)));
+        typedef unsigned u32x2_ __attribute__((ext_vector_type(2)));
+        const int lt = tg * 32 + l31;
+        const int tx = lt & (TX - 1), ty = (lt >> txl) & (TY - 1), tb = lt >> (txl + tyl);
+        const int b = tb0 + tb, oy = 2 * (ty0 + ty), ox = 2 * (tx0 + tx);
+        const bool pvalid = (b < g.B) & (oy < (kCls ? g.OHs : g.OH)) & (ox < (kCls ? g.OWs : g.OW));
+        const __amdgpu_buffer_rsrc_t ro = make_rsrc(out + (size_t)ks * wp.slab, (size_t)g.B * g.Cout * ohw * sizeof(float));
+        const int nw = n0 + fw * 32;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            float y[4];
+            wino_output_2x2(acc, r, y);
+            const int n = nw + (r & 3) + 8 * (r >> 2) + 4 * lh;
+            const bool ok = pvalid & (n < g.Cout);
+            if constexpr (kCls) {
+                const unsigned off = (unsigned)((b * g.Cout + n) * ohw + (2 * oy + py) * g.OW + 2 * ox + px) * 4u;
+                buf_store(ro, ok ? off : kOOB, y[0]);
+                buf_store(ro, ok ? off + 8u : kOOB, y[1]);
+                buf_store(ro, ok ? off + (unsigned)(2 * g.OW) * 4u : kOOB, y[2]);
+                buf_store(ro, ok ? off + (unsigned)(2 * g.OW + 2) * 4u : kOOB, y[3]);
+            } else {
+                const unsigned off = (unsigned)((b * g.Cout + n) * ohw + oy * g.OW + ox) * 4u;
+                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2_, f32x2_{y[0], y[1]}), ro, ok ? off : kOOB, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2_, f32x2_{y[2], y[3]}), ro, ok ? off + (unsigned)g.OW * 4u : kOOB, 0, 0);
+            }
+        }
+    }
+};
+
+// F(2x2, 3x3), conv3x3 stride 1.  NFW = cout fragments per workgroup: 4 (128 output channels x 32 tiles) or 2 (64 output channels x 64 tiles).
+template <int NFW>
+__global__ __launch_bounds__(256, 1) void conv_wino_f32_kernel(const float* __restrict__ x, const float* __restrict__ U, float* __restrict__ out,
+                                                               const Geom g, const WinoPlan wp) {
+    WinoGather<WinoKind::conv3x3, 4 / NFW> k(x, U, g, wp);
+    f32x16 acc[k.NACC];
+    k.accumulate(acc);
+    k.epilogue(acc, out);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -277,134 +413,9 @@ __global__ __launch_bounds__(256, 1) void conv_wino_f32_kernel(const float* __re
 // (32 floats per lane), then finishes the other.
 __global__ __launch_bounds__(256, 2) void conv_wino_h_f32_kernel(const float* __restrict__ x, const float* __restrict__ U, float* __restrict__ out,
                                                                  const Geom g, const WinoPlan wp) {
-    constexpr int NTL = 32, NI = 7;
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int fw = w & 1, hh = w >> 1;
-    const int l31 = lane & 31, lh = lane >> 5;
-    int mt, nt;
-    {
-        const int F = xcd_contiguous(linear_block_id(), wp.mtiles * wp.ntiles);
-        nt = F % wp.ntiles; mt = F / wp.ntiles;
-    }
-    const int n0 = nt * 64;
-    const int txl = wp.txl, tyl = wp.tyl;
-    const int TX = 1 << txl, TY = 1 << tyl;
-    const int bxi = mt % wp.blocks_x, byi = (mt / wp.blocks_x) % wp.blocks_y, bbi = mt / (wp.blocks_x * wp.blocks_y);
-    const int tx0 = bxi << txl, ty0 = byi << tyl, tb0 = bbi << (5 - txl - tyl);
-    const int ihw = g.IH * g.IW, ohw = g.OH * g.OW;
-    const int PR = 2 * TY + 2, PC = 2 * TX + 2;
-    const int PCP = wp.pcp;
-    float* const raw = reinterpret_cast<float*>(lds);
-    const int RAWBUF = wp.raw_bytes >> 2;
-    float* const V = reinterpret_cast<float*>(lds + 2 * wp.raw_bytes);
-    constexpr int VBUF = 16 * NTL * 8;
-    const __amdgpu_buffer_rsrc_t rx = make_rsrc(x, (size_t)g.B * g.Cin * ihw * sizeof(float));
-    const __amdgpu_buffer_rsrc_t rU = make_rsrc(U, (size_t)16 * (g.Cin >> 3) * g.Nld * 8 * sizeof(float));
-    const int nch = g.Cin >> 3;
-
-    unsigned it_lds[NI];
-    int it_off[NI];
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-        const int e = tid + i * 256;                               // < 2048: e / d = (e * ceil(65536 / d)) >> 16 exactly for d <= 18 (two VALU
-        const int t1 = (int)(__umul24(e, wp.mpc) >> 16), col = e - (int)__umul24(t1, PC);       // instructions instead of the ~12 of a general
-        const int t2 = (int)(__umul24(t1, wp.mpr) >> 16), row = t1 - (int)__umul24(t2, PR);     // division; 24-bit multiplies are full rate)
-        const int ci = t2 & 7, tb = t2 >> 3;
-        const int b = tb0 + tb, iy = 2 * ty0 - 1 + row, ix = 2 * tx0 - 1 + col;
-        const bool ok = (e < wp.raw_items) & (b < g.B) & ((unsigned)iy < (unsigned)g.IH) & ((unsigned)ix < (unsigned)g.IW);
-        it_off[i] = ok ? (int)__umul24(b * g.Cin + ci, ihw) + iy * g.IW + ix : -1;
-        it_lds[i] = (unsigned)((int)__umul24(__umul24(t2, PR) + row, PCP) + col);
-    }
-    float rawv[NI];
-    auto load_raw = [&](int ch, float (&rv)[NI]) {
-#pragma unroll
-        for (int i = 0; i < NI; ++i)
-            rv[i] = buf_load_s(rx, it_off[i] >= 0 ? (unsigned)it_off[i] * 4u : kOOB, (unsigned)(ch * 8 * ihw) * 4u);
-    };
-    auto store_raw = [&](int ch, const float (&rv)[NI]) {
-        float* const rb = raw + (ch & 1) * RAWBUF;
-#pragma unroll
-        for (int i = 0; i < NI; ++i)
-            if (tid + i * 256 < wp.raw_items) rb[it_lds[i]] = rv[i];
-    };
-    const int tci = tid & 7, tt = tid >> 3;
-    const int ttx = tt & (TX - 1), tty = (tt >> txl) & (TY - 1), ttb = tt >> (txl + tyl);
-    const int tsrc_off = ((ttb * 8 + tci) * PR + 2 * tty) * PCP + 2 * ttx;
-    float td[4][4];
-    auto transform_piece = [&](const float* rb, float* Vb, int xi) {
-        if (xi == 0) {
-            const float* const tsrc = rb + tsrc_off;
-            float d[4][4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const float2 a = *reinterpret_cast<const float2*>(tsrc + i * PCP), b = *reinterpret_cast<const float2*>(tsrc + i * PCP + 2);
-                d[i][0] = a.x; d[i][1] = a.y; d[i][2] = b.x; d[i][3] = b.y;
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                td[0][j] = d[0][j] - d[2][j];
-                td[1][j] = d[1][j] + d[2][j];
-                td[2][j] = d[2][j] - d[1][j];
-                td[3][j] = d[1][j] - d[3][j];
-            }
-        }
-        Vb[((xi * 4 + 0) * NTL + tt) * 8 + tci] = td[xi][0] - td[xi][2];
-        Vb[((xi * 4 + 1) * NTL + tt) * 8 + tci] = td[xi][1] + td[xi][2];
-        Vb[((xi * 4 + 2) * NTL + tt) * 8 + tci] = td[xi][2] - td[xi][1];
-        Vb[((xi * 4 + 3) * NTL + tt) * 8 + tci] = td[xi][1] - td[xi][3];
-    };
-    const unsigned ulane = (unsigned)(min(n0 + fw * 32 + l31, g.Nld - 1) * 32 + lh * 16);
-    auto load_u = [&](int ch, int half, u32x4 (&uf)[4]) {            // this wave's positions hh * 8 + half * 4 ..
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            uf[q] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                rU, ulane, (unsigned)(((hh * 8 + half * 4 + q) * nch + min(ch, nch - 1)) * g.Nld) * 32u, 0));
-    };
-
+    WinoGather<WinoKind::conv3x3_half, 1> k(x, U, g, wp);
     f32x16 acc[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[q][r] = 0.f;
-    u32x4 ua[4], ub[4];
-    {
-        float rawv1[NI];
-        load_raw(0, rawv);
-        if (nch > 1) load_raw(1, rawv1);
-        load_u(0, 0, ua);
-        store_raw(0, rawv);
-        if (nch > 1) store_raw(1, rawv1);
-        lds_barrier_w();
-#pragma unroll
-        for (int xi = 0; xi < 4; ++xi) transform_piece(raw, V, xi);
-        lds_barrier_w();
-    }
-    for (int ch = 0; ch < nch; ++ch) {
-        const float* Vc = V + (ch & 1) * VBUF;
-        float* Vn = V + ((ch + 1) & 1) * VBUF;
-        const float* rn = raw + ((ch + 1) & 1) * RAWBUF;
-        const bool more = ch + 1 < nch;
-        const unsigned vlane = (unsigned)(hh * 8 * NTL * 8 + l31 * 8 + lh * 4);
-        u32x4 vf[2];
-        vf[0] = *reinterpret_cast<const u32x4*>(Vc + vlane);
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            if (q + 1 < 8) vf[(q + 1) & 1] = *reinterpret_cast<const u32x4*>(Vc + (q + 1) * NTL * 8 + vlane);
-            if (q == 0) load_u(ch, 1, ub);
-            if (q == 1 && ch + 2 < nch) load_raw(ch + 2, rawv);
-            if (q == 4) load_u(ch + 1, 0, ua);
-            if (more && q >= 1 && q <= 4) transform_piece(rn, Vn, q - 1);
-            if (q == 6 && ch + 2 < nch) store_raw(ch + 2, rawv);
-            const u32x4 uf = q < 4 ? ua[q & 3] : ub[q & 3];
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(uf[j]), __uint_as_float(vf[q & 1][j]), acc[q], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        lds_barrier_w();
-    }
+    k.accumulate(acc);
 
     // ---- output transform: columns in registers, rows across the wave pair (fw, hh = 0 / 1).  acc[x2 * 4 + nu] = M[2 hh + x2][nu].
     //      hh = 0 holds rows 0, 1: output row 0 gets M0 + M1, row 1 gets M1;   hh = 1 holds rows 2, 3: row 0 gets M2, row 1 gets -M2 - M3.
@@ -413,15 +424,16 @@ __global__ __launch_bounds__(256, 2) void conv_wino_h_f32_kernel(const float* __
     //      wave: every VALU instruction here is ~0.04 % of the workgroup.  So: packed adds on (r, r + 1) register pairs (consecutive
     //      accumulator registers: no moves), one code path per hh (no selects), the register-dependent part of the store address in
     //      the scalar offset. ----
-    float* const X = reinterpret_cast<float*>(lds);            // [wave 4][32 values][64 lanes]
+    const int w = k.w, lane = k.lane, hh = k.hh, ohw = k.ohw;
+    float* const X = k.raw;                                     // [wave 4][32 values][64 lanes]
     typedef float f32x2_ __attribute__((ext_vector_type(2)));
     typedef unsigned u32x2_ __attribute__((ext_vector_type(2)));
-    const int tx = l31 & (TX - 1), ty = (l31 >> txl) & (TY - 1), tb = l31 >> (txl + tyl);
-    const int b = tb0 + tb, oy = 2 * (ty0 + ty) + hh, ox = 2 * (tx0 + tx);
+    const int tx = k.l31 & (k.TX - 1), ty = (k.l31 >> k.txl) & (k.TY - 1), tb = k.l31 >> (k.txl + k.tyl);
+    const int b = k.tb0 + tb, oy = 2 * (k.ty0 + ty) + hh, ox = 2 * (k.tx0 + tx);
     const bool pvalid = (b < g.B) & (oy < g.OH) & (ox < g.OW);
     const __amdgpu_buffer_rsrc_t ro = make_rsrc(out, (size_t)g.B * g.Cout * ohw * sizeof(float));
-    const int nw = n0 + fw * 32, pw = w ^ 2;                    // partner wave: same cout fragment, other position half
-    const unsigned vo = pvalid ? (unsigned)((b * g.Cout + nw + 4 * lh) * ohw + oy * g.OW + ox) * 4u : kOOB;
+    const int nw = k.n0 + k.fw * 32, pw = w ^ 2;                // partner wave: same cout fragment, other position half
+    const unsigned vo = pvalid ? (unsigned)((b * g.Cout + nw + 4 * k.lh) * ohw + oy * g.OW + ox) * 4u : kOOB;
     auto finish = [&](auto hc) {
         constexpr int HH = decltype(hc)::value;
         f32x2_ keep[8][2];                                       // [register pair][output column]; HH = 1: the NEGATIVE of its share
@@ -469,317 +481,40 @@ __global__ __launch_bounds__(256, 2) void conv_wino_h_f32_kernel(const float* __
 //     instead of 16:   B^T = [[1,-1,0],[0,1,0],[0,-1,1]],  G = [[1,0],[1,1],[0,1]],  A^T = [[1,1,0],[0,1,1]]  (all +-1: exact transforms
 //     up to the adds).  The output transform is the same for the four phases, so their products are summed in the SAME nine
 //     accumulators: 36 products per 2x2 outputs and input channel instead of 64.
-// Structure as conv_wino_f32_kernel: 32 tiles x 128 output channels per workgroup, a wave = one cout fragment x all 9 positions (144
-// accumulator registers), input channels 8 at a time = 36 stages (phase, position) of 4 MFMAs; the raw patch of a tile is 6 x 6 pixels
-// (rows / columns 4 t .. 4 t + 5 of the block's patch), a phase takes every second row / column of it.
+// 32 tiles x 128 output channels per workgroup, a wave = one cout fragment x all 9 positions (144 accumulator registers), input channels 8
+// at a time = 36 stages (phase, position); the raw patch of a tile is 6 x 6 pixels (rows / columns 4 t .. 4 t + 5 of the block's patch).
 template <int NFW>
 __global__ __launch_bounds__(256, 1) void conv_wino_s2_f32_kernel(const float* __restrict__ x, const float* __restrict__ U, float* __restrict__ out,
                                                                   const Geom g, const WinoPlan wp) {
-    constexpr int NTG = 4 / NFW, NTL = 32 * NTG, LT = NTG == 1 ? 5 : 6;
-    constexpr int NI = NTG == 1 ? 21 : 36;                         // raw staging values per thread and chunk
-    constexpr int NP = 36;                                         // (phase, position) planes
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int fw = w % NFW, tg = w / NFW;
-    const int l31 = lane & 31, lh = lane >> 5;
-    int mt, nt, ks;
-    {
-        int F = xcd_contiguous(linear_block_id(), wp.mtiles * wp.ntiles * wp.ksplit);
-        nt = F % wp.ntiles; F /= wp.ntiles;
-        mt = F % wp.mtiles; ks = F / wp.mtiles;                     // ks: which part of the input channels (partial sums to slab ks)
-    }
-    const int n0 = nt * (NFW * 32);
-    const int txl = wp.txl, tyl = wp.tyl;
-    const int TX = 1 << txl, TY = 1 << tyl;
-    const int bxi = mt % wp.blocks_x, byi = (mt / wp.blocks_x) % wp.blocks_y, bbi = mt / (wp.blocks_x * wp.blocks_y);
-    const int tx0 = bxi << txl, ty0 = byi << tyl, tb0 = bbi << (LT - txl - tyl);
-    const int ihw = g.IH * g.IW, ohw = g.OH * g.OW;
-    const int PR = 4 * TY + 2, PC = 4 * TX + 2;                     // raw patch rows / columns per image
-    const int PCP = wp.pcp;
-    float* const raw = reinterpret_cast<float*>(lds);                               // [2 buffers][tb][8 ci][PR][PCP]
-    const int RAWBUF = wp.raw_bytes >> 2;
-    float* const V = reinterpret_cast<float*>(lds + 2 * wp.raw_bytes);              // [2 buffers][36 planes][NTL tiles][8 ci]
-    constexpr int VBUF = NP * NTL * 8;
-    const __amdgpu_buffer_rsrc_t rx = make_rsrc(x, (size_t)g.B * g.Cin * ihw * sizeof(float));
-    const __amdgpu_buffer_rsrc_t rU = make_rsrc(U, (size_t)NP * (g.Cin >> 3) * g.Nld * 8 * sizeof(float));
-    const int nch_all = g.Cin >> 3;
-    const int c_beg = ks * wp.chunks_per_split, nch = min(nch_all, c_beg + wp.chunks_per_split) - c_beg;      // this workgroup's chunks: c_beg .. c_beg + nch
-
-    unsigned it_lds[NI];
-    int it_off[NI];
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-        const int e = tid + i * 256;
-        const int col = e % PC, t1 = e / PC;
-        const int row = t1 % PR, t2 = t1 / PR;
-        const int ci = t2 & 7, tb = t2 >> 3;
-        const int b = tb0 + tb, iy = 4 * ty0 - 1 + row, ix = 4 * tx0 - 1 + col;
-        const bool ok = (e < wp.raw_items) & (b < g.B) & ((unsigned)iy < (unsigned)g.IH) & ((unsigned)ix < (unsigned)g.IW);
-        it_off[i] = ok ? (b * g.Cin + ci) * ihw + iy * g.IW + ix : -1;
-        it_lds[i] = (unsigned)(((tb * 8 + ci) * PR + row) * PCP + col);
-    }
-    float rawv[NI];
-    auto load_raw = [&](int ch, float (&rv)[NI]) {
-#pragma unroll
-        for (int i = 0; i < NI; ++i)
-            rv[i] = buf_load_s(rx, it_off[i] >= 0 ? (unsigned)it_off[i] * 4u : kOOB, (unsigned)((c_beg + ch) * 8 * ihw) * 4u);
-    };
-    auto store_raw = [&](int ch, const float (&rv)[NI]) {
-        float* const rb = raw + (ch & 1) * RAWBUF;
-#pragma unroll
-        for (int i = 0; i < NI; ++i)
-            if (tid + i * 256 < wp.raw_items) rb[it_lds[i]] = rv[i];
-    };
-    // input transform, one (tile group k, phase) piece at a time: thread (tile (tid >> 3) + 32 k, channel tid & 7)
-    const int tci = tid & 7;
-    auto transform_piece = [&](const float* rb, float* Vb, int pi) {
-        const int k = pi >> 2, ph = pi & 3, p = ph >> 1, q = ph & 1;
-        const int tt = (tid >> 3) + 32 * k;
-        const int ttx = tt & (TX - 1), tty = (tt >> txl) & (TY - 1), ttb = tt >> (txl + tyl);
-        const float* const src = rb + ((ttb * 8 + tci) * PR + 4 * tty + p) * PCP + 4 * ttx + q;
-        float t[3][3];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const float d0 = src[2 * j], d1 = src[2 * PCP + 2 * j], d2 = src[4 * PCP + 2 * j];
-            t[0][j] = d0 - d1; t[1][j] = d1; t[2][j] = d2 - d1;
-        }
-#pragma unroll
-        for (int xi = 0; xi < 3; ++xi) {
-            float* o = Vb + ((ph * 9 + xi * 3) * NTL + tt) * 8 + tci;
-            o[0] = t[xi][0] - t[xi][1]; o[NTL * 8] = t[xi][1]; o[2 * NTL * 8] = t[xi][2] - t[xi][1];
-        }
-    };
-    const unsigned ulane = (unsigned)(min(n0 + fw * 32 + l31, g.Nld - 1) * 32 + lh * 16);
-    auto load_u = [&](int ch, int half, u32x4 (&uf)[18]) {           // planes 18 * half ..
-#pragma unroll
-        for (int q = 0; q < 18; ++q)
-            uf[q] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                rU, ulane, (unsigned)(((half * 18 + q) * nch_all + c_beg + min(ch, nch - 1)) * g.Nld) * 32u, 0));
-    };
-
-    f32x16 acc[9];
-#pragma unroll
-    for (int q = 0; q < 9; ++q)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[q][r] = 0.f;
-    u32x4 ua[18], ub[18];
-    {
-        load_raw(0, rawv);
-        load_u(0, 0, ua);
-        store_raw(0, rawv);
-        if (nch > 1) load_raw(1, rawv);
-        lds_barrier_w();
-#pragma unroll
-        for (int pi = 0; pi < 4 * NTG; ++pi) transform_piece(raw, V, pi);
-        if (nch > 1) store_raw(1, rawv);
-        lds_barrier_w();
-    }
-    for (int ch = 0; ch < nch; ++ch) {
-        const float* Vc = V + (ch & 1) * VBUF;
-        float* Vn = V + ((ch + 1) & 1) * VBUF;
-        const float* rn = raw + ((ch + 1) & 1) * RAWBUF;
-        const bool more = ch + 1 < nch;
-        const unsigned vlane = (unsigned)((tg * 32 + l31) * 8 + lh * 4);
-        u32x4 vf[2];
-        vf[0] = *reinterpret_cast<const u32x4*>(Vc + vlane);
-#pragma unroll
-        for (int st = 0; st < NP; ++st) {
-            if (st + 1 < NP) vf[(st + 1) & 1] = *reinterpret_cast<const u32x4*>(Vc + (st + 1) * NTL * 8 + vlane);
-            if (st == 0) load_u(ch, 1, ub);
-            if (st == 1 && ch + 2 < nch) load_raw(ch + 2, rawv);
-            if (st == 18) load_u(ch + 1, 0, ua);
-            if (more && st >= 2 && st < 2 + 4 * NTG) transform_piece(rn, Vn, st - 2);
-            if (st == 32 && ch + 2 < nch) store_raw(ch + 2, rawv);
-            const u32x4 uf = st < 18 ? ua[st % 18] : ub[st % 18];
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                acc[st % 9] = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(uf[j]), __uint_as_float(vf[st & 1][j]), acc[st % 9], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        lds_barrier_w();
-    }
-
-    // ---- output transform in registers: Y = A^T M A, M[xi][nu] = acc[xi * 3 + nu], A^T = [[1, 1, 0], [0, 1, 1]] ----
-    const int lt = tg * 32 + l31;
-    const int tx = lt & (TX - 1), ty = (lt >> txl) & (TY - 1), tb = lt >> (txl + tyl);
-    const int b = tb0 + tb, oy = 2 * (ty0 + ty), ox = 2 * (tx0 + tx);
-    const bool pvalid = (b < g.B) & (oy < g.OH) & (ox < g.OW);
-    const __amdgpu_buffer_rsrc_t ro = make_rsrc(out + (size_t)ks * wp.slab, (size_t)g.B * g.Cout * ohw * sizeof(float));
-    const int nw = n0 + fw * 32;
-    typedef float f32x2_ __attribute__((ext_vector_type(2)));
-    typedef unsigned u32x2_ __attribute__((ext_vector_type(2)));
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        float c0[3], c1[3];
-#pragma unroll
-        for (int nu = 0; nu < 3; ++nu) {
-            c0[nu] = acc[nu][r] + acc[3 + nu][r];
-            c1[nu] = acc[3 + nu][r] + acc[6 + nu][r];
-        }
-        const int n = nw + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        const bool ok = pvalid & (n < g.Cout);
-        const unsigned off = (unsigned)((b * g.Cout + n) * ohw + oy * g.OW + ox) * 4u;
-        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2_, f32x2_{c0[0] + c0[1], c0[1] + c0[2]}), ro, ok ? off : kOOB, 0, 0);
-        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2_, f32x2_{c1[0] + c1[1], c1[1] + c1[2]}), ro, ok ? off + (unsigned)g.OW * 4u : kOOB, 0, 0);
-    }
+    WinoGather<WinoKind::conv4x4_s2, 4 / NFW> k(x, U, g, wp);
+    f32x16 acc[k.NACC];
+    k.accumulate(acc);
+    k.epilogue(acc, out);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // Data gradient of conv4x4 stride 2: four parity classes of the output, each a 2x2-tap stride-1 gather over dy with taps running backwards
 // (include/agan.h: DY = -1, offsets (0, 1)).  Per class Winograd F(2x2, 2x2) on the class lattice: 9 products per 2x2 lattice points instead of
 // 16.  out[2 yq + py][2 xq + px] = sum_{r,s} Wc[r][s] dy[yq + py - r][xq + px - s] = correlation of the ascending window
-// (dy[yq + py - 1], dy[yq + py]) with g = (Wc[1], Wc[0]).  Same structure as the kernels above; a channel chunk is 16 channels = 18 stages
-// (position, 8-channel half) of 4 MFMAs; the four classes are grid entries; the 2x2 outputs of a tile lie two pixels apart (scalar stores).
+// (dy[yq + py - 1], dy[yq + py]) with g = (Wc[1], Wc[0]).  A channel chunk is 16 channels = 18 stages (position, 8-channel half); the
+// four classes are grid entries.
 template <int NFW>
 __global__ __launch_bounds__(256, 1) void conv_wino_cls_f32_kernel(const float* __restrict__ x, const float* __restrict__ U, float* __restrict__ out,
                                                                    const Geom g, const WinoPlan wp) {
-    constexpr int NTG = 4 / NFW, NTL = 32 * NTG, LT = NTG == 1 ? 5 : 6;
-    constexpr int NI = NTG == 1 ? 11 : 19;                         // raw staging values per thread and chunk (16 channels)
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int fw = w % NFW, tg = w / NFW;
-    const int l31 = lane & 31, lh = lane >> 5;
-    int mt, nt, cls;
-    {
-        int F = xcd_contiguous(linear_block_id(), wp.mtiles * wp.ntiles * 4);
-        nt = F % wp.ntiles; F /= wp.ntiles;
-        cls = F & 3; mt = F >> 2;                                   // (the four classes of a block read the same dy patch: neighbours)
-    }
-    const int py = cls >> 1, px = cls & 1;
-    const int n0 = nt * (NFW * 32);
-    const int txl = wp.txl, tyl = wp.tyl;
-    const int TX = 1 << txl, TY = 1 << tyl;
-    const int bxi = mt % wp.blocks_x, byi = (mt / wp.blocks_x) % wp.blocks_y, bbi = mt / (wp.blocks_x * wp.blocks_y);
-    const int tx0 = bxi << txl, ty0 = byi << tyl, tb0 = bbi << (LT - txl - tyl);
-    const int ihw = g.IH * g.IW, ohw = g.OH * g.OW;
-    const int PR = 2 * TY + 1, PC = 2 * TX + 1;
-    const int PCP = wp.pcp;
-    float* const raw = reinterpret_cast<float*>(lds);                               // [2 buffers][tb][16 ci][PR][PCP]
-    const int RAWBUF = wp.raw_bytes >> 2;
-    float* const V = reinterpret_cast<float*>(lds + 2 * wp.raw_bytes);              // [2 buffers][9 positions][NTL tiles][16 ci]
-    constexpr int VBUF = 9 * NTL * 16;
-    const __amdgpu_buffer_rsrc_t rx = make_rsrc(x, (size_t)g.B * g.Cin * ihw * sizeof(float));
-    const int nch8 = g.Cin >> 3, nch = g.Cin >> 4;
-    const __amdgpu_buffer_rsrc_t rU = make_rsrc(U + (size_t)cls * 9 * nch8 * g.Nld * 8, (size_t)9 * nch8 * g.Nld * 8 * sizeof(float));
+    WinoGather<WinoKind::dgrad2x2_class, 4 / NFW> k(x, U, g, wp);
+    f32x16 acc[k.NACC];
+    k.accumulate(acc);
+    k.epilogue(acc, out);
+}
 
-    unsigned it_lds[NI];
-    int it_off[NI];
+// (G g G^T) of a 2x2 kernel g, G = [[1,0],[1,1],[0,1]]: nine planes [xi * 3 + nu], `pp` floats apart from o on
+__device__ __forceinline__ void wino_weights_f22(const float (&gk)[2][2], float* o, size_t pp) {
+    const float t[3][2] = {{gk[0][0], gk[0][1]}, {gk[0][0] + gk[1][0], gk[0][1] + gk[1][1]}, {gk[1][0], gk[1][1]}};
 #pragma unroll
-    for (int i = 0; i < NI; ++i) {
-        const int e = tid + i * 256;
-        const int col = e % PC, t1 = e / PC;
-        const int row = t1 % PR, t2 = t1 / PR;
-        const int ci = t2 & 15, tb = t2 >> 4;
-        const int b = tb0 + tb, iy = 2 * ty0 + py - 1 + row, ix = 2 * tx0 + px - 1 + col;
-        const bool ok = (e < wp.raw_items) & (b < g.B) & ((unsigned)iy < (unsigned)g.IH) & ((unsigned)ix < (unsigned)g.IW);
-        it_off[i] = ok ? (b * g.Cin + ci) * ihw + iy * g.IW + ix : -1;
-        it_lds[i] = (unsigned)(((tb * 16 + ci) * PR + row) * PCP + col);
-    }
-    float rawv[NI];
-    auto load_raw = [&](int ch, float (&rv)[NI]) {
+    for (int xi = 0; xi < 3; ++xi) {
+        const float u[3] = {t[xi][0], t[xi][0] + t[xi][1], t[xi][1]};
 #pragma unroll
-        for (int i = 0; i < NI; ++i)
-            rv[i] = buf_load_s(rx, it_off[i] >= 0 ? (unsigned)it_off[i] * 4u : kOOB, (unsigned)(ch * 16 * ihw) * 4u);
-    };
-    auto store_raw = [&](int ch, const float (&rv)[NI]) {
-        float* const rb = raw + (ch & 1) * RAWBUF;
-#pragma unroll
-        for (int i = 0; i < NI; ++i)
-            if (tid + i * 256 < wp.raw_items) rb[it_lds[i]] = rv[i];
-    };
-    // input transform, one (tile, channel) pair per piece: pair pi of this thread = (tile (tid >> 3) + 32 (pi >> 1), channel (tid & 7) + 8 (pi & 1))
-    auto transform_piece = [&](const float* rb, float* Vb, int pi) {
-        const int tt = (tid >> 3) + 32 * (pi >> 1), ci = (tid & 7) + 8 * (pi & 1);
-        const int ttx = tt & (TX - 1), tty = (tt >> txl) & (TY - 1), ttb = tt >> (txl + tyl);
-        const float* const src = rb + ((ttb * 16 + ci) * PR + 2 * tty) * PCP + 2 * ttx;
-        float t[3][3];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const float d0 = src[j], d1 = src[PCP + j], d2 = src[2 * PCP + j];
-            t[0][j] = d0 - d1; t[1][j] = d1; t[2][j] = d2 - d1;
-        }
-#pragma unroll
-        for (int xi = 0; xi < 3; ++xi) {
-            float* o = Vb + ((xi * 3) * NTL + tt) * 16 + ci;
-            o[0] = t[xi][0] - t[xi][1]; o[NTL * 16] = t[xi][1]; o[2 * NTL * 16] = t[xi][2] - t[xi][1];
-        }
-    };
-    const unsigned ulane = (unsigned)(min(n0 + fw * 32 + l31, g.Nld - 1) * 32 + lh * 16);
-    auto load_u = [&](int ch, int half, u32x4 (&uf)[9]) {           // stages 9 * half ..: stage = position * 2 + 8-channel half
-#pragma unroll
-        for (int q = 0; q < 9; ++q) {
-            const int st = half * 9 + q;
-            uf[q] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                rU, ulane, (unsigned)(((st >> 1) * nch8 + 2 * min(ch, nch - 1) + (st & 1)) * g.Nld) * 32u, 0));
-        }
-    };
-
-    f32x16 acc[9];
-#pragma unroll
-    for (int q = 0; q < 9; ++q)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[q][r] = 0.f;
-    u32x4 ua[9], ub[9];
-    {
-        load_raw(0, rawv);
-        load_u(0, 0, ua);
-        store_raw(0, rawv);
-        if (nch > 1) load_raw(1, rawv);
-        lds_barrier_w();
-#pragma unroll
-        for (int pi = 0; pi < 2 * NTG; ++pi) transform_piece(raw, V, pi);
-        if (nch > 1) store_raw(1, rawv);
-        lds_barrier_w();
-    }
-    for (int ch = 0; ch < nch; ++ch) {
-        const float* Vc = V + (ch & 1) * VBUF;
-        float* Vn = V + ((ch + 1) & 1) * VBUF;
-        const float* rn = raw + ((ch + 1) & 1) * RAWBUF;
-        const bool more = ch + 1 < nch;
-        const unsigned vlane = (unsigned)((tg * 32 + l31) * 16 + lh * 4);
-        u32x4 vf[2];
-        vf[0] = *reinterpret_cast<const u32x4*>(Vc + vlane);
-#pragma unroll
-        for (int st = 0; st < 18; ++st) {
-            if (st + 1 < 18) vf[(st + 1) & 1] = *reinterpret_cast<const u32x4*>(Vc + ((st + 1) >> 1) * NTL * 16 + ((st + 1) & 1) * 8 + vlane);
-            if (st == 0) load_u(ch, 1, ub);
-            if (st == 1 && ch + 2 < nch) load_raw(ch + 2, rawv);
-            if (st == 9) load_u(ch + 1, 0, ua);
-            if (more && st >= 2 && st < 2 + 2 * NTG) transform_piece(rn, Vn, st - 2);
-            if (st == 15 && ch + 2 < nch) store_raw(ch + 2, rawv);
-            const u32x4 uf = st < 9 ? ua[st % 9] : ub[st % 9];
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                acc[st >> 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(uf[j]), __uint_as_float(vf[st & 1][j]), acc[st >> 1], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        lds_barrier_w();
-    }
-
-    // ---- output transform in registers: Y = A^T M A, A^T = [[1, 1, 0], [0, 1, 1]]; lattice point (yq, xq) -> pixel (2 yq + py, 2 xq + px) ----
-    const int lt = tg * 32 + l31;
-    const int tx = lt & (TX - 1), ty = (lt >> txl) & (TY - 1), tb = lt >> (txl + tyl);
-    const int b = tb0 + tb, yq = 2 * (ty0 + ty), xq = 2 * (tx0 + tx);
-    const bool pvalid = (b < g.B) & (yq < g.OHs) & (xq < g.OWs);
-    const __amdgpu_buffer_rsrc_t ro = make_rsrc(out, (size_t)g.B * g.Cout * ohw * sizeof(float));
-    const int nw = n0 + fw * 32;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        float c0[3], c1[3];
-#pragma unroll
-        for (int nu = 0; nu < 3; ++nu) {
-            c0[nu] = acc[nu][r] + acc[3 + nu][r];
-            c1[nu] = acc[3 + nu][r] + acc[6 + nu][r];
-        }
-        const int n = nw + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        const bool ok = pvalid & (n < g.Cout);
-        const unsigned off = (unsigned)((b * g.Cout + n) * ohw + (2 * yq + py) * g.OW + 2 * xq + px) * 4u;
-        buf_store(ro, ok ? off : kOOB, c0[0] + c0[1]);
-        buf_store(ro, ok ? off + 8u : kOOB, c0[1] + c0[2]);
-        buf_store(ro, ok ? off + (unsigned)(2 * g.OW) * 4u : kOOB, c1[0] + c1[1]);
-        buf_store(ro, ok ? off + (unsigned)(2 * g.OW + 2) * 4u : kOOB, c1[1] + c1[2]);
+        for (int nu = 0; nu < 3; ++nu) o[(xi * 3 + nu) * pp] = u[nu];
     }
 }
 
@@ -794,14 +529,7 @@ __global__ __launch_bounds__(256) void wino_cls_weight_transform_kernel(const fl
         for (int a = 0; a < 2; ++a)
 #pragma unroll
             for (int b = 0; b < 2; ++b) gk[a][b] = n < N ? wc[(size_t)(c * 4 + (1 - a) * 2 + (1 - b)) * Nld + n] : 0.f;
-        const float t[3][2] = {{gk[0][0], gk[0][1]}, {gk[0][0] + gk[1][0], gk[0][1] + gk[1][1]}, {gk[1][0], gk[1][1]}};
-#pragma unroll
-        for (int xi = 0; xi < 3; ++xi) {
-            const float u[3] = {t[xi][0], t[xi][0] + t[xi][1], t[xi][1]};
-#pragma unroll
-            for (int nu = 0; nu < 3; ++nu)
-                U[((size_t)((cls * 9 + xi * 3 + nu) * nch8 + (c >> 3)) * Nld + n) * 8 + (c & 7)] = u[nu];
-        }
+        wino_weights_f22(gk, U + ((size_t)(cls * 9 * nch8 + (c >> 3)) * Nld + n) * 8 + (c & 7), (size_t)nch8 * Nld * 8);
     }
 }
 
@@ -819,14 +547,7 @@ __global__ __launch_bounds__(256) void wino_s2_weight_transform_kernel(const flo
                 for (int a = 0; a < 2; ++a)
 #pragma unroll
                     for (int b = 0; b < 2; ++b) gk[a][b] = n < N ? wk[(size_t)(c * 16 + (2 * a + p) * 4 + 2 * b + q) * Nld + n] : 0.f;
-                const float t[3][2] = {{gk[0][0], gk[0][1]}, {gk[0][0] + gk[1][0], gk[0][1] + gk[1][1]}, {gk[1][0], gk[1][1]}};
-#pragma unroll
-                for (int xi = 0; xi < 3; ++xi) {
-                    const float u[3] = {t[xi][0], t[xi][0] + t[xi][1], t[xi][1]};
-#pragma unroll
-                    for (int nu = 0; nu < 3; ++nu)
-                        U[((size_t)(((p * 2 + q) * 9 + xi * 3 + nu) * nch8 + (c >> 3)) * Nld + n) * 8 + (c & 7)] = u[nu];
-                }
+                wino_weights_f22(gk, U + ((size_t)((p * 2 + q) * 9 * nch8 + (c >> 3)) * Nld + n) * 8 + (c & 7), (size_t)nch8 * Nld * 8);
             }
     }
 }
@@ -1068,24 +789,25 @@ int pow2floor_log(int v) {
 namespace agan {
 namespace conv {
 
-// Plan of the Winograd kernel for gather geometry g (forward or data gradient of a conv3x3 stride 1 pad 1); p.ok == 0: not taken.
+// Plan of the Winograd gather for geometry g: the forward or data gradient of a conv3x3 stride 1 pad 1, the forward of a conv4x4 stride 2
+// pad 1, or the data gradient of one (a 2x2-tap gather per parity class); p.ok == 0: not taken.
 WinoPlan plan_wino(const Geom& g) {
     WinoPlan p;
     memset(&p, 0, sizeof(p));
-    if (g.SY == 1 && g.R == 3 && g.S == 3 && g.DY == 1 && g.OS == 1 && g.OY0 == -1 && g.IH == g.OH && g.IW == g.OW) p.s2 = 0;
-    else if (g.SY == 2 && g.R == 4 && g.S == 4 && g.DY == 1 && g.OS == 1 && g.OY0 == -1 && g.IH == 2 * g.OH && g.IW == 2 * g.OW) p.s2 = 1;
-    else if (g.SY == 1 && g.R == 2 && g.S == 2 && g.DY == -1 && g.OS == 2 && g.OY0 == 0 && g.OY1 == 1 && g.OH == 2 * g.IH && g.OW == 2 * g.IW) p.s2 = 2;
+    if (g.SY == 1 && g.R == 3 && g.S == 3 && g.DY == 1 && g.OS == 1 && g.OY0 == -1 && g.IH == g.OH && g.IW == g.OW)
+        p.kind = (g.Cout & 7) == 0 ? WinoKind::conv3x3_half : WinoKind::conv3x3;     // half: 32 tiles x 64 channels, two workgroups per CU
+    else if (g.SY == 2 && g.R == 4 && g.S == 4 && g.DY == 1 && g.OS == 1 && g.OY0 == -1 && g.IH == 2 * g.OH && g.IW == 2 * g.OW) p.kind = WinoKind::conv4x4_s2;
+    else if (g.SY == 1 && g.R == 2 && g.S == 2 && g.DY == -1 && g.OS == 2 && g.OY0 == 0 && g.OY1 == 1 && g.OH == 2 * g.IH && g.OW == 2 * g.IW) p.kind = WinoKind::dgrad2x2_class;
     else return p;
-    if ((g.OHs & 1) || (g.OWs & 1) || (g.Cin & 7) || g.Cout < 32) return p;
-    if (p.s2 == 1 && g.Cout < 96) return p;                   // (the stride-2 forward kernel is built for 128-channel tiles)
-    // (the class kernel walks 16 channels at a time; with 64 output channels -- 64-tile blocks, short K loops, 64 scalar stores per lane -- it
-    //  measured 15 % SLOWER than the direct kernel, with 128+ 15 % faster)
-    if (p.s2 == 2 && ((g.Cin & 15) || g.Cout < 96)) return p;
+    const WinoTraits T = wino_traits(p.kind);
+    const bool k3x3 = p.kind == WinoKind::conv3x3 || p.kind == WinoKind::conv3x3_half;
+    if ((g.OHs & 1) || (g.OWs & 1) || (g.Cin & (T.cch - 1)) || g.Cout < 32) return p;
+    // the stride-2 forward kernel is built for 128-channel tiles.  So is the class kernel: with 64 output channels -- 64-tile blocks, short K
+    // loops, 64 scalar stores per lane -- it measured 15 % SLOWER than the direct kernel, with 128+ 15 % faster
+    if (!k3x3 && g.Cout < 96) return p;
     const int tw = g.OWs / 2, th = g.OHs / 2;                 // tiles per row / column of the output lattice
     if (tw < 4) return p;                                     // (4x4 maps: two tiles per row -- the direct kernel's K split serves them better)
-    p.nf = g.Cout >= 96 ? 4 : 2;                             // cout fragments per workgroup; 4: 32 tiles, 2: 64 tiles
-    p.hmode = (p.s2 == 0 && (g.Cout & 7) == 0) ? 1 : 0;   // conv3x3: 32 tiles x 64 channels, two workgroups per CU (conv_wino_h_f32_kernel)
-    if (p.hmode) p.nf = 4;                                    // (tile geometry of the 32-tile blocks)
+    p.nf = (g.Cout >= 96 || p.kind == WinoKind::conv3x3_half) ? 4 : 2;      // tile geometry: 4: 32-tile blocks, 2: 64-tile blocks (of 64 output channels)
     const int lt = p.nf == 4 ? 5 : 6;
     p.txl = std::min(3, pow2floor_log(tw));
     p.tyl = std::min(lt - p.txl, pow2floor_log(th));
@@ -1094,78 +816,66 @@ WinoPlan plan_wino(const Geom& g) {
     p.blocks_y = cdiv(th, TY);
     p.blocks_b = cdiv(g.B, TB);
     p.mtiles = p.blocks_x * p.blocks_y * p.blocks_b;
-    p.ntiles = p.hmode ? cdiv(g.Cout, 64) : cdiv(g.Cout, p.nf * 32);
+    p.ntiles = p.kind == WinoKind::conv3x3_half ? cdiv(g.Cout, 64) : cdiv(g.Cout, p.nf * 32);
     // the 32 x 32 x 2 product needs thousands of tiles to pay for a workgroup's 256 accumulators: small layers stay on the direct kernel
     // (stride 2, measured: 384 workgroups = 1.5 rounds of the chip gain nothing, 768+ do: such layers split their input channels over two
     //  workgroups and sum the halves -- their outputs are small)
     p.ksplit = 1;
-    if (p.s2 == 1 && p.mtiles * p.ntiles < 512 && p.mtiles * p.ntiles >= 256 && g.Cin >= 128) p.ksplit = 2;
-    if (p.mtiles * p.ntiles * p.ksplit * (p.s2 == 2 ? 4 : 1) < (p.s2 ? 512 : 256)) return p;
+    if (p.kind == WinoKind::conv4x4_s2 && p.mtiles * p.ntiles < 512 && p.mtiles * p.ntiles >= 256 && g.Cin >= 128) p.ksplit = 2;
+    if (p.mtiles * p.ntiles * p.ksplit * T.classes < (k3x3 ? 256 : 512)) return p;
     p.chunks_per_split = cdiv(g.Cin / 8, p.ksplit);
     p.slab = ((size_t)g.B * g.Cout * g.OH * g.OW + 3) / 4 * 4;
-    const int PR = p.s2 == 2 ? 2 * TY + 1 : (p.s2 ? 4 : 2) * TY + 2, PC = p.s2 == 2 ? 2 * TX + 1 : (p.s2 ? 4 : 2) * TX + 2;
-    const int cch = p.s2 == 2 ? 16 : 8;                       // channels per chunk
+    const int PR = T.step * TY + T.extra, PC = T.step * TX + T.extra;
     p.pcp = (PC + 1) & ~1;
     p.mpc = (65536 + PC - 1) / PC;
     p.mpr = (65536 + PR - 1) / PR;
-    p.raw_items = TB * cch * PR * PC;
-    if (p.raw_items > (p.s2 == 2 ? (p.nf == 4 ? 11 : 19) : (p.s2 ? 21 : (p.nf == 4 ? 7 : 11))) * 256) return p;
-    p.raw_bytes = (TB * cch * PR * p.pcp * 4 + 15) & ~15;
-    const int planes = p.s2 == 2 ? 9 * 4 : (p.s2 ? 36 : 16);  // (class kernel: 9 positions x 4 classes of weights; its V holds 9 x 16 channels)
-    p.smem_bytes = 2 * p.raw_bytes + 2 * (p.s2 == 2 ? 9 * 2 : planes) * (1 << lt) * 8 * 4;      // two raw patches, two V buffers
-    if (p.smem_bytes > 160 * 1024) return p;
-    p.u_bytes = ((size_t)planes * (g.Cin / 8) * g.Nld * 8 * sizeof(float) + 255) / 256 * 256;
+    p.raw_items = TB * T.cch * PR * PC;
+    if (p.raw_items > (lt == 5 ? T.ni32 : T.ni64) * 256) return p;      // (the kernel's staging registers: WinoGather::NI)
+    p.raw_bytes = (TB * T.cch * PR * p.pcp * 4 + 15) & ~15;
+    p.smem_bytes = 2 * p.raw_bytes + 2 * T.vfrags * (1 << lt) * 8 * 4;      // two raw patches, two V buffers
+    if (p.smem_bytes > T.lds_cap) return p;
+    p.u_bytes = ((size_t)T.planes * (g.Cin / 8) * g.Nld * 8 * sizeof(float) + 255) / 256 * 256;
     p.ws_bytes = p.u_bytes + (p.ksplit > 1 ? p.slab * p.ksplit * sizeof(float) : 0);
     p.ok = 1;
     return p;
 }
 
+namespace {
+template <auto Kernel, WinoKind K>
+void launch_gather_kernel(dim3 grid, const float* in, const float* U, float* out, const Geom& g, const WinoPlan& p, hipStream_t st) {
+    static const hipError_t a = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, wino_traits(K).lds_cap);
+    (void)a;
+    AGAN_LAUNCH(Kernel, grid, dim3(256), (size_t)p.smem_bytes, st, in, U, out, g, p);
+}
+}  // namespace
+
 // wk: the mode's ordinary fp32 pack [K = (c, r, s)][Nld]; ws: >= p.u_bytes
 void launch_wino(const float* in, const float* wk, float* out, const Geom& g, const WinoPlan& p, void* ws, hipStream_t st) {
     float* U = static_cast<float*>(ws);
     const int total = g.Cin * g.Nld;
-    dim3 grid(p.mtiles * p.ntiles * p.ksplit);
-    if (p.s2 == 2) {
+    const dim3 grid(p.mtiles * p.ntiles * p.ksplit * wino_traits(p.kind).classes), tgrid(std::min(cdiv(total, 256), 2048));
+    switch (p.kind) {
+    case WinoKind::dgrad2x2_class:
         AGAN_LAUNCH(wino_cls_weight_transform_kernel, dim3(std::min(cdiv(4 * total, 256), 4096)), dim3(256), 0, st, wk, U, g.Cin, g.Nld, g.Cout);
-        dim3 gridc(p.mtiles * p.ntiles * 4);
-        if (p.nf == 4) {
-            static const hipError_t a4 = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wino_cls_f32_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)a4;
-            AGAN_LAUNCH(conv_wino_cls_f32_kernel<4>, gridc, dim3(256), (size_t)p.smem_bytes, st, in, U, out, g, p);
-        } else {
-            static const hipError_t a2 = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wino_cls_f32_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)a2;
-            AGAN_LAUNCH(conv_wino_cls_f32_kernel<2>, gridc, dim3(256), (size_t)p.smem_bytes, st, in, U, out, g, p);
-        }
-        return;
-    }
-    if (p.s2) {
-        AGAN_LAUNCH(wino_s2_weight_transform_kernel, dim3(std::min(cdiv(total, 256), 2048)), dim3(256), 0, st, wk, U, g.Cin, g.Nld, g.Cout);
-        static const hipError_t a4 = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wino_s2_f32_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)a4;
+        launch_gather_kernel<conv_wino_cls_f32_kernel<4>, WinoKind::dgrad2x2_class>(grid, in, U, out, g, p, st);
+        break;
+    case WinoKind::conv4x4_s2:
+        AGAN_LAUNCH(wino_s2_weight_transform_kernel, tgrid, dim3(256), 0, st, wk, U, g.Cin, g.Nld, g.Cout);
         // (a split launch writes its partial sums to the slabs behind U in the workspace: the caller sums them into `out`)
-        float* dst = p.ksplit > 1 ? reinterpret_cast<float*>(static_cast<char*>(ws) + p.u_bytes) : out;
-        AGAN_LAUNCH(conv_wino_s2_f32_kernel<4>, grid, dim3(256), (size_t)p.smem_bytes, st, in, U, dst, g, p);
-        return;
-    }
-    AGAN_LAUNCH(wino_weight_transform_kernel, dim3(std::min(cdiv(total, 256), 2048)), dim3(256), 0, st, wk, U, g.Cin, g.Nld, g.Cout);
-    if (p.hmode) {
-        static const hipError_t ah = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wino_h_f32_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-        (void)ah;
-        AGAN_LAUNCH(conv_wino_h_f32_kernel, grid, dim3(256), (size_t)p.smem_bytes, st, in, U, out, g, p);
-        return;
-    }
-    if (p.nf == 4) {
-        static const hipError_t a4 = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wino_f32_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)a4;
-        AGAN_LAUNCH(conv_wino_f32_kernel<4>, grid, dim3(256), (size_t)p.smem_bytes, st, in, U, out, g, p);
-    } else {
-        static const hipError_t a2 = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wino_f32_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)a2;
-        AGAN_LAUNCH(conv_wino_f32_kernel<2>, grid, dim3(256), (size_t)p.smem_bytes, st, in, U, out, g, p);
+        launch_gather_kernel<conv_wino_s2_f32_kernel<4>, WinoKind::conv4x4_s2>(
+            grid, in, U, p.ksplit > 1 ? reinterpret_cast<float*>(static_cast<char*>(ws) + p.u_bytes) : out, g, p, st);
+        break;
+    case WinoKind::conv3x3_half:
+        AGAN_LAUNCH(wino_weight_transform_kernel, tgrid, dim3(256), 0, st, wk, U, g.Cin, g.Nld, g.Cout);
+        launch_gather_kernel<conv_wino_h_f32_kernel, WinoKind::conv3x3_half>(grid, in, U, out, g, p, st);
+        break;
+    case WinoKind::conv3x3:
+        AGAN_LAUNCH(wino_weight_transform_kernel, tgrid, dim3(256), 0, st, wk, U, g.Cin, g.Nld, g.Cout);
+        if (p.nf == 4) launch_gather_kernel<conv_wino_f32_kernel<4>, WinoKind::conv3x3>(grid, in, U, out, g, p, st);
+        else launch_gather_kernel<conv_wino_f32_kernel<2>, WinoKind::conv3x3>(grid, in, U, out, g, p, st);
+        break;
     }
 }
-
 
 // Winograd weight gradient of a conv3x3 stride 1 pad 1 (forward geometry g); p.ok == 0: not taken.
 WinoWgradPlan plan_wino_wgrad(const Geom& g) {

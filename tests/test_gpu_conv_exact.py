@@ -69,6 +69,8 @@ CASES = [
     ("same", 8, 16, 64, 64, 128, ""),       # f32: conv_wino_h / gather32 / rows (fp32 operands); 16: p16 / p16 / rows
     ("same", 8, 16, 64, 64, 100, ""),       # f32: conv_wino_f32 (Cout % 8 != 0) / gather32 / rows; 16: p16, partial cout tile / patch / rows
     ("same", 2, 40, 128, 128, 72, ""),      # f32: conv_wino_h / conv_wino_h / conv_wino_wgrad; 16: p16, last stage 8 of 32 channels / p16 / rows
+    ("same", 4, 8, 128, 128, 36, ""),       # f32: conv_wino_f32 <2> (Cout < 96, Cout % 8 != 0: 64 tiles x 64 channels, 256 blocks -- the smallest that
+                                            #   the plan takes) / gather32 / rows
     ("down", 16, 16, 128, 128, 128, ""),    # f32: conv_wino_s2 / gather32 / conv_wgrad_f32; 16: p16 gk2 / p16 gk1 / rows gk2
     ("down", 16, 128, 64, 64, 32, ""),      # f32: gather32 / conv_wino_cls / conv_wgrad_f32; 16: p16 gk2 / p16 gk1, both column classes / rows
     # ---- <= 4 output channels: vector-ALU kernels, fp32 arithmetic in every mode ---------------------------------------------------------------
@@ -362,7 +364,8 @@ def test_conv_is_bit_exact_on_grid_operands(sweep, mode, case):
 # <ET, NPL, GK, CI2, X16, Y16, NIX, NIY, PC, UPS>.
 GATHER_TILES = [("conv_gather_f32_kernel", {1: bn}, split) for bn in ("128", "64", "32") for split in (1, "split")]
 F32_KERNELS = GATHER_TILES + [
-    ("conv_wino_h_f32_kernel", {}, None), ("conv_wino_f32_kernel", {}, None), ("conv_wino_s2_f32_kernel", {}, None),
+    ("conv_wino_h_f32_kernel", {}, None), ("conv_wino_f32_kernel", {0: "4"}, None), ("conv_wino_f32_kernel", {0: "2"}, None),
+    ("conv_wino_s2_f32_kernel", {}, None),
     ("conv_wino_cls_f32_kernel", {}, None), ("conv_wino_wgrad_f32_kernel", {}, None), ("conv_wgrad_f32_kernel", {}, None),
     ("conv_wgrad_rows_kernel", {}, None),
 ]
