@@ -1689,3 +1689,98 @@ def image_prep(planes, rows: Optional[Tensor], flip: Optional[Tensor], out=None)
         outs.append(o)
     L.call("agan_image_prep", arr, len(planes), _p(rows), _p(flip), B, C, n_src, _stream())
     return outs
+
+
+# --------------------------------------------------------------------------------------------------------------
+# k-means (data/captions.py: kmeans; include/agan.h: agan_kmeans_*)
+# --------------------------------------------------------------------------------------------------------------
+# One Lloyd iteration is kmeans_assign + kmeans_update.  Device tensors run on the library; a CPU tensor takes the torch restatement
+# below, which applies the same rules in float64 (lowest index on a tie, max(0, .) on the distance, out-of-range labels ignored, an
+# empty cluster keeps its centroid) and rounds the centroids once to fp32 -- the host-side path of data/captions.py and its tests.
+# Neither has autograd: clustering is data preparation.
+def _kmeans_call(name: str, *args) -> None:
+    """lib.call, with AGAN_EINVAL (a shape outside the documented domain) raised as ValueError"""
+    lib = L.load()
+    code = getattr(lib, name)(*args)
+    if code == L.EINVAL:
+        msg = lib.agan_last_error()
+        raise ValueError(f"{name}: {msg.decode() if msg else 'bad argument'}")
+    L.check(code, name)
+
+
+def _kmeans_operands(x: Tensor, centroids: Tensor, what: str) -> Tuple[Tensor, Tensor]:
+    if x.dim() != 2 or centroids.dim() != 2 or x.shape[1] != centroids.shape[1]:
+        raise ValueError(f"{what}: expected x [N, D] and centroids [K, D], got {tuple(x.shape)} and {tuple(centroids.shape)}")
+    if centroids.device != x.device:
+        raise ValueError(f"{what}: x is on {x.device}, centroids on {centroids.device}")
+    for t, n in ((x, "x"), (centroids, "centroids")):
+        if t.dtype != torch.float32:
+            raise ValueError(f"{what}: {n} must be float32, got {t.dtype}")
+    return x.contiguous(), centroids.contiguous()
+
+
+def _kmeans_labels(labels: Tensor, x: Tensor, what: str) -> Tensor:
+    if labels.dtype != torch.int32 or labels.shape != (x.shape[0],) or labels.device != x.device:
+        raise ValueError(f"{what}: labels must be int32 [{x.shape[0]}] on {x.device}, got {labels.dtype} {tuple(labels.shape)} on {labels.device}")
+    return labels.contiguous()
+
+
+_KMEANS_CPU_ROWS = 1 << 14          # rows per float64 score block of the CPU path
+
+
+def kmeans_assign(x: Tensor, centroids: Tensor, labels: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """-> (labels int32 [N], dist float32 [N], n_changed int32 [1], inertia float64 [1]), all on x's device.
+
+    labels[i] = argmin_c (|c|^2 - 2 x_i.c), the lowest c on a tie; dist[i] = max(0, |x_i|^2 + that score); n_changed = rows whose
+    label differs from `labels` (None: every row counts as changed); inertia = sum of dist in float64.  `labels` is not modified."""
+    x, centroids = _kmeans_operands(x, centroids, "kmeans_assign")
+    N, D = x.shape
+    K = centroids.shape[0]
+    prev = torch.full((N,), -1, dtype=torch.int32, device=x.device) if labels is None else _kmeans_labels(labels, x, "kmeans_assign")
+    if not x.is_cuda:
+        if N < 1 or not 1 <= D <= 4096 or not 1 <= K <= 4096 or N * D >= 1 << 31:
+            raise ValueError(f"kmeans_assign: N {N}, D {D}, K {K} outside N >= 1, 1 <= D, K <= 4096, N * D < 2^31")
+        c64 = centroids.double()
+        cn = (c64 * c64).sum(1)
+        new = torch.empty(N, dtype=torch.int32)
+        dist = torch.empty(N, dtype=torch.float32)
+        for s in range(0, N, _KMEANS_CPU_ROWS):
+            x64 = x[s:s + _KMEANS_CPU_ROWS].double()
+            score = cn.view(1, K) - 2.0 * (x64 @ c64.t())
+            best = torch.from_numpy(score.numpy().argmin(axis=1))           # numpy: the first minimum
+            d = ((x64 * x64).sum(1) + score.gather(1, best.view(-1, 1)).view(-1)).clamp_(min=0.0)
+            new[s:s + _KMEANS_CPU_ROWS] = best.to(torch.int32)
+            dist[s:s + _KMEANS_CPU_ROWS] = d.to(torch.float32)
+        return new, dist, (new != prev).sum().to(torch.int32).view(1), dist.double().sum().view(1)
+    new = prev.clone() if labels is not None else prev
+    dist = torch.empty(N, dtype=torch.float32, device=x.device)
+    n_changed = torch.empty(1, dtype=torch.int32, device=x.device)
+    inertia = torch.empty(1, dtype=torch.float64, device=x.device)
+    nbytes = L.load().agan_kmeans_assign_ws_bytes(N, D, K)
+    ws, wsp = _ws(nbytes, x)
+    _kmeans_call("agan_kmeans_assign", _p(x), _p(centroids), _p(new), _p(dist), _p(n_changed), _p(inertia), N, D, K, wsp, nbytes, _stream())
+    return new, dist, n_changed, inertia
+
+
+def kmeans_update(x: Tensor, labels: Tensor, centroids: Tensor) -> Tuple[Tensor, Tensor]:
+    """-> (centroids float32 [K, D], counts int32 [K]): counts[c] = rows with label c, centroids[c] = fp32(float64 mean of those rows);
+    a cluster without rows keeps the centroid passed in; a label outside [0, K) is ignored.  `centroids` is not modified."""
+    x, centroids = _kmeans_operands(x, centroids, "kmeans_update")
+    labels = _kmeans_labels(labels, x, "kmeans_update")
+    N, D = x.shape
+    K = centroids.shape[0]
+    if not x.is_cuda:
+        if N < 1 or not 1 <= D <= 4096 or not 1 <= K <= 4096 or N * D >= 1 << 31:
+            raise ValueError(f"kmeans_update: N {N}, D {D}, K {K} outside N >= 1, 1 <= D, K <= 4096, N * D < 2^31")
+        lab = labels.long()
+        ok = (lab >= 0) & (lab < K)
+        counts = torch.bincount(lab[ok], minlength=K)
+        sums = torch.zeros(K, D, dtype=torch.float64).index_add_(0, lab[ok], x[ok].double())
+        mean = (sums / counts.clamp(min=1).view(K, 1).double()).to(torch.float32)
+        return torch.where((counts > 0).view(K, 1), mean, centroids), counts.to(torch.int32)
+    new = centroids.clone()
+    counts = torch.empty(K, dtype=torch.int32, device=x.device)
+    nbytes = L.load().agan_kmeans_update_ws_bytes(N, D, K)
+    ws, wsp = _ws(nbytes, x)
+    _kmeans_call("agan_kmeans_update", _p(x), _p(labels), _p(new), _p(counts), N, D, K, wsp, nbytes, _stream())
+    return new, counts

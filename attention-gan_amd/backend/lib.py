@@ -20,6 +20,7 @@ ACT_NONE, ACT_GLU, ACT_LRELU, ACT_TANH, ACT_SIGMOID, ACT_RELU = 0, 1, 2, 3, 4, 5
 COMM_ID_BYTES = 128    # include/agan.h: AGAN_COMM_ID_BYTES
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2          # include/agan.h: AGAN_DT_* (storage type of an activation tensor)
 AMAX_SLOT = 256        # floats per amax slot (include/agan.h: AGAN_AMAX_SLOT)
+EINVAL, EWORKSPACE = -1, -2                # include/agan.h: AGAN_EINVAL, AGAN_EWORKSPACE
 ABI_VERSION = 101      # include/agan.h: AGAN_VERSION this binding was written against (argument lists changed between versions)
 
 
@@ -149,6 +150,10 @@ _SIGNATURES = {
     "agan_lstm_bwd": (c_int, [_P] * 9 + [c_int] * 4 + [_P]),
     "agan_lstm_wgrad": (c_int, [_P] * 5 + [c_int] * 4 + [_P]),
     "agan_image_prep": (c_int, [POINTER(ImagePlane), c_int, _P, _P, c_int, c_int, c_int, _P]),
+    "agan_kmeans_assign_ws_bytes": (c_size_t, [c_int] * 3),
+    "agan_kmeans_assign": (c_int, [_P] * 6 + [c_int] * 3 + [_P, c_size_t, _P]),
+    "agan_kmeans_update_ws_bytes": (c_size_t, [c_int] * 3),
+    "agan_kmeans_update": (c_int, [_P] * 4 + [c_int] * 3 + [_P, c_size_t, _P]),
     "agan_adam_step": (c_int, [_P, _P, _P, _P, c_size_t, _P, c_double, c_double, c_double, c_double, c_float, _P]),
 }
 

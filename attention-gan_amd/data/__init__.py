@@ -1,2 +1,2 @@
-__all__ = ["batches"]
-from . import batches  # noqa: F401,E402
+__all__ = ["batches", "captions"]
+from . import batches, captions  # noqa: F401,E402

@@ -1,9 +1,9 @@
 """Batch wire format of the training loop (reference data/bedrooms.py:209-238).
 
 The reference's DataLoader yields the tuple  (words [B,T] int64, lengths [B] int64, class_ids [B] int64,
-img64, img128, img256 float32 in [-1,1])  -- train.py:111.  Everything upstream of that tuple (image folders, UMAP /
-agglomerative pseudo-captions, vocabulary building) is host-side data preparation outside the hot path; what is kept here
-is the tuple itself, produced either synthetically (benchmarks, tests) or from pre-resized uint8 shards on disk.
+img64, img128, img256 float32 in [-1,1])  -- train.py:111.  This module is the tuple itself, produced either synthetically (benchmarks,
+tests) or from pre-resized uint8 shards on disk.  What lies upstream of it -- image folders, k-means pseudo-captions and class ids,
+vocabulary building -- is data/captions.py, whose Dataset.write_shards writes the shards read here.
 
 Shard format (.npz, data only): `words` int64 [N,T] (0-padded), `lengths` int64 [N], `class_ids` int64 [N],
 `img64` / `img128` / `img256` uint8 [N,3,R,R].  Pixels are mapped with (x - 127.5) / 127.5 like the reference's

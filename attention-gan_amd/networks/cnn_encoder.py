@@ -255,15 +255,29 @@ class CNNEncoder(nn.Module):
         features = AF.conv2d(x6e, self.emb_features.weight, None, "same", cache[0])
         return features, AF.linear(pooled, self.emb_cnn_code.weight, self.emb_cnn_code.bias, cache[1])
 
-    def _forward_torch(self, x: Tensor) -> Tuple[Tensor, Tensor]:
+    def _trunk_torch(self, x: Tensor) -> Tuple[Tensor, Tensor]:
+        """-> (Mixed_6e output [B, 768, 17, 17], pooled Mixed_7c [B, 2048]) on stock ops"""
         x = F.interpolate(x, size=(299, 299), mode="bilinear", align_corners=False)      # :75
         x = self.Conv2d_2b_3x3(self.Conv2d_2a_3x3(self.Conv2d_1a_3x3(x)))
         x = F.max_pool2d(x, 3, 2)
         x = self.Conv2d_4a_3x3(self.Conv2d_3b_1x1(x))
         x = F.max_pool2d(x, 3, 2)
         x = self.Mixed_5d(self.Mixed_5c(self.Mixed_5b(x)))
-        x = self.Mixed_6e(self.Mixed_6d(self.Mixed_6c(self.Mixed_6b(self.Mixed_6a(x)))))
-        features = self.emb_features(x)                                                   # [B, out_dim, 17, 17]
-        x = self.Mixed_7c(self.Mixed_7b(self.Mixed_7a(x)))
-        x = F.avg_pool2d(x, 8).flatten(1)                                                 # [B, 2048]
-        return features, self.emb_cnn_code(x)
+        x6e = self.Mixed_6e(self.Mixed_6d(self.Mixed_6c(self.Mixed_6b(self.Mixed_6a(x)))))
+        x = self.Mixed_7c(self.Mixed_7b(self.Mixed_7a(x6e)))
+        return x6e, F.avg_pool2d(x, 8).flatten(1)                                         # [B, 2048]
+
+    def _forward_torch(self, x: Tensor) -> Tuple[Tensor, Tensor]:
+        x6e, pooled = self._trunk_torch(x)
+        return self.emb_features(x6e), self.emb_cnn_code(pooled)                          # [B, out_dim, 17, 17], [B, out_dim]
+
+    def pooled(self, x: Tensor) -> Tensor:
+        """The trunk's global code BEFORE the `emb_cnn_code` head: the average of Mixed_7c, [B, 2048] -- what an image embedder wants from
+        a trunk whose heads are untrained (networks/cnn_embedder.py).  Eval mode only: batch statistics would make an image's vector
+        depend on the batch it is embedded in."""
+        if self.training:
+            raise RuntimeError("CNNEncoder.pooled is an eval-mode call: call .eval() first")
+        if self._backend == "hip":
+            from ..backend import functional as AF
+            return AF.inception_trunk(x, self)[1]
+        return self._trunk_torch(x)[1]

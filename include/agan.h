@@ -36,7 +36,7 @@ extern "C" {
  * the embedding gather and the LSTM recurrence of the caption encoder (agan_embedding_*, agan_lstm_*); the train-mode BatchNorm of the
  * trunk on channel slices (agan_bn_relu_slice_fwd, agan_bn_slice_bwd); the trainable general 2-D conv behind Layers.conv
  * (agan_conv2d_train_*: forward, data gradient and weight gradient of any small geometry); the batch preparation from device-resident
- * uint8 shards (agan_image_prep). */
+ * uint8 shards (agan_image_prep); the two halves of a Lloyd iteration behind the pseudo-caption clustering (agan_kmeans_*). */
 
 enum {
     AGAN_OK = 0,
@@ -569,6 +569,32 @@ typedef struct agan_image_plane { const uint8_t* src; float* dst; int32_t H, W; 
 int agan_image_prep(const agan_image_plane* planes /* host array */, int n_planes /* 1..3 */,
                     const int32_t* rows /* device [B], NULL = 0..B-1 */, const uint8_t* flip /* device [B], NULL = none */,
                     int B, int C, int n_src, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * k-means for the pseudo-captions (csrc/kmeans.hip; data/captions.py: kmeans, HierarchicalClusterer -- the reference clusters image
+ * embeddings with scikit-learn's KMeans, data/bedrooms.py:279-289).  One Lloyd iteration is agan_kmeans_assign + agan_kmeans_update on
+ * x [N, D] fp32 row-major and centroids [K, D] fp32.  Domain: N >= 1, 1 <= D <= 4096, 1 <= K <= 4096, N * D < 2^31; tails in N, D and K
+ * are handled inside the kernels (a D tail reads as zeros).  Anything else, or a missing pointer, is AGAN_EINVAL with a message before any
+ * launch (the *_ws_bytes queries then return 0); a workspace that is too small is AGAN_EWORKSPACE.
+ *   agan_kmeans_assign: labels[i] = argmin_c (|c|^2 - 2 x_i.c), the LOWEST c on a tie; dist[i] = max(0, |x_i|^2 + that score).  The
+ *     contraction runs on v_mfma_f32_32x32x2_f32 (exact fp32 products, AGAN_PREC_F32's meaning; there is no 16-bit mode) and the running
+ *     (min, argmin) stays in registers across the centroid chunks: no N x K matrix exists in memory.  labels is read before it is
+ *     written: *n_changed = the number of rows whose new label differs from the value that was there (any value on a first call).
+ *     *inertia = the sum of dist in fp64.  Whatever x and the centroids hold (NaN included), every label written lies in [0, K).
+ *   agan_kmeans_update: counts[c] = rows with label c; centroids[c] = fp32(fp64 sum of those rows / counts[c]); a cluster without rows
+ *     keeps the centroid passed in, bit for bit.  A label outside [0, K) contributes to nothing and is never used as an index.  The rows
+ *     are ordered by a stable counting sort on the labels and summed, per cluster, in ascending row order in pieces of 512 rows whose
+ *     partial sums are added in piece order: no N x K one-hot matrix.
+ * No float atomics anywhere (integer LDS atomics only for the histogram, whose result does not depend on their order); every sum has one
+ * fixed order: two runs on the same inputs give the same bits.  Only enqueues on `stream`: no allocation, no synchronisation.
+ * ---------------------------------------------------------------------------------------------- */
+size_t agan_kmeans_assign_ws_bytes(int N, int D, int K);
+int agan_kmeans_assign(const float* x /* [N, D] */, const float* centroids /* [K, D] */, int32_t* labels /* [N] in: previous, out: new */,
+                       float* dist /* [N] */, int32_t* n_changed /* [1] */, double* inertia /* [1] */, int N, int D, int K, void* ws,
+                       size_t ws_bytes, void* stream);
+size_t agan_kmeans_update_ws_bytes(int N, int D, int K);
+int agan_kmeans_update(const float* x /* [N, D] */, const int32_t* labels /* [N] */, float* centroids /* [K, D] in: previous, out: new */,
+                       int32_t* counts /* [K] */, int N, int D, int K, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }
