@@ -1784,3 +1784,110 @@ def kmeans_update(x: Tensor, labels: Tensor, centroids: Tensor) -> Tuple[Tensor,
     ws, wsp = _ws(nbytes, x)
     _kmeans_call("agan_kmeans_update", _p(x), _p(labels), _p(new), _p(counts), N, D, K, wsp, nbytes, _stream())
     return new, counts
+
+
+# --------------------------------------------------------------------------------------------------------------
+# evaluation reductions (evaluation.py: FeatureMoments, r_precision; include/agan.h: agan_moments_*, agan_retrieval_rank)
+# --------------------------------------------------------------------------------------------------------------
+# Device tensors run on the library; a CPU tensor takes the float64 torch restatement below with the same rules (upper-triangle state,
+# count == 1 -> zero covariance, the clamp of the cosine's denominator, a tie counts against the match, a bad candidate is refused).
+# None has autograd: these are measurements.
+def _moments_state(sum: Tensor, gram: Tensor, D: int, device, what: str) -> None:
+    for t, n, shape in ((sum, "sum", (D,)), (gram, "gram", (D, D))):
+        if t.dtype != torch.float64 or tuple(t.shape) != shape or t.device != device or not t.is_contiguous():
+            raise ValueError(f"{what}: {n} must be a contiguous float64 {shape} tensor on {device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+
+
+def moments_update(x: Tensor, sum: Tensor, gram: Tensor) -> Tuple[Tensor, Tensor]:
+    """Adds the rows of x [n, D] float32 to the raw moments IN PLACE and returns them: sum [D] += column sums, gram [D, D] += x^T x on
+    and above the diagonal (what lies below the diagonal is unspecified), both float64.  A fresh state is zeros."""
+    if x.dim() != 2:
+        raise ValueError(f"moments_update: expected x [n, D], got {tuple(x.shape)}")
+    if x.dtype != torch.float32:
+        raise ValueError(f"moments_update: x must be float32, got {x.dtype}")
+    x = x.contiguous()
+    n, D = x.shape
+    _moments_state(sum, gram, D, x.device, "moments_update")
+    if not x.is_cuda:
+        if n < 1 or not 1 <= D <= 4096 or n * D >= 1 << 31:
+            raise ValueError(f"moments_update: n {n}, D {D} outside n >= 1, 1 <= D <= 4096, n * D < 2^31")
+        x64 = x.double()
+        sum += x64.sum(0)
+        gram += torch.triu(x64.t() @ x64)
+        return sum, gram
+    nbytes = L.load().agan_moments_update_ws_bytes(n, D)
+    ws, wsp = _ws(nbytes, x)
+    _kmeans_call("agan_moments_update", _p(x), n, D, _p(sum), _p(gram), wsp, nbytes, _stream())
+    return sum, gram
+
+
+def moments_finish(sum: Tensor, gram: Tensor, count: int) -> Tuple[Tensor, Tensor]:
+    """-> (mean [D], cov [D, D]) float64: mean = sum / count, cov = (gram - count mean mean^T) / (count - 1) from the upper triangle of
+    gram, mirrored to a matrix that is symmetric bit for bit; count == 1 gives a zero covariance."""
+    if sum.dim() != 1:
+        raise ValueError(f"moments_finish: expected sum [D], got {tuple(sum.shape)}")
+    D, count = sum.shape[0], int(count)
+    _moments_state(sum, gram, D, sum.device, "moments_finish")
+    if not sum.is_cuda:
+        if not 1 <= D <= 4096 or not 1 <= count < 1 << 53:
+            raise ValueError(f"moments_finish: D {D}, count {count} outside 1 <= D <= 4096, 1 <= count < 2^53")
+        mean = sum / count
+        if count == 1:
+            return mean, torch.zeros(D, D, dtype=torch.float64)
+        upper = torch.triu(gram)
+        full = upper + torch.triu(gram, 1).t()
+        return mean, (full - count * torch.outer(mean, mean)) / (count - 1)
+    mean = torch.empty(D, dtype=torch.float64, device=sum.device)
+    cov = torch.empty(D, D, dtype=torch.float64, device=sum.device)
+    _kmeans_call("agan_moments_finish", _p(sum), _p(gram), count, D, _p(mean), _p(cov), _stream())
+    return mean, cov
+
+
+_RETRIEVAL_CPU_ROWS = 1 << 10       # queries per float64 block of the CPU path
+
+
+def retrieval_rank(query: Tensor, bank: Tensor, cand: Tensor, want_scores: bool = False):
+    """-> rank int32 [N] (with want_scores: (rank, scores float32 [N, R])), on query's device.
+
+    scores[i][j] = q_i . b_c / max(|q_i| |b_c|, 1e-8) with c = cand[i][j]; column 0 of cand is the match and
+    rank[i] = #{ j >= 1 : scores[i][j] >= scores[i][0] }, so a tie counts against the match and rank 0 is a hit.  A candidate outside
+    [0, M) raises ValueError: on the device it is refused by the kernel before it is used as an address and reported as a negative
+    rank, which this wrapper reads back -- the one synchronisation of the call."""
+    if query.dim() != 2 or bank.dim() != 2 or query.shape[1] != bank.shape[1]:
+        raise ValueError(f"retrieval_rank: expected query [N, D] and bank [M, D], got {tuple(query.shape)} and {tuple(bank.shape)}")
+    if bank.device != query.device or cand.device != query.device:
+        raise ValueError(f"retrieval_rank: query is on {query.device}, bank on {bank.device}, cand on {cand.device}")
+    for t, n in ((query, "query"), (bank, "bank")):
+        if t.dtype != torch.float32:
+            raise ValueError(f"retrieval_rank: {n} must be float32, got {t.dtype}")
+    N, D = query.shape
+    M = bank.shape[0]
+    if cand.dtype != torch.int32 or cand.dim() != 2 or cand.shape[0] != N:
+        raise ValueError(f"retrieval_rank: cand must be int32 [{N}, R], got {cand.dtype} {tuple(cand.shape)}")
+    R = cand.shape[1]
+    query, bank, cand = query.contiguous(), bank.contiguous(), cand.contiguous()
+    if not query.is_cuda:
+        if N < 1 or M < 1 or not 1 <= D <= 4096 or not 1 <= R <= 1024:
+            raise ValueError(f"retrieval_rank: N {N}, M {M}, D {D}, R {R} outside N, M >= 1, 1 <= D <= 4096, 1 <= R <= 1024")
+        idx = cand.long()
+        if bool(((idx < 0) | (idx >= M)).any()):
+            raise ValueError(f"retrieval_rank: a candidate index lies outside [0, {M})")
+        b64 = bank.double()
+        bn = (b64 * b64).sum(1).sqrt()
+        rank = torch.empty(N, dtype=torch.int32)
+        scores = torch.empty(N, R, dtype=torch.float32) if want_scores else None
+        for s in range(0, N, _RETRIEVAL_CPU_ROWS):
+            q = query[s:s + _RETRIEVAL_CPU_ROWS].double()
+            c = idx[s:s + _RETRIEVAL_CPU_ROWS]
+            dot = (q.unsqueeze(1) * b64[c]).sum(-1)
+            sc = dot / ((q * q).sum(1).sqrt().view(-1, 1) * bn[c]).clamp_(min=1e-8)
+            rank[s:s + _RETRIEVAL_CPU_ROWS] = (sc[:, 1:] >= sc[:, :1]).sum(1).to(torch.int32)
+            if want_scores:
+                scores[s:s + _RETRIEVAL_CPU_ROWS] = sc.to(torch.float32)
+        return (rank, scores) if want_scores else rank
+    rank = torch.empty(N, dtype=torch.int32, device=query.device)
+    scores = torch.empty(N, R, dtype=torch.float32, device=query.device) if want_scores else None
+    _kmeans_call("agan_retrieval_rank", _p(query), _p(bank), _p(cand), N, M, D, R, _p(scores), _p(rank), _stream())
+    if bool((rank < 0).any()):
+        raise ValueError(f"retrieval_rank: a candidate index lies outside [0, {M})")
+    return (rank, scores) if want_scores else rank

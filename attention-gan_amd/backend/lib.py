@@ -154,6 +154,10 @@ _SIGNATURES = {
     "agan_kmeans_assign": (c_int, [_P] * 6 + [c_int] * 3 + [_P, c_size_t, _P]),
     "agan_kmeans_update_ws_bytes": (c_size_t, [c_int] * 3),
     "agan_kmeans_update": (c_int, [_P] * 4 + [c_int] * 3 + [_P, c_size_t, _P]),
+    "agan_moments_update_ws_bytes": (c_size_t, [c_int] * 2),
+    "agan_moments_update": (c_int, [_P, c_int, c_int, _P, _P, _P, c_size_t, _P]),
+    "agan_moments_finish": (c_int, [_P, _P, c_int64, c_int, _P, _P, _P]),
+    "agan_retrieval_rank": (c_int, [_P, _P, _P] + [c_int] * 4 + [_P, _P, _P]),
     "agan_adam_step": (c_int, [_P, _P, _P, _P, c_size_t, _P, c_double, c_double, c_double, c_double, c_float, _P]),
 }
 

@@ -281,3 +281,17 @@ class CNNEncoder(nn.Module):
             from ..backend import functional as AF
             return AF.inception_trunk(x, self)[1]
         return self._trunk_torch(x)[1]
+
+    def code_and_pooled(self, x: Tensor) -> Tuple[Tensor, Tensor]:
+        """-> (cnn_code [B, out_dim], pooled [B, 2048]) from ONE trunk pass: the global code that the DAMSM sentence loss matches
+        against captions and the average of Mixed_7c before the head -- what an evaluation needs of an image (evaluation.Evaluator:
+        R-precision and feature moments).  Eval mode only, as `pooled`."""
+        if self.training:
+            raise RuntimeError("CNNEncoder.code_and_pooled is an eval-mode call: call .eval() first")
+        if self._backend == "hip":
+            from ..backend import functional as AF
+            pooled = AF.inception_trunk(x, self)[1]
+            cache = self.__dict__.setdefault("_agan_head_cache", ({}, {}))
+            return AF.linear(pooled, self.emb_cnn_code.weight, self.emb_cnn_code.bias, cache[1]), pooled
+        pooled = self._trunk_torch(x)[1]
+        return self.emb_cnn_code(pooled), pooled

@@ -486,18 +486,15 @@ class GanTrainStep(ModelTrainer):
         train_mode_bn=True: the EPOCH-END sample exactly as train.py:154-158 takes it -- under no_grad but WITHOUT .eval(): every
         BatchNorm normalises with the statistics of this batch and pushes them into its running statistics (one more update per
         epoch, which the next checkpoint carries), `noise` is the fixed input of train.py:105."""
-        was_training = self.G.training
-        self.G.train(bool(train_mode_bn))
-        try:
-            b = word_embs.shape[0]
-            if noise is None:
-                noise = torch.randn(b, self.G.z_dim, dtype=torch.float32, device=word_embs.device, generator=self.sample_rng)
-            if eps is None:
-                eps = torch.randn(b, self.G.cond_dim, dtype=torch.float32, device=word_embs.device, generator=self.sample_rng)
-            fakes, _, _, _ = self.G(noise, sent_embs, word_embs, self._make_mask(lengths, word_embs.shape[2]), eps)
-            return self._denormalise_multiple(fakes)
-        finally:
-            self.G.train(was_training)
+        mask = self._make_mask(lengths, word_embs.shape[2])
+        return self._denormalise_multiple(sample_fakes(self.G, word_embs, sent_embs, mask, self.sample_rng, noise, eps, train_mode_bn))
+
+    def evaluate(self, batches, text_encoder: Callable, real, n_samples: int, **kwargs) -> Dict:
+        """R-precision and Frechet distance of this step's generator under its own image encoder (evaluation.Evaluator.evaluate:
+        `real` is a FeatureMoments of real images, e.g. from Evaluator.real_moments; kwargs: R, seed, batch_size, folds)."""
+        from ..evaluation import Evaluator
+        dev = next(self.G.parameters()).device
+        return Evaluator(self.G, text_encoder, self.image_encoder, dev).evaluate(batches, real, n_samples, **kwargs)
 
     # -- the loop around the step (train.py:107-158) -------------------------------------------------------------------
     def skip_batch(self, lengths, batch_rows: int, batch_size: int) -> bool:
@@ -528,6 +525,26 @@ class GanTrainStep(ModelTrainer):
             self.step(word_embs.contiguous(), sent_embs.contiguous(), lengths, cids, [img64.to(dev), img128.to(dev), img256.to(dev)])
             steps += 1
         return steps
+
+
+@torch.no_grad()
+def sample_fakes(G: Module, word_embs: Tensor, sent_embs: Tensor, mask: Tensor, rng: torch.Generator, noise: Optional[Tensor] = None,
+                 eps: Optional[Tensor] = None, train_mode_bn: bool = False) -> List[Tensor]:
+    """The one sampling path (GanTrainStep.generate_images, evaluation.Evaluator): the generator's images in [-1, 1], one per stage,
+    under no_grad, in eval mode unless train_mode_bn; noise and eps that are not given are drawn from `rng`, noise first.  The
+    generator's mode is restored."""
+    was_training = G.training
+    G.train(bool(train_mode_bn))
+    try:
+        b = word_embs.shape[0]
+        if noise is None:
+            noise = torch.randn(b, G.z_dim, dtype=torch.float32, device=word_embs.device, generator=rng)
+        if eps is None:
+            eps = torch.randn(b, G.cond_dim, dtype=torch.float32, device=word_embs.device, generator=rng)
+        fakes, _, _, _ = G(noise, sent_embs, word_embs, mask, eps)
+        return fakes
+    finally:
+        G.train(was_training)
 
 
 class GraphedStep:

@@ -36,7 +36,8 @@ extern "C" {
  * the embedding gather and the LSTM recurrence of the caption encoder (agan_embedding_*, agan_lstm_*); the train-mode BatchNorm of the
  * trunk on channel slices (agan_bn_relu_slice_fwd, agan_bn_slice_bwd); the trainable general 2-D conv behind Layers.conv
  * (agan_conv2d_train_*: forward, data gradient and weight gradient of any small geometry); the batch preparation from device-resident
- * uint8 shards (agan_image_prep); the two halves of a Lloyd iteration behind the pseudo-caption clustering (agan_kmeans_*). */
+ * uint8 shards (agan_image_prep); the two halves of a Lloyd iteration behind the pseudo-caption clustering (agan_kmeans_*); the
+ * reductions of a generator's evaluation (agan_moments_*, agan_retrieval_rank). */
 
 enum {
     AGAN_OK = 0,
@@ -595,6 +596,38 @@ int agan_kmeans_assign(const float* x /* [N, D] */, const float* centroids /* [K
 size_t agan_kmeans_update_ws_bytes(int N, int D, int K);
 int agan_kmeans_update(const float* x /* [N, D] */, const int32_t* labels /* [N] */, float* centroids /* [K, D] in: previous, out: new */,
                        int32_t* counts /* [K] */, int N, int D, int K, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Evaluation of a generator (csrc/eval.hip; evaluation.py: FeatureMoments, r_precision, Evaluator).
+ *
+ * Streaming raw moments of feature rows x [n, D] fp32 row-major, in fp64:
+ *   agan_moments_update: sum[j] += sum_k x[k][j]; gram[i][j] += sum_k x[k][i] x[k][j] for j >= i.  The state is the UPPER triangle of
+ *     gram [D, D] row-major, diagonal included; what lies below it is unspecified (never read back by agan_moments_finish).  A fresh
+ *     state is all zeros; the caller keeps the row count.  fp32 -> fp64 is exact and so is a product of two fp32 values in fp64: only
+ *     the additions round.  The contraction runs on v_mfma_f64_16x16x4_f64; each element is owned by one workgroup whose accumulator
+ *     starts from gram and walks the rows in ascending order; sum is added in pieces of 512 rows, the pieces in order.
+ *   agan_moments_finish: mean = sum / count; cov = (gram - count mean mean^T) / (count - 1), written as a full matrix that is symmetric
+ *     bit for bit; count == 1 gives cov = 0.
+ *   Domain: n >= 1, 1 <= D <= 4096, n * D < 2^31, 1 <= count < 2^53; tails in n and D are handled inside the kernels.
+ *
+ * agan_retrieval_rank: s[i][j] = q_i . b_c / max(|q_i| |b_c|, 1e-8) with c = cand[i][j] (the cosine of losses/sentence_loss.py without
+ *   gamma3), over GATHERED rows of the bank: no N x M matrix.  rank[i] = #{ j >= 1 : s[i][j] >= s[i][0] } -- column 0 is the match and a
+ *   tie counts against it.  scores may be NULL.  Domain: N, M >= 1, 1 <= D <= 4096, 1 <= R <= 1024.  A candidate outside [0, M) cannot
+ *   be seen by the host without a synchronisation, so it is checked on the device before it is used as an address: the call still
+ *   returns AGAN_OK, rank[i] of every query that holds one is -1 and that candidate's score is NaN; backend/functional.py turns a
+ *   negative rank into ValueError.
+ *
+ * Anything outside the domains, or a missing pointer, is AGAN_EINVAL with a message before any launch (agan_moments_update_ws_bytes then
+ * returns 0); a workspace that is too small is AGAN_EWORKSPACE.  No float atomics; every sum has one fixed order: two runs on the same
+ * inputs give the same bits.  Only enqueues on `stream`: no allocation, no synchronisation.
+ * ---------------------------------------------------------------------------------------------- */
+size_t agan_moments_update_ws_bytes(int n, int D);
+int agan_moments_update(const float* x /* [n, D] */, int n, int D, double* sum /* [D] in/out */, double* gram /* [D, D] in/out */,
+                        void* ws, size_t ws_bytes, void* stream);
+int agan_moments_finish(const double* sum /* [D] */, const double* gram /* [D, D] */, long long count, int D, double* mean /* [D] */,
+                        double* cov /* [D, D] */, void* stream);
+int agan_retrieval_rank(const float* query /* [N, D] */, const float* bank /* [M, D] */, const int32_t* cand /* [N, R] */, int N, int M,
+                        int D, int R, float* scores /* [N, R] or NULL */, int32_t* rank /* [N] */, void* stream);
 
 #ifdef __cplusplus
 }
