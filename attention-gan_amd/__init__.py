@@ -9,7 +9,7 @@ sys.modules so that the reference's own import lines (`from networks.generator i
 """
 import sys as _sys
 
-from . import backend, losses, networks, trainers, utilities  # noqa: F401
+from . import augment, backend, losses, networks, trainers, utilities  # noqa: F401
 from .backend import lib  # noqa: F401
 from .backend.functional import get_precision, set_precision  # noqa: F401
 

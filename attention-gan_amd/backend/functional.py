@@ -1692,6 +1692,67 @@ def image_prep(planes, rows: Optional[Tensor], flip: Optional[Tensor], out=None)
 
 
 # --------------------------------------------------------------------------------------------------------------
+# differentiable augmentation (augment.py; include/agan.h: agan_diffaug_*)
+# --------------------------------------------------------------------------------------------------------------
+def _diffaug_bwd(dy: Tensor, u: Tensor, policy: int) -> Tensor:
+    N, C, H, W = dy.shape
+    dx = torch.empty_like(dy)
+    nbytes = L.load().agan_diffaug_ws_bytes(N, C, H, W)
+    ws, wsp = _ws(nbytes, dy)
+    _kmeans_call("agan_diffaug_bwd", _p(dy), _p(u), policy, _p(dx), N, C, H, W, wsp, nbytes, _stream())
+    return dx
+
+
+class _DiffAugFn(Function):
+    @staticmethod
+    def forward(ctx, u, policy, *xs):
+        x0 = xs[0]
+        x1 = xs[1] if len(xs) > 1 else None
+        n0, C, H, W = x0.shape
+        n1 = 0 if x1 is None else int(x1.shape[0])
+        y = torch.empty((n0 + n1, C, H, W), dtype=torch.float32, device=x0.device)
+        nbytes = L.load().agan_diffaug_ws_bytes(n0 + n1, C, H, W)
+        ws, wsp = _ws(nbytes, x0)
+        _kmeans_call("agan_diffaug_fwd", _p(x0), _p(x1), n0, n1, _p(u), policy, _p(y), C, H, W, wsp, nbytes, _stream())
+        ctx.save_for_backward(u)
+        ctx.policy, ctx.sizes = policy, (n0, n1)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        u, = ctx.saved_tensors
+        n0, n1 = ctx.sizes
+        need = list(ctx.needs_input_grad[2:])
+        dy = _dev(dy, "diffaug dy")
+        if all(need):                                     # one call over the whole batch, split per source
+            dx = _diffaug_bwd(dy, u, ctx.policy)
+            grads = [dx] if n1 == 0 else [dx[:n0], dx[n0:]]
+        else:                                             # only the samples of the source that asks
+            bounds = [(0, n0), (n0, n0 + n1)]
+            grads = [_diffaug_bwd(dy[lo:hi], u[lo:hi], ctx.policy) if want else None for want, (lo, hi) in zip(need, bounds)]
+        return (None, None, *grads)
+
+
+def diffaug(xs, u: Tensor, policy: int) -> Tensor:
+    """DiffAugment of include/agan.h (agan_diffaug_fwd; augment.diffaug_reference states it in torch ops) on one [N, C, H, W] tensor
+    or a PAIR of equal-shaped ones, whose samples come out concatenated in ONE tensor (the [real; fake] batch of
+    NonSaturatingDiscLoss, written by the augmentation itself).  u: [N, 8] uniforms in [0, 1) for all samples of the result, policy:
+    the bit mask of augment.parse_policy.  Differentiable in the images: the backward kernel runs for the sources that require grad."""
+    xs = (xs,) if isinstance(xs, Tensor) else tuple(xs)
+    if not 1 <= len(xs) <= 2:
+        raise ValueError(f"diffaug: expected one tensor or a pair, got {len(xs)}")
+    xs = tuple(_dev(x, "diffaug x") for x in xs)
+    if xs[0].dim() != 4 or any(x.shape != xs[0].shape or x.device != xs[0].device for x in xs):
+        raise ValueError(f"diffaug: expected [N, C, H, W] tensors of one shape on one device, got {[tuple(x.shape) for x in xs]}")
+    n = sum(int(x.shape[0]) for x in xs)
+    u = _dev(u, "diffaug u")
+    if u.device != xs[0].device or tuple(u.shape) != (n, 8):
+        raise ValueError(f"diffaug: u must be [{n}, 8] on {xs[0].device}, got {tuple(u.shape)} on {u.device}")
+    return _DiffAugFn.apply(u, int(policy), *xs)
+
+
+# --------------------------------------------------------------------------------------------------------------
 # k-means (data/captions.py: kmeans; include/agan.h: agan_kmeans_*)
 # --------------------------------------------------------------------------------------------------------------
 # One Lloyd iteration is kmeans_assign + kmeans_update.  Device tensors run on the library; a CPU tensor takes the torch restatement

@@ -21,6 +21,7 @@ COMM_ID_BYTES = 128    # include/agan.h: AGAN_COMM_ID_BYTES
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2          # include/agan.h: AGAN_DT_* (storage type of an activation tensor)
 AMAX_SLOT = 256        # floats per amax slot (include/agan.h: AGAN_AMAX_SLOT)
 EINVAL, EWORKSPACE = -1, -2                # include/agan.h: AGAN_EINVAL, AGAN_EWORKSPACE
+DIFFAUG_COLOR, DIFFAUG_TRANSLATION, DIFFAUG_CUTOUT = 1, 2, 4      # include/agan.h: AGAN_DIFFAUG_*
 ABI_VERSION = 101      # include/agan.h: AGAN_VERSION this binding was written against (argument lists changed between versions)
 
 
@@ -158,6 +159,9 @@ _SIGNATURES = {
     "agan_moments_update": (c_int, [_P, c_int, c_int, _P, _P, _P, c_size_t, _P]),
     "agan_moments_finish": (c_int, [_P, _P, c_int64, c_int, _P, _P, _P]),
     "agan_retrieval_rank": (c_int, [_P, _P, _P] + [c_int] * 4 + [_P, _P, _P]),
+    "agan_diffaug_ws_bytes": (c_size_t, [c_int] * 4),
+    "agan_diffaug_fwd": (c_int, [_P, _P, c_int, c_int, _P, c_int, _P, c_int, c_int, c_int, _P, c_size_t, _P]),
+    "agan_diffaug_bwd": (c_int, [_P, _P, c_int, _P, c_int, c_int, c_int, c_int, _P, c_size_t, _P]),
     "agan_adam_step": (c_int, [_P, _P, _P, _P, c_size_t, _P, c_double, c_double, c_double, c_double, c_float, _P]),
 }
 

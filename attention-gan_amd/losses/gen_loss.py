@@ -12,14 +12,17 @@ class GenLoss:
     def make_labels_for_real_imgs(self, num_labels: int, device="cuda") -> Tensor:
         return torch.ones(num_labels, device=device)
 
-    def get_loss(self, discriminator: Module, fake_images: Tensor) -> Tensor:
+    def get_loss(self, discriminator: Module, fake_images: Tensor, augment=None) -> Tensor:
+        """`augment`: an optional callable applied to the images before D (the generator's gradient flows through it)."""
         raise NotImplementedError
 
 
 class NonSaturatingGenLoss(GenLoss):
     """-mean(log(D(G(z)) + 1e-8))  (gen_loss.py:42-46)."""
 
-    def get_loss(self, discriminator: Module, fake_images: Tensor) -> Tensor:
+    def get_loss(self, discriminator: Module, fake_images: Tensor, augment=None) -> Tensor:
+        if augment is not None:
+            fake_images = augment(fake_images)
         return HF.ns_gen_loss(discriminator(fake_images))
 
 
@@ -27,6 +30,8 @@ class StandardGenLoss(GenLoss):
     """BCE(D(G(z)), 1)  (gen_loss.py:21-35).  Not used by train.py:74; the discriminator runs on the HIP kernels, the
     cross-entropy over its [B] probabilities is a stock ATen elementwise op."""
 
-    def get_loss(self, discriminator: Module, fake_images: Tensor) -> Tensor:
+    def get_loss(self, discriminator: Module, fake_images: Tensor, augment=None) -> Tensor:
+        if augment is not None:
+            fake_images = augment(fake_images)
         p = discriminator(fake_images)
         return torch.nn.functional.binary_cross_entropy(p, self.make_labels_for_real_imgs(p.shape[0], device=p.device))

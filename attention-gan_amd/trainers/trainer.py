@@ -12,6 +12,7 @@ import torch
 from torch import Tensor
 from torch.nn import Module
 
+from ..augment import parse_policy
 from ..backend import functional as HF
 from ..dataparallel import GradBuckets, any_rank, averaged_buffers, broadcast_module_, rank_of, world_size
 from ..losses.disc_loss import NonSaturatingDiscLoss
@@ -130,7 +131,8 @@ class ModelTrainer:
 
 
 # what the generator's forward leaves for the rest of the step
-_Forward = collections.namedtuple("_Forward", "labels mask fakes attn mu logvar")
+# (aug_u: the augmentation's uniforms [3 * len(Ds), B, 8], None without a policy)
+_Forward = collections.namedtuple("_Forward", "labels mask fakes attn mu logvar aug_u")
 
 
 def _forked(streams, i: int, main):
@@ -147,13 +149,22 @@ class GanTrainStep(ModelTrainer):
     Results-identical departures from the script: fakes are detached in the D updates (the reference back-props
     through G there and discards the result at :132); D weight gradients are not produced in the G update.
     BatchNorm call order per D is kept: real batch, fake batch (D update), fake batch again (G update).
+
+    `augment`: a DiffAugment policy ("color,translation,cutout", any subset; augment.parse_policy) applied to every image a
+    discriminator sees -- real and fake in its own update, fake again in the generator update, where the gradient flows through
+    the transform (backend.functional.diffaug: two launches per tensor).  The uniforms are ONE torch.rand draw per step from
+    `self.rng`, taken in _gen_forward right after noise and eps: aug_u [3 * len(Ds), B, 8], slot 3i for discriminator i's real
+    batch, 3i + 1 for its fake batch, 3i + 2 for the fake batch in the generator update.  The image encoder (DAMSM branch)
+    sees the un-augmented image; generate_images and evaluate never augment.  The policy is configuration, not checkpoint
+    content.  With None (default) nothing is drawn and no kernel runs.
     """
 
     def __init__(self, generator: Module, discriminators: Sequence[Module], image_encoder: Optional[Callable] = None,
                  gen_lr: float = 2e-4, disc_lr: float = 2e-4, gamma1: float = 4.0, gamma2: float = 5.0, gamma3: float = 10.0,
                  wlambda: float = 5.0, slambda: float = 5.0, bucket_bytes: int = 64 << 20, group=None, seed: int = 0,
-                 g_bucket_bytes: Optional[int] = None):
+                 g_bucket_bytes: Optional[int] = None, augment: Optional[str] = None):
         super().__init__()
+        self.augment = parse_policy(augment)                # bit mask; 0 = no augmentation
         self.G, self.Ds, self.image_encoder = generator, list(discriminators), image_encoder
         self.group = group
         for m in [self.G] + self.Ds:
@@ -200,7 +211,7 @@ class GanTrainStep(ModelTrainer):
         return self._streams
 
     def step(self, word_embs: Tensor, sent_embs: Tensor, lengths, class_ids, real_imgs: Sequence[Tensor],
-             noise: Optional[Tensor] = None, eps: Optional[Tensor] = None) -> Dict[str, Tensor]:
+             noise: Optional[Tensor] = None, eps: Optional[Tensor] = None, aug_u: Optional[Tensor] = None) -> Dict[str, Tensor]:
         if word_embs.is_cuda and not (isinstance(lengths, Tensor) and lengths.is_cuda):
             # host-side caption lengths (the reference's DataLoader hands over a list / CPU tensor): ONE pinned, non-blocking
             # copy up front -- a blocking H2D copy in the middle of the step drains the launch pipeline (~4 ms per step)
@@ -210,12 +221,12 @@ class GanTrainStep(ModelTrainer):
             HF.amax_begin_step(word_embs.device)        # zeroed amax slots of this step (fp16 split mode only; one fill launch)
         prev_side = HF.set_wgrad_side_stream(self.overlap_weight_gradients and word_embs.is_cuda)
         try:
-            return self._step(word_embs, sent_embs, lengths, class_ids, real_imgs, noise, eps)
+            return self._step(word_embs, sent_embs, lengths, class_ids, real_imgs, noise, eps, aug_u)
         finally:
             HF.set_wgrad_side_stream(prev_side)
 
-    def _step(self, word_embs, sent_embs, lengths, class_ids, real_imgs, noise, eps) -> Dict[str, Tensor]:
-        fw = self._gen_forward(word_embs, sent_embs, lengths, noise, eps)
+    def _step(self, word_embs, sent_embs, lengths, class_ids, real_imgs, noise, eps, aug_u=None) -> Dict[str, Tensor]:
+        fw = self._gen_forward(word_embs, sent_embs, lengths, noise, eps, aug_u)
         out: Dict[str, Tensor] = {}
         # ---- discriminator updates (train.py:123-130) ----
         # The three updates are independent of each other (each D has its own weights, optimiser and images), so each runs on
@@ -244,7 +255,7 @@ class GanTrainStep(ModelTrainer):
         return self._results(fw, out)
 
     # -- the phases of the step: _step() runs them eagerly, capture_segments() records each into a graph of its own --------
-    def _gen_forward(self, word_embs, sent_embs, lengths, noise, eps) -> "_Forward":
+    def _gen_forward(self, word_embs, sent_embs, lengths, noise, eps, aug_u=None) -> "_Forward":
         b = word_embs.shape[0]
         labels = self._make_match_labels(b)
         mask = self._make_mask(lengths, word_embs.shape[2])
@@ -252,14 +263,29 @@ class GanTrainStep(ModelTrainer):
             noise = torch.randn(b, self.G.z_dim, dtype=torch.float32, device=word_embs.device, generator=self.rng)
         if eps is None:
             eps = torch.randn(b, self.G.cond_dim, dtype=torch.float32, device=word_embs.device, generator=self.rng)
-        return _Forward(labels, mask, *self.G(noise, sent_embs, word_embs, mask, eps))
+        if not self.augment:
+            aug_u = None
+        elif aug_u is None:                                 # drawn HERE, after noise and eps: the one place whose graph registers self.rng
+            aug_u = torch.rand(3 * len(self.Ds), b, 8, dtype=torch.float32, device=word_embs.device, generator=self.rng)
+        elif tuple(aug_u.shape) != (3 * len(self.Ds), b, 8):
+            raise ValueError(f"aug_u must be [{3 * len(self.Ds)}, {b}, 8], got {tuple(aug_u.shape)}")
+        return _Forward(labels, mask, *self.G(noise, sent_embs, word_embs, mask, eps), aug_u)
+
+    def _augmenter(self, fw: "_Forward", first: int, count: int) -> Optional[Callable]:
+        """What the losses apply to the images before D: slots first .. first + count - 1 of the step's uniforms, one per tensor."""
+        if fw.aug_u is None:
+            return None
+        u = fw.aug_u[first:first + count].reshape(-1, 8)    # (adjacent slots: a view, no launch)
+        return lambda xs: HF.diffaug(xs, u, self.augment)
 
     def _d_backward(self, i: int, fw: "_Forward", real_imgs, out: Dict[str, Tensor], arm: bool = False) -> None:
         """Discriminator i's gradients on the current stream; `arm`: its buckets exchange them from the backward's hooks."""
         self.d_opts[i].zero_grad()
         if arm:
             self.d_buckets[i].arm()
-        loss = self.disc_loss.get_loss(self.Ds[i], fw.fakes[i].detach(), real_imgs[i])
+        aug = self._augmenter(fw, 3 * i, 2)                 # (None without a policy: the call is then the one it always was)
+        loss = (self.disc_loss.get_loss(self.Ds[i], fw.fakes[i].detach(), real_imgs[i]) if aug is None else
+                self.disc_loss.get_loss(self.Ds[i], fw.fakes[i].detach(), real_imgs[i], augment=aug))
         loss.backward()
         out[f"d_loss{i}"] = loss.detach()
 
@@ -279,7 +305,8 @@ class GanTrainStep(ModelTrainer):
             terms = []
             for i, d in enumerate(self.Ds):
                 with _forked(streams, i, main):
-                    gl = self.gen_loss.get_loss(d, fw.fakes[i])
+                    aug = self._augmenter(fw, 3 * i + 2, 1)
+                    gl = self.gen_loss.get_loss(d, fw.fakes[i]) if aug is None else self.gen_loss.get_loss(d, fw.fakes[i], augment=aug)
                     terms.append(gl)
                     out[f"g_loss{i}"] = gl.detach()
                     if i == len(self.Ds) - 1 and self.image_encoder is not None:
@@ -315,7 +342,7 @@ class GanTrainStep(ModelTrainer):
         out["mu"], out["logvar"] = fw.mu.detach(), fw.logvar.detach()
         return out
 
-    def _warm_up(self, who: str, word_embs, sent_embs, lengths, real_imgs, warmup: int, noise, eps) -> None:
+    def _warm_up(self, who: str, word_embs, sent_embs, lengths, real_imgs, warmup: int, noise, eps, aug_u=None) -> None:
         """What both captures do first: `warmup` real train steps off the default stream, then the host-side tables."""
         if not (isinstance(lengths, Tensor) and lengths.is_cuda and lengths.dtype == torch.int64):
             raise ValueError(f"{who}(): lengths must be an int64 device tensor")
@@ -323,34 +350,35 @@ class GanTrainStep(ModelTrainer):
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):                      # warm-up off the default stream: tables, caches, allocator pools
             for _ in range(max(1, warmup)):
-                self.step(word_embs, sent_embs, lengths, None, real_imgs, noise, eps)
+                self.step(word_embs, sent_embs, lengths, None, real_imgs, noise, eps, aug_u)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         HF.build_pack_tables()                             # the batched re-pack's job tables: host work, not capturable
 
     # -- whole-step HIP graph ----------------------------------------------------------------------------------------
     def capture(self, word_embs: Tensor, sent_embs: Tensor, lengths: Tensor, real_imgs: Sequence[Tensor], warmup: int = 2,
-                noise: Optional[Tensor] = None, eps: Optional[Tensor] = None) -> "GraphedStep":
+                noise: Optional[Tensor] = None, eps: Optional[Tensor] = None, aug_u: Optional[Tensor] = None) -> "GraphedStep":
         """Capture one full train step (all four optimiser updates, every stream) into a HIP graph.
 
         The arguments become the graph's STATIC input buffers: copy each new batch into them (`.copy_()`) and call `replay()`.
         `lengths` must be a device int64 tensor (no host reads inside the step); noise and the CA-net eps are drawn inside the
-        graph (graph-safe Philox state) unless static `noise` / `eps` buffers are given; BatchNorm counters and the Adam step
+        graph (graph-safe Philox state) unless static `noise` / `eps` buffers are given, and so are the augmentation's uniforms
+        (`aug_u`, with an `augment` policy); BatchNorm counters and the Adam step
         counters live in device memory, so replays keep advancing exactly like eager steps.  The warm-up steps are real
         training steps.  Single-process only: with world_size > 1 run the eager `step()`."""
         if self.g_buckets.active:
             raise RuntimeError("capture(): the all-reduce path is not captured; use step() under torch.distributed")
-        self._warm_up("capture", word_embs, sent_embs, lengths, real_imgs, warmup, noise, eps)
+        self._warm_up("capture", word_embs, sent_embs, lengths, real_imgs, warmup, noise, eps, aug_u)
         graph = torch.cuda.CUDAGraph()
         if self.rng.device.type == "cuda":
             graph.register_generator_state(self.rng)       # noise / eps draws inside the graph advance this generator on replay
         with torch.cuda.graph(graph):
-            out = self.step(word_embs, sent_embs, lengths, None, real_imgs, noise, eps)
+            out = self.step(word_embs, sent_embs, lengths, None, real_imgs, noise, eps, aug_u)
         return GraphedStep(graph, out)
 
     # -- segment-wise HIP graphs for world > 1 --------------------------------------------------------------------------
     def capture_segments(self, word_embs: Tensor, sent_embs: Tensor, lengths: Tensor, real_imgs: Sequence[Tensor], warmup: int = 2,
-                         noise: Optional[Tensor] = None, eps: Optional[Tensor] = None) -> "SegmentedStep":
+                         noise: Optional[Tensor] = None, eps: Optional[Tensor] = None, aug_u: Optional[Tensor] = None) -> "SegmentedStep":
         """The train step as NINE HIP graphs with the gradient exchange launched between them -- the form for world_size > 1, where
         the whole-step graph of capture() cannot be used (the RCCL collectives are not captured) and an eager step costs every rank
         ~11 ms of Python per 27 ms step on host cores the 8 ranks share:
@@ -364,7 +392,7 @@ class GanTrainStep(ModelTrainer):
         first -- and nothing overlaps the generator's 28 MB.  The arguments become static input buffers exactly as for capture();
         the graphs share one memory pool and must be replayed in capture order (SegmentedStep.replay does).  Results are
         bit-identical to the eager step (tests/test_gpu_dataparallel.py, one-rank `nccl` rehearsal)."""
-        self._warm_up("capture_segments", word_embs, sent_embs, lengths, real_imgs, warmup, noise, eps)
+        self._warm_up("capture_segments", word_embs, sent_embs, lengths, real_imgs, warmup, noise, eps, aug_u)
         # memory pools: graphs that share a pool must never run concurrently (a later capture re-uses the temporaries an earlier one
         # freed).  The three discriminator updates replay CONCURRENTLY on their own streams, so each gets a private pool for its two
         # graphs; the generator's graphs, which run alone, share one.
@@ -387,7 +415,7 @@ class GanTrainStep(ModelTrainer):
                 g0.register_generator_state(self.rng)
             with torch.cuda.graph(g0, pool=pool, capture_error_mode=mode):
                 HF.amax_begin_step(word_embs.device)
-                fw = self._gen_forward(word_embs, sent_embs, lengths, noise, eps)
+                fw = self._gen_forward(word_embs, sent_embs, lengths, noise, eps, aug_u)
             seg.gen_forward = g0
             out: Dict[str, Tensor] = {}
             # ---- discriminator updates: backward graph, (exchange), Adam graph ----

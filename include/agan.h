@@ -629,6 +629,45 @@ int agan_moments_finish(const double* sum /* [D] */, const double* gram /* [D, D
 int agan_retrieval_rank(const float* query /* [N, D] */, const float* bank /* [M, D] */, const int32_t* cand /* [N, R] */, int N, int M,
                         int D, int R, float* scores /* [N, R] or NULL */, int32_t* rank /* [N] */, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Differentiable augmentation of discriminator inputs (csrc/diffaug.hip; augment.py: diffaug_reference; backend/functional.py: diffaug).
+ * DiffAugment (Zhao et al. 2020): the same family of random colour, translation and cutout transforms on real and fake images on every
+ * pass through a discriminator, differentiated in the generator update.  THIS text defines the transform.
+ *
+ * x is [N, C, H, W] fp32, 1 <= C <= 4; u is [N, 8] fp32 uniforms in [0, 1), slot 7 reserved; policy is a mask of AGAN_DIFFAUG_*.  int()
+ * truncates.  Per sample n, with u0..u6 = u[n][0..6], in this order (a policy bit that is off skips its stage):
+ *   COLOR        b = u0 - 0.5, s = 2 u1, c = u2 + 0.5.   v = x + b;  m = mean of v over the C channels of the pixel;  w = s (v - m) + m;
+ *                M = mean of w over C, H, W of the sample;  z = c (w - M) + M.  Saturation keeps a pixel's channel mean, so
+ *                M = mean(x) + b: one reduction over the input.
+ *   TRANSLATION  Sy = int(0.125 H + 0.5), ty = min(int(u3 * (2 Sy + 1)), 2 Sy) - Sy with the product formed in fp32; Sx, tx likewise from
+ *                W and u4.  out[y][x] = z[y - ty][x - tx], and 0 where that lies outside the image.
+ *   CUTOUT       ch = int(0.5 H + 0.5), oy = min(int(u5 * (H + 1 - ch % 2)), H - ch % 2) (fp32 product); cw, ox likewise from W and u6.
+ *                Rows oy - ch/2 <= y < oy - ch/2 + ch (integer ch/2) and the matching columns, clipped to the image, become 0 in the
+ *                translated image.
+ * The map is linear in x for fixed u; agan_diffaug_bwd is its transpose: g[y][x] = dy[y + ty][x + tx] where that position lies inside
+ * the image and is not cut, else 0;  dw = c g + (1 - c) mean_CHW(g);  dx = s dw + (1 - s) mean_C(dw).
+ *
+ * agan_diffaug_fwd takes its N = n0 + n1 samples from TWO sources -- samples 0..n0-1 from x0, n0..N-1 from x1 (x1 NULL: n1 = 0) -- and
+ * writes ONE [N, C, H, W] tensor y: the [real; fake] batch a discriminator reads is produced by the augmentation itself, no
+ * concatenation pass.  y must not overlap a source; dx must not overlap dy.
+ * Each call is a sum launch (per-sample sums in fp64: workgroup partials go to the workspace and are added in workgroup order; skipped
+ * without COLOR, when the forward is a pure masked gather that moves bits unchanged) and an apply launch.  The kernels compute
+ * w = fma(s, v, (1 - s) m) and z = fma(c, w, (1 - c) M) (and the transposes alike), so s = 1 and c = 1 are exact identities.  Stores are
+ * 16 bytes per lane where W % 4 == 0 and the bases are 16-byte aligned.  No atomics, no allocation, no synchronisation: run-to-run
+ * identical and graph-capturable; the workspace's contents on entry do not matter.
+ * AGAN_EINVAL with a message before any launch for C outside 1..4, a non-positive size, a missing pointer, a policy outside 0..7 or
+ * N * C * H * W >= 2^31 (agan_diffaug_ws_bytes then returns 0); AGAN_EWORKSPACE for a workspace that is too small.
+ * ---------------------------------------------------------------------------------------------- */
+#define AGAN_DIFFAUG_COLOR 1
+#define AGAN_DIFFAUG_TRANSLATION 2
+#define AGAN_DIFFAUG_CUTOUT 4
+size_t agan_diffaug_ws_bytes(int N, int C, int H, int W);
+int agan_diffaug_fwd(const float* x0 /* [n0, C, H, W] */, const float* x1 /* [n1, C, H, W] or NULL */, int n0, int n1,
+                     const float* u /* [n0 + n1, 8] */, int policy, float* y /* [n0 + n1, C, H, W] */, int C, int H, int W, void* ws,
+                     size_t ws_bytes, void* stream);
+int agan_diffaug_bwd(const float* dy /* [N, C, H, W] */, const float* u /* [N, 8] */, int policy, float* dx /* [N, C, H, W] */, int N, int C,
+                     int H, int W, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
