@@ -1240,11 +1240,64 @@ def adam_step_(param: Tensor, grad: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor,
         raise L.AganError("adam_step_: step_state must be an int32 device tensor of 4 elements")
     L.call("agan_adam_step", _p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), param.numel(), _p(step_state), float(lr),
            float(beta1), float(beta2), float(eps), float(grad_scale), _stream())
-    rng = _flat_range(param.data_ptr())
+    mark_flat_written(param)
+
+
+# --------------------------------------------------------------------------------------------------------------
+# exponential moving average of weights over a segment table (include/agan.h: agan_ema_update; optim.FlatEMA)
+# --------------------------------------------------------------------------------------------------------------
+_EMA_SEG_DTYPE = [("src", "<u8"), ("dst", "<u8"), ("n", "<i8"), ("first_block", "<i4"), ("reserved", "<i4")]      # include/agan.h: agan_ema_seg
+
+
+def ema_table(pairs, device) -> Tuple[Tensor, int, int]:
+    """(device table, nseg, total_blocks) for `pairs` = [(src address, dst address, floats), ...]: checked and planned on the host
+    (agan_ema_plan), one H2D copy."""
+    import numpy as np
+    pairs = list(pairs)
+    segs = np.zeros(len(pairs), dtype=_EMA_SEG_DTYPE)
+    for i, (src, dst, n) in enumerate(pairs):
+        segs[i] = (int(src), int(dst), int(n), 0, 0)
+    total = L.load().agan_ema_plan(c_void_p(segs.ctypes.data), len(pairs))
+    if total <= 0:
+        L.check(total if total < 0 else L.EINVAL, "agan_ema_plan")
+    return torch.from_numpy(segs.view(np.uint8).copy()).to(device), len(pairs), int(total)
+
+
+def mark_flat_written(flat: Tensor) -> None:
+    """A kernel wrote `flat` through its raw pointer: packed copies of its views are stale (what adam_step_ and ema_update_ do after
+    their launch; a replayed HIP graph that holds such a launch needs it said once per replay)."""
+    rng = _flat_range(flat.data_ptr())
     if rng is not None:
         rng[2] += 1
     else:
         bump_weight_epoch()
+
+
+def ema_update_(table: Tensor, nseg: int, total_blocks: int, state: Tensor, decay: float, warmup: bool, flat_dst: Tensor) -> None:
+    """One averaging update dst += (1 - beta_t) * (src - dst) over every segment of `table` (ema_table).  `state` is the average's
+    4-element int32 device tensor: the kernel reads the update count t from it, derives beta_t on the device and advances the
+    count (graph-replay safe).  `flat_dst` is the flat buffer among the destinations whose views are conv / linear weights."""
+    if not table.is_cuda or table.dtype != torch.uint8 or not table.is_contiguous() or table.numel() < 32 * int(nseg):
+        raise L.AganError("ema_update_: the segment table must be a contiguous uint8 device tensor of 32 bytes per segment")
+    if not state.is_cuda or state.dtype != torch.int32 or state.numel() < 4:
+        raise L.AganError("ema_update_: state must be an int32 device tensor of 4 elements")
+    if not flat_dst.is_cuda or flat_dst.dtype != torch.float32 or not flat_dst.is_contiguous():
+        raise L.AganError("ema_update_: flat contiguous float32 device buffer required")
+    L.call("agan_ema_update", _p(table), int(nseg), int(total_blocks), _p(state), float(decay), int(bool(warmup)), _stream())
+    mark_flat_written(flat_dst)
+
+
+def ema_beta(t: int, decay: float, warmup: bool = True) -> float:
+    """beta_t of update number t (0-based), in double as the tick kernel forms it"""
+    return min(float(decay), (1.0 + t) / (10.0 + t)) if warmup else float(decay)
+
+
+def ema_reference(src: Tensor, dst: Tensor, t: int, decay: float, warmup: bool = True) -> Tensor:
+    """float64 oracle of update number t: dst + omb * (src - dst) with the SAME fp32-rounded omb = float32(1 - beta_t) the kernel uses,
+    everything else in double.  Returns a new tensor."""
+    omb = float(torch.tensor(1.0 - ema_beta(t, decay, warmup), dtype=torch.float64).to(torch.float32))
+    d = dst.detach().double()
+    return d + omb * (src.detach().double() - d)
 
 
 # --------------------------------------------------------------------------------------------------------------

@@ -162,6 +162,8 @@ _SIGNATURES = {
     "agan_diffaug_ws_bytes": (c_size_t, [c_int] * 4),
     "agan_diffaug_fwd": (c_int, [_P, _P, c_int, c_int, _P, c_int, _P, c_int, c_int, c_int, _P, c_size_t, _P]),
     "agan_diffaug_bwd": (c_int, [_P, _P, c_int, _P, c_int, c_int, c_int, c_int, _P, c_size_t, _P]),
+    "agan_ema_plan": (c_int, [_P, c_int]),
+    "agan_ema_update": (c_int, [_P, c_int, c_int, _P, c_double, c_int, _P]),
     "agan_adam_step": (c_int, [_P, _P, _P, _P, c_size_t, _P, c_double, c_double, c_double, c_double, c_float, _P]),
 }
 

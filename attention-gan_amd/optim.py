@@ -159,3 +159,147 @@ class FlatAdam:
         with torch.no_grad():
             self.step_state.zero_()
             self.step_state[0] = self.step_count
+
+
+class FlatEMA:
+    """Exponential moving average of a module's weights in a shadow module, as ONE fused HIP launch per update.
+
+    The shadow's trainable parameters are re-homed into a flat buffer of its own with `live_opt`'s order, offsets and padding, so
+    the parameter part of an update is one flat-to-flat segment; every floating-point buffer of the live module (BatchNorm running
+    statistics) is one more segment into the shadow's buffer of the same name.  Integer buffers (num_batches_tracked) are not
+    averaged: shadow_state_dict() copies them from the live module.  Parameters the live optimiser does not own (frozen ones) stay
+    as the shadow holds them.  update() does  shadow += (1 - beta_t) * (live - shadow)  with beta_t = min(decay, (1 + t) / (10 + t))
+    (warmup) or decay, t counted in device memory (include/agan.h: agan_ema_update).
+
+    The shadow is an inference copy: no gradients, always in eval mode (its train() is pinned to False -- batch statistics would
+    depend on the batch), and its packed weights follow the shadow buffer's own epoch (HF.register_flat)."""
+
+    def __init__(self, live_module: nn.Module, shadow_module: nn.Module, live_opt: FlatAdam, decay: float, warmup: bool = True):
+        if not 0.0 < float(decay) < 1.0:
+            raise ValueError(f"FlatEMA: decay must lie inside (0, 1), got {decay}")
+        self.live, self.shadow, self.live_opt = live_module, shadow_module, live_opt
+        self.decay, self.warmup = float(decay), bool(warmup)
+        live_named = [(k, p) for k, p in live_module.named_parameters() if p.requires_grad]
+        if len(live_named) != len(live_opt.params) or any(p is not q for (_, p), q in zip(live_named, live_opt.params)):
+            raise ValueError("FlatEMA: live_opt does not hold the trainable parameters of live_module in named_parameters() order")
+        if any(p.dtype != torch.float32 for p in shadow_module.parameters()):
+            raise ValueError("FlatEMA: float32 parameters only")
+        live_all = {k: tuple(p.shape) for k, p in live_module.named_parameters()}
+        shadow_all = {k: tuple(p.shape) for k, p in shadow_module.named_parameters()}
+        if live_all != shadow_all:
+            odd = sorted(k for k in set(live_all) | set(shadow_all) if live_all.get(k) != shadow_all.get(k))
+            raise ValueError(f"FlatEMA: the shadow's parameters differ from the live module's in name or shape: {odd[:4]}")
+        shadow_params = dict(shadow_module.named_parameters())
+        self.params: List[nn.Parameter] = [shadow_params[k] for k, _ in live_named]
+        self.offsets, total = [], 0
+        for p in self.params:
+            self.offsets.append(total)
+            total += (p.numel() + 3) // 4 * 4
+        assert self.offsets == live_opt.offsets and total == live_opt.numel, "FlatEMA: the shadow's layout must be the live optimiser's"
+        self.numel = total
+        self.flat = torch.zeros(total, dtype=torch.float32, device=live_opt.flat.device)
+        with torch.no_grad():
+            for p, o in zip(self.params, self.offsets):
+                self.flat[o:o + p.numel()].copy_(p.detach().reshape(-1))
+                p.data = self.flat[o:o + p.numel()].view(p.shape)
+                p.grad = None
+        for p in shadow_module.parameters():
+            p.requires_grad_(False)
+        for m in shadow_module.modules():                  # packed copies the original had made of ITS weights
+            if isinstance(m.__dict__.get("_packed"), dict):
+                m._packed = {}
+        if self.flat.is_cuda:
+            HF.register_flat(self.flat)
+        cls = type(shadow_module)
+        shadow_module.__class__ = type(cls.__name__, (cls,), {"train": lambda self, mode=True: nn.Module.train(self, False),
+                                                              "__module__": cls.__module__})
+        shadow_module.train(False)
+        self.updates = 0
+        self.state = torch.zeros(4, dtype=torch.int32, device=self.flat.device)    # [0] update count, [2] fp32 1 - beta_t (device-made)
+        self._table = None
+        if self.flat.is_cuda:
+            self._segments()
+
+    def __del__(self):
+        try:
+            HF.unregister_flat(self.flat)
+        except Exception:      # interpreter shutdown
+            pass
+
+    def _buffer_pairs(self):
+        """[(live module's buffer dict, shadow module's buffer dict, name)] of every floating-point buffer, checked"""
+        shadow_mods = dict(self.shadow.named_modules())
+        pairs = []
+        for prefix, m in self.live.named_modules():
+            for k, b in m._buffers.items():
+                if b is None or not b.is_floating_point():
+                    continue
+                sm = shadow_mods.get(prefix)
+                s = sm._buffers.get(k) if sm is not None else None
+                name = f"{prefix}.{k}" if prefix else k
+                if s is None or s.shape != b.shape:
+                    raise ValueError(f"FlatEMA: the shadow has no buffer {name!r} of shape {tuple(b.shape)}")
+                if b.dtype != torch.float32 or s.dtype != torch.float32 or not (b.is_contiguous() and s.is_contiguous()) or s.device != b.device:
+                    raise ValueError(f"FlatEMA: buffer {name!r} must be contiguous float32 on one device in both modules")
+                pairs.append((m._buffers, sm._buffers, k))
+        return pairs
+
+    def _segments(self):
+        """(device table, nseg, total_blocks).  Built once; before every launch the recorded addresses are compared with the modules'
+        buffers of the moment (a .to() or a dtype change reallocates them) and the table is rebuilt when one moved."""
+        hit = self._table
+        if hit is not None:
+            key, pairs = hit[0], hit[1]
+            if key[0][0] == self.live_opt.flat.data_ptr() and all(
+                    lb[k].data_ptr() == ptrs[0] and sb[k].data_ptr() == ptrs[1] for (lb, sb, k), ptrs in zip(pairs, key[1:])):
+                return hit[2:]
+        if self.flat.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise HF.L.AganError("averaging segment table missing or stale during HIP-graph capture: run a warm-up step first "
+                                 "(GanTrainStep.capture does)")
+        pairs = self._buffer_pairs()
+        key = [(self.live_opt.flat.data_ptr(), self.flat.data_ptr(), self.numel)] + \
+              [(lb[k].data_ptr(), sb[k].data_ptr(), lb[k].numel()) for lb, sb, k in pairs]
+        self._table = (key, pairs) + HF.ema_table(key, self.flat.device)
+        return self._table[2:]
+
+    def update(self) -> None:
+        if not self.flat.is_cuda:
+            raise RuntimeError("FlatEMA.update: parameters are not on an MI355X (no CPU fallback)")
+        table, nseg, total = self._segments()
+        self.updates += 1
+        HF.ema_update_(table, nseg, total, self.state, self.decay, self.warmup, self.flat)
+
+    def mark_updated(self) -> None:
+        """A replayed HIP graph ran update(): the shadow's packed weights are stale (update() itself says so when it runs eagerly)."""
+        HF.mark_flat_written(self.flat)
+
+    def sync_updates(self) -> int:
+        """The device counter is the truth (a replayed HIP graph advances only it): mirror it on the host.  One host sync."""
+        self.updates = int(self.state[0].item())
+        return self.updates
+
+    def copy_from_live(self) -> None:
+        """shadow := live (parameters and buffers), update count 0"""
+        with torch.no_grad():
+            self.shadow.load_state_dict(self.live.state_dict())
+            self.state.zero_()
+        self.updates = 0
+
+    def shadow_state_dict(self) -> Dict:
+        with torch.no_grad():
+            shadow = dict(self.shadow.named_buffers())
+            for k, b in self.live.named_buffers():
+                if not b.is_floating_point() and k in shadow:
+                    shadow[k].copy_(b)
+        return self.shadow.state_dict()
+
+    def state_dict(self) -> Dict:
+        return {"shadow": self.shadow_state_dict(), "decay": self.decay, "warmup": self.warmup, "updates": self.sync_updates()}
+
+    def load_state_dict(self, sd: Dict) -> None:
+        """decay and warmup are configuration: the constructor's values stay."""
+        with torch.no_grad():
+            self.shadow.load_state_dict(sd["shadow"])
+            self.updates = int(sd.get("updates", 0))
+            self.state.zero_()
+            self.state[0] = self.updates

@@ -4,6 +4,8 @@ from __future__ import annotations
 
 import collections
 import contextlib
+import copy
+import logging
 import math
 import os
 from typing import Callable, Dict, List, Optional, Sequence
@@ -20,7 +22,7 @@ from ..losses.gen_loss import NonSaturatingGenLoss
 from ..losses.KL_loss import KL_loss
 from ..losses.sentence_loss import SentenceLoss
 from ..losses.words_loss import WordsLoss
-from ..optim import FlatAdam
+from ..optim import FlatAdam, FlatEMA
 
 
 def _device() -> torch.device:
@@ -157,13 +159,22 @@ class GanTrainStep(ModelTrainer):
     batch, 3i + 1 for its fake batch, 3i + 2 for the fake batch in the generator update.  The image encoder (DAMSM branch)
     sees the un-augmented image; generate_images and evaluate never augment.  The policy is configuration, not checkpoint
     content.  With None (default) nothing is drawn and no kernel runs.
+
+    `ema`: the decay of an exponential moving average of the generator (optim.FlatEMA; `ema_warmup`: beta_t = min(ema, (1 + t) /
+    (10 + t))).  `self.G_ema` is a copy of the generator taken before training whose weights and BatchNorm running statistics follow
+    the live ones by ONE launch right after the generator's Adam step -- in step(), inside capture()'s graph and inside the Adam
+    graph of capture_segments() alike; warm-up steps count.  generate_images(use_ema=True) and evaluate(use_ema=True) sample it;
+    state_dict() carries it as "generator_ema" and "ema".  With None (default) there is no copy, no launch and no checkpoint key.
     """
 
     def __init__(self, generator: Module, discriminators: Sequence[Module], image_encoder: Optional[Callable] = None,
                  gen_lr: float = 2e-4, disc_lr: float = 2e-4, gamma1: float = 4.0, gamma2: float = 5.0, gamma3: float = 10.0,
                  wlambda: float = 5.0, slambda: float = 5.0, bucket_bytes: int = 64 << 20, group=None, seed: int = 0,
-                 g_bucket_bytes: Optional[int] = None, augment: Optional[str] = None):
+                 g_bucket_bytes: Optional[int] = None, augment: Optional[str] = None, ema: Optional[float] = None,
+                 ema_warmup: bool = True):
         super().__init__()
+        if ema is not None and not 0.0 < float(ema) < 1.0:
+            raise ValueError(f"GanTrainStep: ema must be a decay inside (0, 1) or None, got {ema}")
         self.augment = parse_policy(augment)                # bit mask; 0 = no augmentation
         self.G, self.Ds, self.image_encoder = generator, list(discriminators), image_encoder
         self.group = group
@@ -179,7 +190,10 @@ class GanTrainStep(ModelTrainer):
         # training noise stream
         self.sample_rng = torch.Generator(device=dev0)
         self.sample_rng.manual_seed(int(seed) * 1000003 + 500009 + self.rank)
+        # the averaged generator is copied while the live parameters are still plain tensors (FlatAdam re-homes them next)
+        self.G_ema = copy.deepcopy(self.G) if ema is not None else None
         self.g_opt = FlatAdam(self.G.parameters(), lr=gen_lr, betas=(0.5, 0.999))
+        self.g_ema = FlatEMA(self.G, self.G_ema, self.g_opt, float(ema), ema_warmup) if ema is not None else None
         self.d_opts = [FlatAdam(d.parameters(), lr=disc_lr, betas=(0.5, 0.999)) for d in self.Ds]
         # the generator's 28 MB would be ONE 64 MB bucket, launched when its whole backward is done and fully exposed: it goes out in
         # 8 MB buckets instead, so all but the last travel under the ~10 ms of backward that remain
@@ -247,6 +261,8 @@ class GanTrainStep(ModelTrainer):
         # ---- generator update (train.py:132-151) ----
         self._g_backward(fw, word_embs, sent_embs, lengths, class_ids, out, streams, arm=True)
         self._apply("G", self.g_opt, self.g_buckets.finish())
+        if self.g_ema is not None:
+            self.g_ema.update()
         # loss histories stay device tensors: no .item() host sync inside the step (reference syncs at train.py:130,144-145)
         self.d_losses.append(out[f"d_loss{len(self.Ds) - 1}"])
         self.g_losses.append(out[f"g_loss{len(self.Ds) - 1}"])
@@ -374,7 +390,7 @@ class GanTrainStep(ModelTrainer):
             graph.register_generator_state(self.rng)       # noise / eps draws inside the graph advance this generator on replay
         with torch.cuda.graph(graph):
             out = self.step(word_embs, sent_embs, lengths, None, real_imgs, noise, eps, aug_u)
-        return GraphedStep(graph, out)
+        return GraphedStep(graph, out, self.g_ema)
 
     # -- segment-wise HIP graphs for world > 1 --------------------------------------------------------------------------
     def capture_segments(self, word_embs: Tensor, sent_embs: Tensor, lengths: Tensor, real_imgs: Sequence[Tensor], warmup: int = 2,
@@ -437,6 +453,8 @@ class GanTrainStep(ModelTrainer):
             gadam = torch.cuda.CUDAGraph()
             with torch.cuda.graph(gadam, pool=pool, capture_error_mode=mode):
                 self.g_opt.step(self.g_buckets.scale)
+                if self.g_ema is not None:
+                    self.g_ema.update()
             seg.g_backward, seg.g_adam = gg, gadam
             seg.out = self._results(fw, out)
         finally:
@@ -462,9 +480,17 @@ class GanTrainStep(ModelTrainer):
         sd = {"generator": self.G.state_dict(), "discriminators": [d.state_dict() for d in self.Ds],
               "g_optim": self.g_opt.state_dict(), "d_optims": [o.state_dict() for o in self.d_opts],
               "rng": {self.rank: mine["rng"]}, "sample_rng": {self.rank: mine["sample_rng"]}, "rng_world": w}
+        averaged = list(zip([self.G] + self.Ds, [sd["generator"]] + sd["discriminators"]))
+        if self.g_ema is not None:
+            # the averaged generator (its parameters are identical on every rank by construction, its running statistics per replica
+            # like the live ones) and the average's configuration and update count
+            e = self.g_ema.state_dict()
+            sd["generator_ema"] = e.pop("shadow")
+            sd["ema"] = e
+            averaged.append((self.G_ema, sd["generator_ema"]))
         if all_ranks and w > 1:
             import torch.distributed as dist
-            for m, msd in zip([self.G] + self.Ds, [sd["generator"]] + sd["discriminators"]):
+            for m, msd in averaged:
                 for k, v in averaged_buffers(m, self.group).items():
                     msd[k] = v
             gathered = [None] * w
@@ -495,8 +521,19 @@ class GanTrainStep(ModelTrainer):
         gen.manual_seed(int.from_bytes(digest[:8], "little") & ((1 << 63) - 1))
 
     def load_state_dict(self, sd: Dict) -> None:
+        """A checkpoint without "generator_ema" / "ema" (written before the average existed, or by a run without `ema`) is accepted by
+        a trainer with `ema`: the average restarts as a copy of the loaded generator with an update count of 0.  decay and warm-up are
+        configuration: the constructor's values hold, a differing saved decay is logged."""
         self.G.load_state_dict(sd["generator"])
         self.g_opt.load_state_dict(sd["g_optim"])
+        if self.g_ema is not None:
+            if "generator_ema" in sd and "ema" in sd:
+                self.g_ema.load_state_dict({"shadow": sd["generator_ema"], "updates": sd["ema"]["updates"]})
+                if float(sd["ema"]["decay"]) != self.g_ema.decay:
+                    logging.getLogger(__name__).warning("GanTrainStep: the checkpoint's average was kept with decay %g, this run uses %g",
+                                                        float(sd["ema"]["decay"]), self.g_ema.decay)
+            else:
+                self.g_ema.copy_from_live()
         for d, o, ds, os_ in zip(self.Ds, self.d_opts, sd["discriminators"], sd["d_optims"]):
             d.load_state_dict(ds)
             o.load_state_dict(os_)
@@ -507,22 +544,34 @@ class GanTrainStep(ModelTrainer):
 
     @torch.no_grad()
     def generate_images(self, word_embs: Tensor, sent_embs: Tensor, lengths, noise: Optional[Tensor] = None,
-                        train_mode_bn: bool = False, eps: Optional[Tensor] = None) -> List[Tensor]:
+                        train_mode_bn: bool = False, eps: Optional[Tensor] = None, use_ema: bool = False) -> List[Tensor]:
         """Sampling path; images mapped from [-1,1] to [0,1].  Same kernels as training, forward only.
 
         train_mode_bn=False (default): test.py:77-87 -- eval-mode generator (running BatchNorm statistics).
         train_mode_bn=True: the EPOCH-END sample exactly as train.py:154-158 takes it -- under no_grad but WITHOUT .eval(): every
         BatchNorm normalises with the statistics of this batch and pushes them into its running statistics (one more update per
-        epoch, which the next checkpoint carries), `noise` is the fixed input of train.py:105."""
+        epoch, which the next checkpoint carries), `noise` is the fixed input of train.py:105.
+        use_ema=True samples the averaged generator (`ema` at construction); it never runs batch statistics."""
+        G = self._sampled_generator(use_ema, train_mode_bn)
         mask = self._make_mask(lengths, word_embs.shape[2])
-        return self._denormalise_multiple(sample_fakes(self.G, word_embs, sent_embs, mask, self.sample_rng, noise, eps, train_mode_bn))
+        return self._denormalise_multiple(sample_fakes(G, word_embs, sent_embs, mask, self.sample_rng, noise, eps, train_mode_bn))
 
-    def evaluate(self, batches, text_encoder: Callable, real, n_samples: int, **kwargs) -> Dict:
+    def _sampled_generator(self, use_ema: bool, train_mode_bn: bool = False) -> Module:
+        if not use_ema:
+            return self.G
+        if self.g_ema is None:
+            raise ValueError("use_ema=True needs a GanTrainStep built with ema=<decay>")
+        if train_mode_bn:
+            raise ValueError("use_ema=True cannot be combined with train_mode_bn=True: the averaged generator never runs batch statistics")
+        return self.G_ema
+
+    def evaluate(self, batches, text_encoder: Callable, real, n_samples: int, use_ema: bool = False, **kwargs) -> Dict:
         """R-precision and Frechet distance of this step's generator under its own image encoder (evaluation.Evaluator.evaluate:
-        `real` is a FeatureMoments of real images, e.g. from Evaluator.real_moments; kwargs: R, seed, batch_size, folds)."""
+        `real` is a FeatureMoments of real images, e.g. from Evaluator.real_moments; kwargs: R, seed, batch_size, folds); of the
+        averaged generator with use_ema=True."""
         from ..evaluation import Evaluator
         dev = next(self.G.parameters()).device
-        return Evaluator(self.G, text_encoder, self.image_encoder, dev).evaluate(batches, real, n_samples, **kwargs)
+        return Evaluator(self._sampled_generator(use_ema), text_encoder, self.image_encoder, dev).evaluate(batches, real, n_samples, **kwargs)
 
     # -- the loop around the step (train.py:107-158) -------------------------------------------------------------------
     def skip_batch(self, lengths, batch_rows: int, batch_size: int) -> bool:
@@ -578,11 +627,13 @@ def sample_fakes(G: Module, word_embs: Tensor, sent_embs: Tensor, mask: Tensor, 
 class GraphedStep:
     """A captured train step: `replay()` runs it; `out` holds the static result tensors (losses, fake images)."""
 
-    def __init__(self, graph, out: Dict[str, Tensor]):
-        self.graph, self.out = graph, out
+    def __init__(self, graph, out: Dict[str, Tensor], ema: Optional[FlatEMA] = None):
+        self.graph, self.out, self.ema = graph, out, ema
 
     def replay(self) -> Dict[str, Tensor]:
         self.graph.replay()
+        if self.ema is not None:
+            self.ema.mark_updated()                        # the averaged generator re-packs its weights at its next use
         return self.out
 
 
@@ -612,6 +663,8 @@ class SegmentedStep:
         self.g_backward.replay()
         t.g_buckets.exchange_all()
         self.g_adam.replay()
+        if t.g_ema is not None:
+            t.g_ema.mark_updated()
         return self.out
 
 

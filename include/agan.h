@@ -668,6 +668,32 @@ int agan_diffaug_fwd(const float* x0 /* [n0, C, H, W] */, const float* x1 /* [n1
 int agan_diffaug_bwd(const float* dy /* [N, C, H, W] */, const float* u /* [N, 8] */, int policy, float* dx /* [N, C, H, W] */, int N, int C,
                      int H, int W, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Exponential moving average of a module's weights (csrc/ema.hip; optim.py: FlatEMA; backend/functional.py: ema_update_, ema_reference).
+ * One call updates every segment of a DEVICE-resident table:  dst[i] = fma(omb, src[i] - dst[i], dst[i])  in fp32, src only read.
+ * Segment i owns workgroups [first_block, next segment's first_block); the last one runs to total_blocks.  A segment moves 16 bytes per
+ * lane where BOTH its pointers are 16-byte aligned (plus a dword tail of n % 4 elements) and one dword per lane otherwise; no float outside
+ * [dst, dst + n) is read or written.  src and dst of a segment must not overlap; destinations of different segments must not overlap.
+ *
+ * agan_ema_plan works on a HOST copy of the table: it checks every segment (both pointers set and 4-byte aligned, n >= 1), fills
+ * first_block and returns the launch's total_blocks (> 0), or AGAN_EINVAL with a message.  The caller copies the planned table to the device.
+ *
+ * state: 16 bytes of device memory owned by the caller ([0] = int32 count of updates so far, advanced by the call; [2] = the fp32 factor
+ * the call derives).  A one-thread kernel in front of the update reads t = state[0], forms in double
+ *     beta_t = warmup ? min(decay, (1 + t) / (10 + t)) : decay
+ * and stores omb = (float)(1 - beta_t): a young average follows the weights closely (beta_0 = 0.1) and settles at `decay`.  No other
+ * host-side scalar enters the launch, so a captured HIP graph keeps counting on replay.  Plain loads and stores, no atomics:
+ * run-to-run identical.  AGAN_EINVAL before any launch for a null pointer, nseg < 1, total_blocks < nseg or decay outside (0, 1).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct agan_ema_seg {
+    const float* src;
+    float* dst;
+    int64_t n;
+    int32_t first_block, reserved;
+} agan_ema_seg;
+int agan_ema_plan(agan_ema_seg* segs /* HOST, nseg entries */, int nseg);
+int agan_ema_update(const agan_ema_seg* table /* DEVICE */, int nseg, int total_blocks, int32_t* state, double decay, int warmup, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
