@@ -2,10 +2,7 @@
 // HBM-bound streaming kernels over NCHW fp32: lanes run along the contiguous pixel axis with 16-B accesses; the
 // per-channel reductions accumulate in fp64 per thread (the kernels are bandwidth-bound, the DP adds are free)
 // so that var = E[x^2] - mean^2 does not cancel.
-#include "agan_common.h"
-
-#include <algorithm>
-#include <type_traits>
+#include "bn_common.h"
 
 using namespace agan;
 
@@ -107,16 +104,7 @@ __global__ __launch_bounds__(256) void bn_stats_final_kernel(const double* __res
         s += part[((size_t)c * nchunk + k) * 2 + 0];
         q += part[((size_t)c * nchunk + k) * 2 + 1];
     }
-    const double m = s / n;
-    double var = q / n - m * m;
-    if (var < 0.0) var = 0.0;
-    mean[c] = (float)m;
-    invstd[c] = (float)(1.0 / sqrt(var + (double)eps));
-    if (rmean) {
-        const double unbiased = n > 1 ? var * ((double)n / (n - 1)) : var;
-        rmean[c] = (float)((1.0 - momentum) * rmean[c] + momentum * m);
-        rvar[c] = (float)((1.0 - momentum) * rvar[c] + momentum * unbiased);
-    }
+    bn_finish_channel(s, q, n, eps, momentum, c, true, mean, invstd, rmean, rvar);
 }
 
 // HW == 1 (BatchNorm1d on [B, C], generator_submodules.py:38): one thread per channel, coalesced across channels
@@ -133,23 +121,7 @@ __global__ __launch_bounds__(256) void bn_stats_rows_kernel(const float* __restr
         s += v;
         q += (double)v * v;
     }
-    const double m = s / B;
-    double var = q / B - m * m;
-    if (var < 0.0) var = 0.0;
-    mean[c] = (float)m;
-    invstd[c] = (float)(1.0 / sqrt(var + (double)eps));
-    if (rmean) {
-        const double unbiased = B > 1 ? var * ((double)B / (B - 1)) : var;
-        rmean[c] = (float)((1.0 - momentum) * rmean[c] + momentum * m);
-        rvar[c] = (float)((1.0 - momentum) * rvar[c] + momentum * unbiased);
-    }
-}
-
-int stats_chunks(int B, int C, int HW) {
-    const int n = B * HW;
-    int nchunk = std::max(1, 2048 / std::max(C, 1));
-    nchunk = std::min(nchunk, std::max(1, n / 2048));
-    return nchunk;
+    bn_finish_channel(s, q, B, eps, momentum, c, true, mean, invstd, rmean, rvar);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -430,22 +402,7 @@ __global__ __launch_bounds__(256) void glu_bwd_kernel(const float* __restrict__ 
 // small tensors (B*HW <= kSmallN per channel: the 4x4 / 8x8 / 16x16 layers): statistics + normalise + activation in ONE launch,
 // one workgroup per (output) channel with the channel's values held in registers between the two phases
 // ---------------------------------------------------------------------------------------------------------
-constexpr int kSmallN = 8192;
-constexpr int kSmallPer = kSmallN / 256;
-
-__device__ __forceinline__ void block_sum2_d(double& a, double& b, double (*red)[4]) {
-    a = wave_sum_d(a);
-    b = wave_sum_d(b);
-    const int w = threadIdx.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) { red[0][w] = a; red[1][w] = b; }
-    __syncthreads();
-    a = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-    b = red[1][0] + red[1][1] + red[1][2] + red[1][3];
-}
-
-// PER = values a thread holds per half (round 4): 32 covers kSmallN; the 4x4 / 8x8 maps (n <= 512 / 2048) take PER = 2 / 8 -- the 32-deep
-// form spent most of its ~11 us on 30 dead, fully unrolled iterations (an integer division and four predicated loads each)
+// PER = values a thread holds per half (bn_common.h: with_per)
 template <int ACT, int XDT, int ODT, int PER = kSmallPer>
 __global__ __launch_bounds__(256) void bn_small_fwd_kernel(const void* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta,
                                                            const void* __restrict__ res, void* __restrict__ out, float* __restrict__ mean,
@@ -477,40 +434,15 @@ __global__ __launch_bounds__(256) void bn_small_fwd_kernel(const void* __restric
             }
         }
     }
-    block_sum2_d(s, q, red);
-    const double m = s / n;
-    double var = q / n - m * m;
-    var = var < 0.0 ? 0.0 : var;
-    const float is = (float)(1.0 / sqrt(var + (double)eps));
-    float mgf = 0.f, isg = 0.f;
-    double mg = 0.0, varg = 0.0;
+    block_sum2(s, q, red);
+    const BnStats sa = bn_finish_channel(s, q, n, eps, momentum, c, threadIdx.x == 0, mean, invstd, rmean, rvar);
+    const Affine a = make_affine(sa.mean, sa.invstd, gamma[c], beta[c]);
+    Affine g = a;
     if (GLU) {
-        block_sum2_d(sg, qg, red);
-        mg = sg / n;
-        varg = qg / n - mg * mg;
-        varg = varg < 0.0 ? 0.0 : varg;
-        mgf = (float)mg;
-        isg = (float)(1.0 / sqrt(varg + (double)eps));
+        block_sum2(sg, qg, red);
+        const BnStats sb = bn_finish_channel(sg, qg, n, eps, momentum, c + Co, threadIdx.x == 0, mean, invstd, rmean, rvar);
+        g = make_affine(sb.mean, sb.invstd, gamma[c + Co], beta[c + Co]);
     }
-    if (threadIdx.x == 0) {
-        const double ub = n > 1 ? (double)n / (n - 1) : 1.0;
-        mean[c] = (float)m;
-        invstd[c] = is;
-        if (rmean) {
-            rmean[c] = (float)((1.0 - momentum) * rmean[c] + momentum * m);
-            rvar[c] = (float)((1.0 - momentum) * rvar[c] + momentum * var * ub);
-        }
-        if (GLU) {
-            mean[c + Co] = mgf;
-            invstd[c + Co] = isg;
-            if (rmean) {
-                rmean[c + Co] = (float)((1.0 - momentum) * rmean[c + Co] + momentum * mg);
-                rvar[c + Co] = (float)((1.0 - momentum) * rvar[c + Co] + momentum * varg * ub);
-            }
-        }
-    }
-    const Affine a = make_affine((float)m, is, gamma[c], beta[c]);
-    const Affine g = GLU ? make_affine(mgf, isg, gamma[c + Co], beta[c + Co]) : a;
     float mx = 0.f;
 #pragma unroll
     for (int j = 0; j < PER; ++j) {
@@ -569,8 +501,8 @@ __global__ __launch_bounds__(256) void bn_small_bwd_kernel(const void* __restric
             }
         }
     }
-    block_sum2_d(s0, s1, red);
-    if (GLU) block_sum2_d(s2, s3, red);
+    block_sum2(s0, s1, red);
+    if (GLU) block_sum2(s2, s3, red);
     if (threadIdx.x == 0) {
         dbeta[c] = accumulate ? dbeta[c] + (float)s0 : (float)s0;
         dgamma[c] = accumulate ? dgamma[c] + (float)s1 : (float)s1;
@@ -602,26 +534,81 @@ __global__ __launch_bounds__(256) void bn_small_bwd_kernel(const void* __restric
 
 int ew_blocks(size_t work) { return (int)std::max<size_t>(1, std::min<size_t>(cdivz(work, 256), 256 * 8)); }
 
-}  // namespace
-
-// storage-type combinations the BatchNorm kernels are built for: (x / dx, out / dout / residual)
-#define AGAN_BN_DT(XD, OD, CALL)                                                                                  \
-    do {                                                                                                          \
-        if ((XD) == AGAN_DT_F32 && (OD) == AGAN_DT_F32) { CALL(AGAN_DT_F32, AGAN_DT_F32); }                       \
-        else if ((XD) == AGAN_DT_BF16 && (OD) == AGAN_DT_BF16) { CALL(AGAN_DT_BF16, AGAN_DT_BF16); }              \
-        else if ((XD) == AGAN_DT_F32 && (OD) == AGAN_DT_BF16) { CALL(AGAN_DT_F32, AGAN_DT_BF16); }                \
-        else if ((XD) == AGAN_DT_F16 && (OD) == AGAN_DT_F16) { CALL(AGAN_DT_F16, AGAN_DT_F16); }                  \
-        else { CALL(AGAN_DT_F32, AGAN_DT_F16); }                                                                  \
-    } while (0)
-static bool bn_dt_ok(int xd, int od) {
-    return (xd == AGAN_DT_F32 && (od == AGAN_DT_F32 || od == AGAN_DT_BF16 || od == AGAN_DT_F16)) || (xd == od && (xd == AGAN_DT_BF16 || xd == AGAN_DT_F16));
+// ---------------------------------------------------------------------------------------------------------
+// host: run-time values -> the kernel form.  Each helper calls f with Int<> tags; the launch sites are generic lambdas over them.
+// ---------------------------------------------------------------------------------------------------------
+// The storage-type pairs the BatchNorm kernels are built for, (x / dx, out / dout / residual): f(Int<XDT>, Int<ODT>) for the pair
+// (xd, od); false, and no call, if it is none of them.  This list is the only one.
+template <class F> bool bn_pair(int xd, int od, F&& f) {
+    auto is = [&](auto XD, auto OD) { return xd == XD() && od == OD() && (f(XD, OD), true); };
+    return is(Int<AGAN_DT_F32>{}, Int<AGAN_DT_F32>{}) || is(Int<AGAN_DT_BF16>{}, Int<AGAN_DT_BF16>{}) ||
+           is(Int<AGAN_DT_F32>{}, Int<AGAN_DT_BF16>{}) || is(Int<AGAN_DT_F16>{}, Int<AGAN_DT_F16>{}) ||
+           is(Int<AGAN_DT_F32>{}, Int<AGAN_DT_F16>{});
 }
-static const void* off(const void* p, size_t elems, int dt) { return static_cast<const char*>(p) + elems * dt_size(dt); }
-static void* off(void* p, size_t elems, int dt) { return static_cast<char*>(p) + elems * dt_size(dt); }
+bool bn_dt_ok(int xd, int od) { return bn_pair(xd, od, [](auto, auto) {}); }
+
+// f(Int<ACT>, Int<XDT>, Int<ODT>): the three BatchNorm activations x the pairs of bn_pair (check_bn_args has admitted act, xd and od)
+template <class F> void bn_variant(int act, int xd, int od, F&& f) {
+    bn_pair(xd, od, [&](auto XD, auto OD) {
+        if (act == AGAN_ACT_GLU) f(Int<AGAN_ACT_GLU>{}, XD, OD);
+        else if (act == AGAN_ACT_LRELU) f(Int<AGAN_ACT_LRELU>{}, XD, OD);
+        else f(Int<AGAN_ACT_NONE>{}, XD, OD);
+    });
+}
+// f(Int<V>) for the sweep width vw = vec_width(ANY16, HW); V = 8 is built only where a 16-bit tensor is involved (vw is 8 only there)
+template <bool ANY16, class F> void with_width(int vw, F&& f) {
+    if (vw == 8) { if constexpr (ANY16) f(Int<8>{}); }
+    else if (vw == 4) f(Int<4>{});
+    else f(Int<1>{});
+}
+// f(Int<DT>) for one storage type (the caller has checked it)
+template <class F> void with_dt(int dt, F&& f) {
+    if (dt == AGAN_DT_F32) f(Int<AGAN_DT_F32>{});
+    else if (dt == AGAN_DT_BF16) f(Int<AGAN_DT_BF16>{});
+    else f(Int<AGAN_DT_F16>{});
+}
+// f(Int<ACT>) for an activation of agan_act_fwd / agan_act_bwd; false, and no call, for any other
+template <class F> bool bare_act(int act, F&& f) {
+    if (act == AGAN_ACT_LRELU) f(Int<AGAN_ACT_LRELU>{});
+    else if (act == AGAN_ACT_TANH) f(Int<AGAN_ACT_TANH>{});
+    else if (act == AGAN_ACT_SIGMOID) f(Int<AGAN_ACT_SIGMOID>{});
+    else return false;
+    return true;
+}
+
+const void* off(const void* p, size_t elems, int dt) { return static_cast<const char*>(p) + elems * dt_size(dt); }
+void* off(void* p, size_t elems, int dt) { return static_cast<char*>(p) + elems * dt_size(dt); }
+
+// Group gi of `groups` consecutive sub-batches of Bg samples with their own statistics: its part of each tensor.
+struct BnGroup {
+    size_t xe, oe, se;      // element offsets into x-shaped tensors, out-shaped tensors and the [groups, C] statistics
+    int xdt, odt;
+    int acc;                // group 0 writes (or adds to, as the caller asked) the gamma / beta gradients, the others add
+    template <class P> P x(P p) const { return off(p, xe, xdt); }              // x, dx
+    template <class P> P o(P p) const { return p ? off(p, oe, odt) : p; }      // out, dout, residual (which may be null)
+    template <class P> P stat(P p) const { return p + se; }                    // mean, invstd
+};
+BnGroup bn_group(int gi, int Bg, int C, int Co, int HW, int xdt, int odt, int accumulate = 0) {
+    return {(size_t)gi * Bg * C * HW, (size_t)gi * Bg * Co * HW, (size_t)gi * C, xdt, odt, gi == 0 ? accumulate : 1};
+}
+
+// What agan_bn_train_fwd_dt, bn_act_fwd_impl and agan_bn_act_bwd_dt require, in one order.  An entry point without a residual,
+// running statistics or groups passes false, true and 1 group.
+int check_bn_args(const char* who, bool present, const char* absent, int act, int C, bool residual, bool running_paired, int B,
+                  int groups, int xd, int od) {
+    AGAN_REQUIRE(present, "%s: %s", who, absent);
+    AGAN_REQUIRE(act == AGAN_ACT_NONE || act == AGAN_ACT_GLU || act == AGAN_ACT_LRELU, "%s: activation %d", who, act);
+    AGAN_REQUIRE(act != AGAN_ACT_GLU || (C % 2 == 0), "channels dont divide 2!");
+    AGAN_REQUIRE(!(residual && act != AGAN_ACT_NONE), "%s: residual only with ACT_NONE", who);
+    AGAN_REQUIRE(running_paired, "%s: running_mean/var must come together", who);
+    AGAN_REQUIRE(groups >= 1 && B % groups == 0, "%s: batch %d does not split into %d groups", who, B, groups);
+    AGAN_REQUIRE(bn_dt_ok(xd, od), "%s: storage types %d -> %d", who, xd, od);
+    return AGAN_OK;
+}
 
 // (bodies of agan_bn_stats_dt / agan_bn_act_fwd_dt without the launch-log reset: agan_bn_train_fwd_dt calls them per group)
-static int bn_stats_impl(const void* x, int B, int C, int HW, float eps, float* mean, float* invstd, float* running_mean,
-                         float* running_var, int64_t* nbt, float momentum, void* ws, size_t ws_bytes, void* stream, int x_dtype) {
+int bn_stats_impl(const void* x, int B, int C, int HW, float eps, float* mean, float* invstd, float* running_mean, float* running_var,
+                  int64_t* nbt, float momentum, void* ws, size_t ws_bytes, void* stream, int x_dtype) {
     AGAN_REQUIRE(x && mean && invstd && B > 0 && C > 0 && HW > 0, "bn_stats: bad argument");
     AGAN_REQUIRE((running_mean == nullptr) == (running_var == nullptr), "bn_stats: running_mean/var must come together");
     AGAN_REQUIRE(x_dtype == AGAN_DT_F32 || x_dtype == AGAN_DT_BF16 || x_dtype == AGAN_DT_F16, "bn_stats: storage type %d", x_dtype);
@@ -633,58 +620,48 @@ static int bn_stats_impl(const void* x, int B, int C, int HW, float eps, float* 
                            running_mean, running_var, nbt, momentum);
         return check_launch("bn_stats_rows");
     }
-    const int nchunk = stats_chunks(B, C, HW);
+    const int nchunk = bn_chunks(B, C, HW);
     if (ws_bytes < agan_bn_stats_ws_bytes(B, C, HW) || !ws) {
         set_error("bn_stats: workspace too small");
         return AGAN_EWORKSPACE;
     }
     double* part = static_cast<double*>(ws);
     log_launch(kLogStatsPartial, 0, x_dtype, x_dtype, vec_width(x_dtype != AGAN_DT_F32, HW));
-    if (x_dtype == AGAN_DT_F32) hipLaunchKernelGGL(bn_stats_partial_kernel<AGAN_DT_F32>, dim3(C, nchunk), dim3(256), 0, st, x, B, C, HW, nchunk, part);
-    else if (x_dtype == AGAN_DT_BF16) hipLaunchKernelGGL(bn_stats_partial_kernel<AGAN_DT_BF16>, dim3(C, nchunk), dim3(256), 0, st, x, B, C, HW, nchunk, part);
-    else hipLaunchKernelGGL(bn_stats_partial_kernel<AGAN_DT_F16>, dim3(C, nchunk), dim3(256), 0, st, x, B, C, HW, nchunk, part);
+    with_dt(x_dtype, [&](auto XD) {
+        hipLaunchKernelGGL(bn_stats_partial_kernel<XD()>, dim3(C, nchunk), dim3(256), 0, st, x, B, C, HW, nchunk, part);
+    });
     log_launch(kLogStatsFinal, 0, x_dtype, x_dtype, 1);
     hipLaunchKernelGGL(bn_stats_final_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, part, C, nchunk, B * HW, eps, mean, invstd,
                        running_mean, running_var, nbt, momentum);
     return check_launch("bn_stats");
 }
 
-static int bn_act_fwd_impl(const void* x, const float* mean, const float* invstd, const float* gamma, const float* beta,
-                           const void* residual, void* out, int B, int C, int HW, int act, void* stream, float* out_amax, int x_dtype,
-                           int out_dtype) {
-    AGAN_REQUIRE(x && mean && invstd && gamma && beta && out && B > 0 && C > 0 && HW > 0, "bn_act_fwd: bad argument");
-    AGAN_REQUIRE(act == AGAN_ACT_NONE || act == AGAN_ACT_GLU || act == AGAN_ACT_LRELU, "bn_act_fwd: activation %d", act);
-    AGAN_REQUIRE(act != AGAN_ACT_GLU || (C % 2 == 0), "channels dont divide 2!");
-    AGAN_REQUIRE(!(residual && act != AGAN_ACT_NONE), "bn_act_fwd: residual only with ACT_NONE");
-    AGAN_REQUIRE(bn_dt_ok(x_dtype, out_dtype), "bn_act_fwd: storage types %d -> %d", x_dtype, out_dtype);
+int bn_act_fwd_impl(const void* x, const float* mean, const float* invstd, const float* gamma, const float* beta, const void* residual,
+                    void* out, int B, int C, int HW, int act, void* stream, float* out_amax, int x_dtype, int out_dtype) {
+    if (int e = check_bn_args("bn_act_fwd", x && mean && invstd && gamma && beta && out && B > 0 && C > 0 && HW > 0, "bad argument", act, C,
+                              residual != nullptr, true, B, 1, x_dtype, out_dtype))
+        return e;
     hipStream_t st = as_stream(stream);
-    // elements per thread and iteration: 8 where a 16-bit tensor is involved and rows are whole 8-groups (16-byte accesses on it), else 4 / 1
     const int vw = vec_width(x_dtype != AGAN_DT_F32 || out_dtype != AGAN_DT_F32, HW);
     const int Co = act == AGAN_ACT_GLU ? C / 2 : C;
     const int blocks = ew_blocks((size_t)B * Co * HW / vw);
-#define AGAN_L(A, V, XD, OD) do { log_launch(kLogFwdApply, A, XD, OD, V); hipLaunchKernelGGL((bn_act_fwd_kernel<A, V, XD, OD>), dim3(blocks), dim3(256), 0, st, x, mean, invstd, gamma, beta, residual, out, B, C, HW, out_amax); } while (0)
-#define AGAN_V(A, XD, OD)                                                                                           \
-    do {                                                                                                            \
-        if (vw == 8) { if constexpr ((XD) != AGAN_DT_F32 || (OD) != AGAN_DT_F32) AGAN_L(A, 8, XD, OD); }             \
-        else if (vw == 4) AGAN_L(A, 4, XD, OD);                                                                     \
-        else AGAN_L(A, 1, XD, OD);                                                                                  \
-    } while (0)
-#define AGAN_C(XD, OD)                                                  \
-    if (act == AGAN_ACT_GLU) AGAN_V(AGAN_ACT_GLU, XD, OD);              \
-    else if (act == AGAN_ACT_LRELU) AGAN_V(AGAN_ACT_LRELU, XD, OD);     \
-    else AGAN_V(AGAN_ACT_NONE, XD, OD);
-    AGAN_BN_DT(x_dtype, out_dtype, AGAN_C);
-#undef AGAN_C
-#undef AGAN_V
-#undef AGAN_L
+    bn_variant(act, x_dtype, out_dtype, [&](auto A, auto XD, auto OD) {
+        with_width<XD() != AGAN_DT_F32 || OD() != AGAN_DT_F32>(vw, [&](auto V) {
+            log_launch(kLogFwdApply, A(), XD(), OD(), V());
+            hipLaunchKernelGGL((bn_act_fwd_kernel<A(), V(), XD(), OD()>), dim3(blocks), dim3(256), 0, st, x, mean, invstd, gamma, beta,
+                               residual, out, B, C, HW, out_amax);
+        });
+    });
     return check_launch("bn_act_fwd");
 }
+
+}  // namespace
 
 extern "C" {
 
 size_t agan_bn_stats_ws_bytes(int B, int C, int HW) {
     if (HW == 1) return 0;
-    return (size_t)C * stats_chunks(B, C, HW) * 2 * sizeof(double);
+    return (size_t)C * bn_chunks(B, C, HW) * 2 * sizeof(double);
 }
 
 int agan_bn_last_launch(int* codes, int capacity) {
@@ -714,21 +691,17 @@ int agan_bn_act_fwd(const float* x, const float* mean, const float* invstd, cons
     return agan_bn_act_fwd_dt(x, mean, invstd, gamma, beta, residual, out, B, C, HW, act, stream, out_amax, AGAN_DT_F32, AGAN_DT_F32);
 }
 
-static int bwd_chunks(int B, int C, int HW) { return stats_chunks(B, C, HW); }
-
 size_t agan_bn_act_bwd_ws_bytes(int B, int C, int HW) {
-    return (size_t)C * bwd_chunks(B, C, HW) * 4 * sizeof(double) + (size_t)C * 2 * sizeof(float) + 64;
+    return (size_t)C * bn_chunks(B, C, HW) * 4 * sizeof(double) + (size_t)C * 2 * sizeof(float) + 64;
 }
 
 int agan_bn_act_bwd_dt(const void* x, const void* dout, const float* mean, const float* invstd, const float* gamma,
                        const float* beta, void* dx, float* dgamma, float* dbeta, int B, int C, int HW, int act, int accumulate,
                        int groups, void* ws, size_t ws_bytes, void* stream, float* dx_amax, int x_dtype, int out_dtype) {
     log_reset();
-    AGAN_REQUIRE(x && dout && mean && invstd && gamma && beta && dx && dgamma && dbeta && ws, "bn_act_bwd: null pointer");
-    AGAN_REQUIRE(act == AGAN_ACT_NONE || act == AGAN_ACT_GLU || act == AGAN_ACT_LRELU, "bn_act_bwd: activation %d", act);
-    AGAN_REQUIRE(act != AGAN_ACT_GLU || (C % 2 == 0), "channels dont divide 2!");
-    AGAN_REQUIRE(groups >= 1 && B % groups == 0, "bn_act_bwd: batch %d does not split into %d groups", B, groups);
-    AGAN_REQUIRE(bn_dt_ok(x_dtype, out_dtype), "bn_act_bwd: storage types %d -> %d", x_dtype, out_dtype);
+    if (int e = check_bn_args("bn_act_bwd", x && dout && mean && invstd && gamma && beta && dx && dgamma && dbeta && ws, "null pointer", act,
+                              C, false, true, B, groups, x_dtype, out_dtype))
+        return e;
     const int Bg = B / groups;
     if (ws_bytes < agan_bn_act_bwd_ws_bytes(Bg, C, HW)) {
         set_error("bn_act_bwd: workspace too small");
@@ -739,61 +712,39 @@ int agan_bn_act_bwd_dt(const void* x, const void* dout, const float* mean, const
     const int Co = glu ? C / 2 : C;
     if (HW > 1 && (long long)Bg * HW <= kSmallN) {
         for (int gi = 0; gi < groups; ++gi) {      // (one launch per group: see agan_bn_train_fwd)
-            const void* xg = off(x, (size_t)gi * Bg * C * HW, x_dtype);
-            const void* dg = off(dout, (size_t)gi * Bg * Co * HW, out_dtype);
-            void* dxg = off(dx, (size_t)gi * Bg * C * HW, x_dtype);
-            const int acc = gi == 0 ? accumulate : 1;
-#define AGAN_LP(A, XD, OD, P) do { log_launch(kLogSmallBwd, A, XD, OD, P); hipLaunchKernelGGL((bn_small_bwd_kernel<A, XD, OD, P>), dim3(Co), dim3(256), 0, st, xg, dg, mean + (size_t)gi * C, invstd + (size_t)gi * C, gamma, beta, dxg, dgamma, dbeta, Bg, C, HW, acc, dx_amax); } while (0)
-#define AGAN_L(A, XD, OD) do { if (Bg * HW <= 512) AGAN_LP(A, XD, OD, 2); else if (Bg * HW <= 2048) AGAN_LP(A, XD, OD, 8); else AGAN_LP(A, XD, OD, kSmallPer); } while (0)
-#define AGAN_C(XD, OD)                                           \
-    if (act == AGAN_ACT_GLU) AGAN_L(AGAN_ACT_GLU, XD, OD);       \
-    else if (act == AGAN_ACT_LRELU) AGAN_L(AGAN_ACT_LRELU, XD, OD); \
-    else AGAN_L(AGAN_ACT_NONE, XD, OD);
-            AGAN_BN_DT(x_dtype, out_dtype, AGAN_C);
-#undef AGAN_C
-#undef AGAN_L
-#undef AGAN_LP
+            const BnGroup g = bn_group(gi, Bg, C, Co, HW, x_dtype, out_dtype, accumulate);
+            bn_variant(act, x_dtype, out_dtype, [&](auto A, auto XD, auto OD) {
+                with_per(Bg * HW, [&](auto P) {
+                    log_launch(kLogSmallBwd, A(), XD(), OD(), P());
+                    hipLaunchKernelGGL((bn_small_bwd_kernel<A(), XD(), OD(), P()>), dim3(Co), dim3(256), 0, st, g.x(x), g.o(dout),
+                                       g.stat(mean), g.stat(invstd), gamma, beta, g.x(dx), dgamma, dbeta, Bg, C, HW, g.acc, dx_amax);
+                });
+            });
         }
         return check_launch("bn_act_bwd/small");
     }
-    const int nchunk = bwd_chunks(Bg, C, HW);
+    const int nchunk = bn_chunks(Bg, C, HW);
     double* part = static_cast<double*>(ws);
     float* coef = reinterpret_cast<float*>(part + (size_t)C * nchunk * 4);
-    dim3 grid(Co, nchunk);
     const int vw = vec_width(x_dtype != AGAN_DT_F32 || out_dtype != AGAN_DT_F32, HW);      // (also the partial kernel's sweep width)
     const int blocks = ew_blocks((size_t)Bg * Co * HW / vw);
-    for (int gi = 0; gi < groups; ++gi) {      // group 0 writes (or adds to) the gamma/beta gradients, the others add
-        const void* xg = off(x, (size_t)gi * Bg * C * HW, x_dtype);
-        const void* dg = off(dout, (size_t)gi * Bg * Co * HW, out_dtype);
-        const float* mg = mean + (size_t)gi * C;
-        const float* ig = invstd + (size_t)gi * C;
-        void* dxg = off(dx, (size_t)gi * Bg * C * HW, x_dtype);
-        const int acc = gi == 0 ? accumulate : 1;
-#define AGAN_P(A, XD, OD) do { log_launch(kLogBwdPartial, A, XD, OD, vw); hipLaunchKernelGGL((bn_bwd_partial_kernel<A, XD, OD>), grid, dim3(256), 0, st, xg, dg, mg, ig, gamma, beta, Bg, C, HW, nchunk, part); } while (0)
-#define AGAN_C(XD, OD)                                           \
-    if (glu) AGAN_P(AGAN_ACT_GLU, XD, OD);                        \
-    else if (act == AGAN_ACT_LRELU) AGAN_P(AGAN_ACT_LRELU, XD, OD); \
-    else AGAN_P(AGAN_ACT_NONE, XD, OD);
-        AGAN_BN_DT(x_dtype, out_dtype, AGAN_C);
-#undef AGAN_C
-#undef AGAN_P
+    for (int gi = 0; gi < groups; ++gi) {
+        const BnGroup g = bn_group(gi, Bg, C, Co, HW, x_dtype, out_dtype, accumulate);
+        bn_variant(act, x_dtype, out_dtype, [&](auto A, auto XD, auto OD) {
+            log_launch(kLogBwdPartial, A(), XD(), OD(), vw);
+            hipLaunchKernelGGL((bn_bwd_partial_kernel<A(), XD(), OD()>), dim3(Co, nchunk), dim3(256), 0, st, g.x(x), g.o(dout), g.stat(mean),
+                               g.stat(invstd), gamma, beta, Bg, C, HW, nchunk, part);
+        });
         log_launch(kLogBwdFinal, act, x_dtype, out_dtype, 1);
-        hipLaunchKernelGGL(bn_bwd_final_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, part, C, Co, nchunk, Bg * HW, glu, dgamma, dbeta, coef, acc);
-#define AGAN_L(A, V, XD, OD) do { log_launch(kLogBwdApply, A, XD, OD, V); hipLaunchKernelGGL((bn_bwd_apply_kernel<A, V, XD, OD>), dim3(blocks), dim3(256), 0, st, xg, dg, mg, ig, gamma, beta, coef, dxg, Bg, C, HW, dx_amax); } while (0)
-#define AGAN_V(A, XD, OD)                                                                                           \
-    do {                                                                                                            \
-        if (vw == 8) { if constexpr ((XD) != AGAN_DT_F32 || (OD) != AGAN_DT_F32) AGAN_L(A, 8, XD, OD); }             \
-        else if (vw == 4) AGAN_L(A, 4, XD, OD);                                                                     \
-        else AGAN_L(A, 1, XD, OD);                                                                                  \
-    } while (0)
-#define AGAN_C(XD, OD)                                                  \
-    if (glu) AGAN_V(AGAN_ACT_GLU, XD, OD);                              \
-    else if (act == AGAN_ACT_LRELU) AGAN_V(AGAN_ACT_LRELU, XD, OD);     \
-    else AGAN_V(AGAN_ACT_NONE, XD, OD);
-        AGAN_BN_DT(x_dtype, out_dtype, AGAN_C);
-#undef AGAN_C
-#undef AGAN_V
-#undef AGAN_L
+        hipLaunchKernelGGL(bn_bwd_final_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, part, C, Co, nchunk, Bg * HW, glu, dgamma, dbeta, coef,
+                           g.acc);
+        bn_variant(act, x_dtype, out_dtype, [&](auto A, auto XD, auto OD) {
+            with_width<XD() != AGAN_DT_F32 || OD() != AGAN_DT_F32>(vw, [&](auto V) {
+                log_launch(kLogBwdApply, A(), XD(), OD(), V());
+                hipLaunchKernelGGL((bn_bwd_apply_kernel<A(), V(), XD(), OD()>), dim3(blocks), dim3(256), 0, st, g.x(x), g.o(dout),
+                                   g.stat(mean), g.stat(invstd), gamma, beta, coef, g.x(dx), Bg, C, HW, dx_amax);
+            });
+        });
     }
     return check_launch("bn_act_bwd");
 }
@@ -810,12 +761,8 @@ int agan_act_fwd(const float* x, float* out, size_t n, int act, void* stream) {
     hipStream_t st = as_stream(stream);
     log_launch(kLogActFwd, act, AGAN_DT_F32, AGAN_DT_F32, 4);
     const int blocks = ew_blocks(n / 4 + 1);
-    switch (act) {
-        case AGAN_ACT_LRELU: hipLaunchKernelGGL((act_fwd_kernel<AGAN_ACT_LRELU>), dim3(blocks), dim3(256), 0, st, x, out, n); break;
-        case AGAN_ACT_TANH: hipLaunchKernelGGL((act_fwd_kernel<AGAN_ACT_TANH>), dim3(blocks), dim3(256), 0, st, x, out, n); break;
-        case AGAN_ACT_SIGMOID: hipLaunchKernelGGL((act_fwd_kernel<AGAN_ACT_SIGMOID>), dim3(blocks), dim3(256), 0, st, x, out, n); break;
-        default: set_error("act_fwd: activation %d", act); return AGAN_EINVAL;
-    }
+    AGAN_REQUIRE(bare_act(act, [&](auto A) { hipLaunchKernelGGL(act_fwd_kernel<A()>, dim3(blocks), dim3(256), 0, st, x, out, n); }),
+                 "act_fwd: activation %d", act);
     return check_launch("act_fwd");
 }
 
@@ -825,12 +772,8 @@ int agan_act_bwd(const float* y, const float* dout, float* dx, size_t n, int act
     hipStream_t st = as_stream(stream);
     log_launch(kLogActBwd, act, AGAN_DT_F32, AGAN_DT_F32, 4);
     const int blocks = ew_blocks(n / 4 + 1);
-    switch (act) {
-        case AGAN_ACT_LRELU: hipLaunchKernelGGL((act_bwd_kernel<AGAN_ACT_LRELU>), dim3(blocks), dim3(256), 0, st, y, dout, dx, n); break;
-        case AGAN_ACT_TANH: hipLaunchKernelGGL((act_bwd_kernel<AGAN_ACT_TANH>), dim3(blocks), dim3(256), 0, st, y, dout, dx, n); break;
-        case AGAN_ACT_SIGMOID: hipLaunchKernelGGL((act_bwd_kernel<AGAN_ACT_SIGMOID>), dim3(blocks), dim3(256), 0, st, y, dout, dx, n); break;
-        default: set_error("act_bwd: activation %d", act); return AGAN_EINVAL;
-    }
+    AGAN_REQUIRE(bare_act(act, [&](auto A) { hipLaunchKernelGGL(act_bwd_kernel<A()>, dim3(blocks), dim3(256), 0, st, y, dout, dx, n); }),
+                 "act_bwd: activation %d", act);
     return check_launch("act_bwd");
 }
 
@@ -861,13 +804,9 @@ int agan_bn_train_fwd_dt(const void* x, const float* gamma, const float* beta, c
                          float momentum, int act, int groups, void* ws, size_t ws_bytes, void* stream, float* out_amax, int x_dtype,
                          int out_dtype) {
     log_reset();
-    AGAN_REQUIRE(x && gamma && beta && out && mean && invstd && B > 0 && C > 0 && HW > 0, "bn_train_fwd: bad argument");
-    AGAN_REQUIRE(act == AGAN_ACT_NONE || act == AGAN_ACT_GLU || act == AGAN_ACT_LRELU, "bn_train_fwd: activation %d", act);
-    AGAN_REQUIRE(act != AGAN_ACT_GLU || (C % 2 == 0), "channels dont divide 2!");
-    AGAN_REQUIRE(!(residual && act != AGAN_ACT_NONE), "bn_train_fwd: residual only with ACT_NONE");
-    AGAN_REQUIRE((running_mean == nullptr) == (running_var == nullptr), "bn_train_fwd: running_mean/var must come together");
-    AGAN_REQUIRE(groups >= 1 && B % groups == 0, "bn_train_fwd: batch %d does not split into %d groups", B, groups);
-    AGAN_REQUIRE(bn_dt_ok(x_dtype, out_dtype), "bn_train_fwd: storage types %d -> %d", x_dtype, out_dtype);
+    if (int e = check_bn_args("bn_train_fwd", x && gamma && beta && out && mean && invstd && B > 0 && C > 0 && HW > 0, "bad argument", act, C,
+                              residual != nullptr, (running_mean == nullptr) == (running_var == nullptr), B, groups, x_dtype, out_dtype))
+        return e;
     const int Bg = B / groups;
     const int Co = act == AGAN_ACT_GLU ? C / 2 : C;
     if (HW > 1 && (long long)Bg * HW <= kSmallN) {
@@ -875,31 +814,25 @@ int agan_bn_train_fwd_dt(const void* x, const float* gamma, const float* beta, c
         // are latency-bound; two short ones overlap tail to head)
         hipStream_t st = as_stream(stream);
         for (int gi = 0; gi < groups; ++gi) {
-            const void* xg = off(x, (size_t)gi * Bg * C * HW, x_dtype);
-            const void* rg = residual ? off(residual, (size_t)gi * Bg * Co * HW, out_dtype) : nullptr;
-            void* og = off(out, (size_t)gi * Bg * Co * HW, out_dtype);
-            float* mg = mean + (size_t)gi * C;
-            float* ig = invstd + (size_t)gi * C;
-#define AGAN_LP(A, XD, OD, P) do { log_launch(kLogSmallFwd, A, XD, OD, P); hipLaunchKernelGGL((bn_small_fwd_kernel<A, XD, OD, P>), dim3(Co), dim3(256), 0, st, xg, gamma, beta, rg, og, mg, ig, running_mean, running_var, nbt, Bg, C, HW, eps, momentum, out_amax); } while (0)
-#define AGAN_L(A, XD, OD) do { if (Bg * HW <= 512) AGAN_LP(A, XD, OD, 2); else if (Bg * HW <= 2048) AGAN_LP(A, XD, OD, 8); else AGAN_LP(A, XD, OD, kSmallPer); } while (0)
-#define AGAN_C(XD, OD)                                           \
-    if (act == AGAN_ACT_GLU) AGAN_L(AGAN_ACT_GLU, XD, OD);       \
-    else if (act == AGAN_ACT_LRELU) AGAN_L(AGAN_ACT_LRELU, XD, OD); \
-    else AGAN_L(AGAN_ACT_NONE, XD, OD);
-            AGAN_BN_DT(x_dtype, out_dtype, AGAN_C);
-#undef AGAN_C
-#undef AGAN_L
-#undef AGAN_LP
+            const BnGroup g = bn_group(gi, Bg, C, Co, HW, x_dtype, out_dtype);
+            bn_variant(act, x_dtype, out_dtype, [&](auto A, auto XD, auto OD) {
+                with_per(Bg * HW, [&](auto P) {
+                    log_launch(kLogSmallFwd, A(), XD(), OD(), P());
+                    hipLaunchKernelGGL((bn_small_fwd_kernel<A(), XD(), OD(), P()>), dim3(Co), dim3(256), 0, st, g.x(x), gamma, beta,
+                                       g.o(residual), g.o(out), g.stat(mean), g.stat(invstd), running_mean, running_var, nbt, Bg, C, HW, eps,
+                                       momentum, out_amax);
+                });
+            });
         }
         return check_launch("bn_train_fwd/small");
     }
     for (int gi = 0; gi < groups; ++gi) {      // same stream: statistics, running-stat update and apply in group order
-        const void* xg = off(x, (size_t)gi * Bg * C * HW, x_dtype);
-        float* mg = mean + (size_t)gi * C;
-        float* ig = invstd + (size_t)gi * C;
-        if (int e = bn_stats_impl(xg, Bg, C, HW, eps, mg, ig, running_mean, running_var, nbt, momentum, ws, ws_bytes, stream, x_dtype)) return e;
-        if (int e = bn_act_fwd_impl(xg, mg, ig, gamma, beta, residual ? off(residual, (size_t)gi * Bg * Co * HW, out_dtype) : nullptr,
-                                       off(out, (size_t)gi * Bg * Co * HW, out_dtype), Bg, C, HW, act, stream, out_amax, x_dtype, out_dtype))
+        const BnGroup g = bn_group(gi, Bg, C, Co, HW, x_dtype, out_dtype);
+        if (int e = bn_stats_impl(g.x(x), Bg, C, HW, eps, g.stat(mean), g.stat(invstd), running_mean, running_var, nbt, momentum, ws, ws_bytes,
+                                  stream, x_dtype))
+            return e;
+        if (int e = bn_act_fwd_impl(g.x(x), g.stat(mean), g.stat(invstd), gamma, beta, g.o(residual), g.o(out), Bg, C, HW, act, stream,
+                                    out_amax, x_dtype, out_dtype))
             return e;
     }
     return AGAN_OK;

@@ -7,27 +7,11 @@
 // Two size regimes, as in bn_act.hip: n = B*HW <= kSmallN (the 17x17 and 8x8 layers at B = 24) is ONE launch, a workgroup per channel
 // holding the channel's values in registers between the statistics and the apply; larger channels are agan_bn_stats (partial sums +
 // final, the library's statistics kernels) followed by a plane-wise apply.
-#include "agan_common.h"
-
-#include <algorithm>
+#include "bn_common.h"
 
 using namespace agan;
 
 namespace {
-
-constexpr int kSmallN = 8192;     // (bn_act.hip's one-launch bound)
-constexpr int kThreads = 256;
-
-__device__ __forceinline__ void block_sum2(double& a, double& b, double (*red)[4]) {
-    a = wave_sum_d(a);
-    b = wave_sum_d(b);
-    const int w = threadIdx.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) { red[0][w] = a; red[1][w] = b; }
-    __syncthreads();
-    a = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-    b = red[1][0] + red[1][1] + red[1][2] + red[1][3];
-}
 
 // ---- forward ------------------------------------------------------------------------------------------------------------------
 // one workgroup per channel; PER values per thread (n <= 256 * PER)
@@ -55,19 +39,8 @@ __global__ __launch_bounds__(kThreads) void bn_relu_slice_small_kernel(const flo
         }
     }
     block_sum2(s, q, red);
-    const double m = s / n;
-    double var = q / n - m * m;
-    var = var < 0.0 ? 0.0 : var;
-    const float mf = (float)m, is = (float)(1.0 / sqrt(var + (double)eps));
-    if (threadIdx.x == 0) {
-        mean[c] = mf;
-        invstd[c] = is;
-        if (rmean) {
-            const double ub = n > 1 ? (double)n / (n - 1) : 1.0;
-            rmean[c] = (float)((1.0 - momentum) * rmean[c] + momentum * m);
-            rvar[c] = (float)((1.0 - momentum) * rvar[c] + momentum * var * ub);
-        }
-    }
+    const BnStats st = bn_finish_channel(s, q, n, eps, momentum, c, threadIdx.x == 0, mean, invstd, rmean, rvar);
+    const float mf = st.mean, is = st.invstd;
     const float sc = gamma[c] * is, bc = beta[c];
 #pragma unroll
     for (int j = 0; j < PER; ++j) {
@@ -189,13 +162,6 @@ __global__ __launch_bounds__(kThreads) void bn_slice_bwd_apply_kernel(const floa
 
 bool small_path(int B, int HW) { return (long long)B * HW <= kSmallN; }
 
-// partial sums per channel of the large backward: about 2048 workgroups in all, each over at least 2048 values
-int bwd_chunks(int B, int C, int HW) {
-    const long long n = (long long)B * HW;
-    int nchunk = std::max(1, 2048 / std::max(C, 1));
-    return (int)std::min<long long>(nchunk, std::max<long long>(1, n / 2048));
-}
-
 bool slice_ok(int B, int C, int HW, int c0, int ctot) {
     return B > 0 && C > 0 && HW > 0 && c0 >= 0 && ctot > 0 && (long long)c0 + C <= ctot;
 }
@@ -218,13 +184,10 @@ int agan_bn_relu_slice_fwd(const float* x, const float* gamma, const float* beta
                  out_c0, out_c0 + C, out_ctot);
     hipStream_t st = as_stream(stream);
     if (small_path(B, HW)) {
-        const int n = B * HW;
-#define AGAN_L(P) hipLaunchKernelGGL((bn_relu_slice_small_kernel<P>), dim3(C), dim3(kThreads), 0, st, x, gamma, beta, out, out_c0, out_ctot, \
-                                     mean, invstd, running_mean, running_var, num_batches_tracked, B, C, HW, eps, momentum)
-        if (n <= 2 * kThreads) AGAN_L(2);
-        else if (n <= 8 * kThreads) AGAN_L(8);
-        else AGAN_L(kSmallN / kThreads);
-#undef AGAN_L
+        with_per(B * HW, [&](auto P) {
+            hipLaunchKernelGGL((bn_relu_slice_small_kernel<P()>), dim3(C), dim3(kThreads), 0, st, x, gamma, beta, out, out_c0, out_ctot, mean,
+                               invstd, running_mean, running_var, num_batches_tracked, B, C, HW, eps, momentum);
+        });
         return check_launch("bn_relu_slice_fwd/small");
     }
     if (!ws || ws_bytes < agan_bn_relu_slice_fwd_ws_bytes(B, C, HW)) {
@@ -241,7 +204,7 @@ int agan_bn_relu_slice_fwd(const float* x, const float* gamma, const float* beta
 
 size_t agan_bn_slice_bwd_ws_bytes(int B, int C, int HW) {
     if (B <= 0 || C <= 0 || HW <= 0 || small_path(B, HW)) return 0;
-    return (size_t)C * bwd_chunks(B, C, HW) * 2 * sizeof(double) + (size_t)C * 2 * sizeof(float);
+    return (size_t)C * bn_chunks(B, C, HW) * 2 * sizeof(double) + (size_t)C * 2 * sizeof(float);
 }
 
 int agan_bn_slice_bwd(const float* x, const float* dout, int dout_c0, int dout_ctot, const float* mean, const float* invstd,
@@ -251,20 +214,17 @@ int agan_bn_slice_bwd(const float* x, const float* dout, int dout_c0, int dout_c
                  dout_c0, dout_c0 + C, dout_ctot);
     hipStream_t st = as_stream(stream);
     if (small_path(B, HW)) {
-        const int n = B * HW;
-#define AGAN_L(P) hipLaunchKernelGGL((bn_slice_small_bwd_kernel<P>), dim3(C), dim3(kThreads), 0, st, x, dout, dout_c0, dout_ctot, mean, \
-                                     invstd, gamma, dx, B, C, HW)
-        if (n <= 2 * kThreads) AGAN_L(2);
-        else if (n <= 8 * kThreads) AGAN_L(8);
-        else AGAN_L(kSmallN / kThreads);
-#undef AGAN_L
+        with_per(B * HW, [&](auto P) {
+            hipLaunchKernelGGL((bn_slice_small_bwd_kernel<P()>), dim3(C), dim3(kThreads), 0, st, x, dout, dout_c0, dout_ctot, mean, invstd,
+                               gamma, dx, B, C, HW);
+        });
         return check_launch("bn_slice_bwd/small");
     }
     if (!ws || ws_bytes < agan_bn_slice_bwd_ws_bytes(B, C, HW)) {
         set_error("bn_slice_bwd: workspace too small");
         return AGAN_EWORKSPACE;
     }
-    const int nchunk = bwd_chunks(B, C, HW);
+    const int nchunk = bn_chunks(B, C, HW);
     double* part = static_cast<double*>(ws);
     float* coef = reinterpret_cast<float*>(part + (size_t)C * nchunk * 2);
     hipLaunchKernelGGL(bn_slice_bwd_partial_kernel, dim3(C, nchunk), dim3(kThreads), 0, st, x, dout, dout_c0, dout_ctot, mean, invstd, B, C,
