@@ -2005,3 +2005,122 @@ def retrieval_rank(query: Tensor, bank: Tensor, cand: Tensor, want_scores: bool 
     if bool((rank < 0).any()):
         raise ValueError(f"retrieval_rank: a candidate index lies outside [0, {M})")
     return (rank, scores) if want_scores else rank
+
+
+# --------------------------------------------------------------------------------------------------------------
+# pairwise-geometry reductions (evaluation.py: manifold_metrics, kernel_distance; include/agan.h: agan_knn_radius, agan_manifold_scan,
+# agan_poly_kernel_sum)
+# --------------------------------------------------------------------------------------------------------------
+# Device tensors run on the library.  A CPU tensor takes the float64 restatement below with the same rules: the row itself is left
+# out by index, `<=` against the radius, the lowest index on a tie, the diagonal left out by index.  There a squared distance is the
+# float64 sum of squared differences rounded once to float32 -- the value an exact fp32 computation would give -- so a distance
+# compared with a radius that IS that distance ties on the CPU as it does on the device.  None has autograd: these are measurements.
+_MANIFOLD_CPU_ELEMS = 1 << 24       # float64 elements per block of the CPU paths
+
+
+def _rows_operand(t: Tensor, name: str, what: str) -> Tensor:
+    if t.dim() != 2:
+        raise ValueError(f"{what}: expected {name} [n, D], got {tuple(t.shape)}")
+    if t.dtype != torch.float32:
+        raise ValueError(f"{what}: {name} must be float32, got {t.dtype}")
+    return t.contiguous()
+
+
+def _rows_in_domain(n: int, D: int) -> bool:
+    return n >= 1 and 1 <= D <= 4096 and n * D < 1 << 31
+
+
+def _pair_d2_blocks(q: Tensor, ref: Tensor):
+    """yields (first query row, d2 float64 [rows, n]) over blocks of query rows; d2 holds float32 values"""
+    r64 = ref.double()
+    rows = max(1, _MANIFOLD_CPU_ELEMS // max(1, ref.shape[0] * ref.shape[1]))
+    for s in range(0, q.shape[0], rows):
+        diff = q[s:s + rows].double().unsqueeze(1) - r64.unsqueeze(0)
+        yield s, (diff * diff).sum(-1).to(torch.float32).double()
+
+
+def knn_radius(x: Tensor, k: int) -> Tensor:
+    """-> rad2 float32 [n] on x's device: the k-th smallest squared distance from row i to the OTHER rows of x [n, D].  The row itself
+    is left out by index, so a duplicate row at distance 0 counts as a neighbour.  1 <= k <= 8, n >= k + 1."""
+    x = _rows_operand(x, "x", "knn_radius")
+    n, D = x.shape
+    k = int(k)
+    if not 1 <= k <= 8 or n < k + 1 or not _rows_in_domain(n, D):
+        raise ValueError(f"knn_radius: n {n}, D {D}, k {k} outside 1 <= k <= 8, n >= k + 1, 1 <= D <= 4096, n * D < 2^31")
+    if not x.is_cuda:
+        rad2 = torch.empty(n, dtype=torch.float32)
+        for s, d2 in _pair_d2_blocks(x, x):
+            rows = torch.arange(d2.shape[0])
+            d2[rows, s + rows] = float("inf")
+            rad2[s:s + d2.shape[0]] = d2.kthvalue(k, dim=1)[0].to(torch.float32)
+        return rad2
+    rad2 = torch.empty(n, dtype=torch.float32, device=x.device)
+    nbytes = L.load().agan_knn_radius_ws_bytes(n, D, k)
+    ws, wsp = _ws(nbytes, x)
+    _kmeans_call("agan_knn_radius", _p(x), n, D, k, _p(rad2), wsp, nbytes, _stream())
+    return rad2
+
+
+def manifold_scan(q: Tensor, ref: Tensor, rad2: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor]:
+    """-> (count int32 [m], near_d2 float32 [m], near_idx int32 [m]) on q's device, for q [m, D] against ref [n, D]:
+    count[i] = #{ j : d2(q_i, ref_j) <= rad2[j] } (all zeros without rad2), near_d2[i] = min_j d2(q_i, ref_j) and near_idx[i] the lowest
+    j that attains it."""
+    q, ref = _rows_operand(q, "q", "manifold_scan"), _rows_operand(ref, "ref", "manifold_scan")
+    m, D = q.shape
+    n = ref.shape[0]
+    if ref.shape[1] != D or ref.device != q.device:
+        raise ValueError(f"manifold_scan: q is {tuple(q.shape)} on {q.device}, ref {tuple(ref.shape)} on {ref.device}")
+    if rad2 is not None:
+        if rad2.dtype != torch.float32 or tuple(rad2.shape) != (n,) or rad2.device != q.device:
+            raise ValueError(f"manifold_scan: rad2 must be float32 [{n}] on {q.device}, got {rad2.dtype} {tuple(rad2.shape)} on {rad2.device}")
+        rad2 = rad2.contiguous()
+    if not _rows_in_domain(m, D) or not _rows_in_domain(n, D):
+        raise ValueError(f"manifold_scan: m {m}, n {n}, D {D} outside m, n >= 1, 1 <= D <= 4096, m * D and n * D < 2^31")
+    if not q.is_cuda:
+        count = torch.zeros(m, dtype=torch.int32)
+        near_d2 = torch.empty(m, dtype=torch.float32)
+        near_idx = torch.empty(m, dtype=torch.int32)
+        for s, d2 in _pair_d2_blocks(q, ref):
+            e = s + d2.shape[0]
+            if rad2 is not None:
+                count[s:e] = (d2 <= rad2.double().view(1, n)).sum(1).to(torch.int32)
+            best = torch.from_numpy(d2.numpy().argmin(axis=1))              # numpy: the first minimum
+            near_idx[s:e] = best.to(torch.int32)
+            near_d2[s:e] = d2.gather(1, best.view(-1, 1)).view(-1).to(torch.float32)
+        return count, near_d2, near_idx
+    count = torch.empty(m, dtype=torch.int32, device=q.device)
+    near_d2 = torch.empty(m, dtype=torch.float32, device=q.device)
+    near_idx = torch.empty(m, dtype=torch.int32, device=q.device)
+    nbytes = L.load().agan_manifold_scan_ws_bytes(m, n, D)
+    ws, wsp = _ws(nbytes, q)
+    _kmeans_call("agan_manifold_scan", _p(q), _p(ref), _p(rad2), m, n, D, _p(count), _p(near_d2), _p(near_idx), wsp, nbytes, _stream())
+    return count, near_d2, near_idx
+
+
+def poly_kernel_sum(x: Tensor, y: Tensor, exclude_diagonal: bool = False) -> Tensor:
+    """-> float64 [1] on x's device: sum_ij ((x_i . y_j) / D + 1)^3 over x [n, D] and y [m, D], without the terms i == j when
+    exclude_diagonal is set (then n == m; the caller passes y = x)."""
+    x, y = _rows_operand(x, "x", "poly_kernel_sum"), _rows_operand(y, "y", "poly_kernel_sum")
+    n, D = x.shape
+    m = y.shape[0]
+    if y.shape[1] != D or y.device != x.device:
+        raise ValueError(f"poly_kernel_sum: x is {tuple(x.shape)} on {x.device}, y {tuple(y.shape)} on {y.device}")
+    if not _rows_in_domain(n, D) or not _rows_in_domain(m, D) or (exclude_diagonal and n != m):
+        raise ValueError(f"poly_kernel_sum: n {n}, m {m}, D {D} outside n, m >= 1, 1 <= D <= 4096, n * D and m * D < 2^31 "
+                         f"(n == m with exclude_diagonal)")
+    if not x.is_cuda:
+        y64 = y.double()
+        total = torch.zeros((), dtype=torch.float64)
+        rows = max(1, _MANIFOLD_CPU_ELEMS // m)
+        for s in range(0, n, rows):
+            kv = ((x[s:s + rows].double() @ y64.t()) / D + 1.0) ** 3
+            if exclude_diagonal:
+                r = torch.arange(kv.shape[0])
+                kv[r, s + r] = 0.0
+            total += kv.sum()
+        return total.view(1)
+    out = torch.empty(1, dtype=torch.float64, device=x.device)
+    nbytes = L.load().agan_poly_kernel_sum_ws_bytes(n, m, D)
+    ws, wsp = _ws(nbytes, x)
+    _kmeans_call("agan_poly_kernel_sum", _p(x), _p(y), n, m, D, 1 if exclude_diagonal else 0, _p(out), wsp, nbytes, _stream())
+    return out

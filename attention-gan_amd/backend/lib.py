@@ -165,6 +165,12 @@ _SIGNATURES = {
     "agan_ema_plan": (c_int, [_P, c_int]),
     "agan_ema_update": (c_int, [_P, c_int, c_int, _P, c_double, c_int, _P]),
     "agan_adam_step": (c_int, [_P, _P, _P, _P, c_size_t, _P, c_double, c_double, c_double, c_double, c_float, _P]),
+    "agan_knn_radius_ws_bytes": (c_size_t, [c_int] * 3),
+    "agan_knn_radius": (c_int, [_P, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
+    "agan_manifold_scan_ws_bytes": (c_size_t, [c_int] * 3),
+    "agan_manifold_scan": (c_int, [_P, _P, _P] + [c_int] * 3 + [_P, _P, _P, _P, c_size_t, _P]),
+    "agan_poly_kernel_sum_ws_bytes": (c_size_t, [c_int] * 3),
+    "agan_poly_kernel_sum": (c_int, [_P, _P] + [c_int] * 4 + [_P, _P, c_size_t, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

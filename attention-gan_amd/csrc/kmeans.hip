@@ -26,19 +26,13 @@
 // A label outside [0, K) is counted nowhere and indexes nothing.  Every sum has one fixed order: the same bits on every run.
 #include <algorithm>
 
-#include "agan_common.h"
+#include "mfma_tile.h"
 
 namespace {
 using namespace agan;
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kThreads = 256;
+constexpr int kThreads = kTileThreads;        // (TileRegs, the k-major store and the MFMA stage: mfma_tile.h)
 constexpr int kRows = 128;             // rows of X per assign workgroup
-constexpr int kStep = 32;              // columns of D per LDS stage
-constexpr int kPad = 2;                // LDS row pad.  Row stride R + 2 = 2 (mod 64 banks): a wave's k-major stores hit 64 different banks on both load
-                                       // paths (16-byte path: bank 8 (t & 7) + (t >> 3) + const; 4-byte path: 2 (t & 31) + (t >> 5) + const), and the two
-                                       // lane halves of an MFMA operand read, 16 rows apart, lie 16 * 130 = 32 (mod 64) banks apart
 constexpr int kMaxDim = 4096;          // largest D and K
 constexpr int kSmallK = 32;            // K <= kSmallK: the one-chunk tiling
 constexpr int kPiece = 512;            // sorted rows per partial sum of the update
@@ -57,60 +51,6 @@ __global__ __launch_bounds__(kThreads) void centroid_norm_kernel(const float* __
     s = wave_sum(s);
     if (lane == 0) cnorm[k] = s;
 }
-
-// R rows x kStep columns of a row-major [n_rows, D] matrix, from (row0, d0), into registers; rows and columns past the matrix read 0.
-// VEC (D % 4 == 0): lane -> 4 columns (t & 7) * 4 of row (t >> 3) + 32 j; else lane -> column t & 31 of row (t >> 5) + 8 j.
-template <int R, bool VEC>
-struct TileRegs {
-    static constexpr int kN = R * kStep / kThreads;     // floats per thread
-    float v[kN];
-    __device__ __forceinline__ void load(const float* __restrict__ m, int n_rows, int D, int row0, int d0) {
-        const int t = threadIdx.x;
-        const int left = n_rows - row0;                             // (row0 + a tile row may pass 2^31: compare tile rows with what is left)
-        if (VEC) {
-            const int col = d0 + (t & 7) * 4;
-#pragma unroll
-            for (int j = 0; j < kN / 4; ++j) {
-                const int row = (t >> 3) + 32 * j;
-                float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (row < left && col < D) q = *reinterpret_cast<const float4*>(m + ((size_t)row0 + row) * D + col);
-                v[4 * j] = q.x, v[4 * j + 1] = q.y, v[4 * j + 2] = q.z, v[4 * j + 3] = q.w;
-            }
-        } else {
-            const int col = d0 + (t & 31);
-#pragma unroll
-            for (int j = 0; j < kN; ++j) {
-                const int row = (t >> 5) + 8 * j;
-                v[j] = (row < left && col < D) ? m[((size_t)row0 + row) * D + col] : 0.f;
-            }
-        }
-    }
-    // -> the k-major LDS image s[k][R + kPad]
-    __device__ __forceinline__ void store(float* s) const {
-        const int t = threadIdx.x;
-        if (VEC) {
-#pragma unroll
-            for (int j = 0; j < kN / 4; ++j)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) s[((t & 7) * 4 + q) * (R + kPad) + (t >> 3) + 32 * j] = v[4 * j + q];
-        } else {
-#pragma unroll
-            for (int j = 0; j < kN; ++j) s[(t & 31) * (R + kPad) + (t >> 5) + 8 * j] = v[j];
-        }
-    }
-    // adds the squares of this thread's part of each of its rows to sq[] (VEC: kN / 4 rows, else kN rows)
-    __device__ __forceinline__ void add_squares(float* sq) const {
-        if (VEC) {
-#pragma unroll
-            for (int j = 0; j < kN / 4; ++j)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) sq[j] = fmaf(v[4 * j + q], v[4 * j + q], sq[j]);
-        } else {
-#pragma unroll
-            for (int j = 0; j < kN; ++j) sq[j] = fmaf(v[j], v[j], sq[j]);
-        }
-    }
-};
 
 // WR x WC waves (rows x centroids), TR x TC tiles of 32 x 32 per wave: kRows = WR * TR * 32 rows, a chunk of KC = WC * TC * 32 centroids
 template <int WR, int WC, int TR, int TC, bool VEC>
@@ -163,20 +103,7 @@ __global__ __launch_bounds__(kThreads) void assign_kernel(const float* __restric
                 xr.load(x, N, D, row0, (s + 1) * kStep);
                 cr.load(cen, K, D, c0, (s + 1) * kStep);
             }
-            // MFMA j of the step multiplies columns j (lane half 0) and j + 16 (half 1): any pairing gives the same sum order on every run
-#pragma unroll 4
-            for (int j = 0; j < kStep / 2; ++j) {
-                const int k = j + (kStep / 2) * half;
-                float a[TC], b[TR];
-#pragma unroll
-                for (int i = 0; i < TC; ++i) a[i] = cs[k * (KC + kPad) + (wc * TC + i) * 32 + l32];
-#pragma unroll
-                for (int r = 0; r < TR; ++r) b[r] = xs[k * (kRows + kPad) + (wr * TR + r) * 32 + l32];
-#pragma unroll
-                for (int i = 0; i < TC; ++i)
-#pragma unroll
-                    for (int r = 0; r < TR; ++r) acc[i][r] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], b[r], acc[i][r], 0, 0, 0);
-            }
+            mfma_stage<KC, kRows, TC, TR>(cs, xs, wc * TC, wr * TR, half, l32, acc);
         }
         // register e of tile (i, r): centroid (e & 3) + 8 (e >> 2) + 4 half of the tile, row l32 -- ascending in (i, e) for a lane
 #pragma unroll

@@ -1,4 +1,5 @@
-"""Evaluation of a generator: R-precision and the Frechet distance, the two numbers AttnGAN-style work is judged by.
+"""Evaluation of a generator: R-precision and the Frechet distance, the two numbers AttnGAN-style work is judged by, and three
+companions that look at the image distribution where the Frechet distance is blind or biased.
 
   * R-precision: does the DAMSM image code of a generated image retrieve its own caption's sentence embedding among R - 1 mismatched
     ones (cosine similarity, losses/sentence_loss.py without gamma3)?  `r_precision` draws the mismatched captions from OTHER class ids
@@ -7,16 +8,24 @@
   * Frechet distance between the pooled 2048-vectors of the image encoder's trunk over real and over generated images.  The features
     never leave the device: `FeatureMoments` folds each batch into raw fp64 moments (functional.moments_update) and only mean and
     covariance travel to the host, once, for `frechet_distance`.
+  * Improved precision and recall (Kynkaanniemi et al. 2019) and density and coverage (Naeem et al. 2020), `manifold_metrics`: the
+    Frechet distance mixes fidelity and diversity into one scalar; these tell a collapsed generator (precision high, recall and
+    coverage low) from a diverse but poor one.  They need the feature ROWS of both sets -- `FeatureBank` keeps them on the device --
+    and reduce the pairwise distances without ever storing them (functional.knn_radius, functional.manifold_scan).
+  * The Kernel Inception Distance (Binkowski et al. 2018), `kernel_distance`: an unbiased estimate at any sample count, for the
+    "folder of images" case with fewer samples than feature dimensions, where most of the Frechet distance's spectrum is noise
+    (functional.poly_kernel_sum).
 
 The trunk's weights are whatever the user loaded (CNNEncoder.load_trunk_state_dict); nothing is downloaded.  A Frechet distance over a
 randomly initialised or self-trained trunk orders the checkpoints of one run; it is NOT comparable with published FID values, which
-presuppose the ImageNet-trained Inception-v3.  The Inception Score is out of scope (the trunk has no classifier head), and so is
-data-parallel evaluation beyond `FeatureMoments.merge`.
+presuppose the ImageNet-trained Inception-v3.  The same holds for precision, recall, density, coverage and the kernel distance.
+The Inception Score is out of scope (the trunk has no classifier head), and so is data-parallel evaluation beyond
+`FeatureMoments.merge`.
 """
 from __future__ import annotations
 
 import contextlib
-from typing import Callable, Dict, Iterable, List, Optional
+from typing import Callable, Dict, Iterable, List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -76,6 +85,101 @@ class FeatureMoments:
         self.count = int(sd["count"])
         self.sum.copy_(sd["sum"])
         self.gram.copy_(sd["gram"])
+
+
+class FeatureBank:
+    """Append-only store of float32 feature rows [capacity, D] on `device`: what the manifold metrics and the kernel distance need of a
+    set of images.  Like FeatureMoments, the real set is computed once, saved (`state_dict`) and reused for every checkpoint."""
+
+    def __init__(self, D: int, capacity: int, device="cpu"):
+        if not 1 <= int(D) <= 4096 or int(capacity) < 1 or int(capacity) * int(D) >= 1 << 31:
+            raise ValueError(f"FeatureBank: D {D}, capacity {capacity} outside 1 <= D <= 4096, capacity >= 1, capacity * D < 2^31")
+        self.D, self.capacity, self.device, self.count = int(D), int(capacity), torch.device(device), 0
+        self.data = torch.empty(self.capacity, self.D, dtype=torch.float32, device=self.device)
+
+    def update(self, x: Tensor) -> "FeatureBank":
+        """appends the rows of x [n, D]; ValueError when they do not fit"""
+        if x.dim() != 2 or x.shape[1] != self.D:
+            raise ValueError(f"FeatureBank.update: expected [n, {self.D}], got {tuple(x.shape)}")
+        n = int(x.shape[0])
+        if self.count + n > self.capacity:
+            raise ValueError(f"FeatureBank.update: {self.count} + {n} rows into a capacity of {self.capacity}")
+        self.data[self.count:self.count + n].copy_(x.detach())
+        self.count += n
+        return self
+
+    def rows(self) -> Tensor:
+        """the rows so far, [count, D]: a view of the store"""
+        return self.data[:self.count]
+
+    def state_dict(self) -> Dict:
+        return {"D": self.D, "capacity": self.capacity, "count": self.count, "rows": self.rows().cpu().clone()}
+
+    def load_state_dict(self, sd: Dict) -> None:
+        if int(sd["D"]) != self.D or int(sd["count"]) > self.capacity:
+            raise ValueError(f"FeatureBank.load_state_dict: {sd['count']} rows of D {sd['D']} into D {self.D}, capacity {self.capacity}")
+        self.count = int(sd["count"])
+        self.data[:self.count].copy_(sd["rows"])
+
+
+def _feature_rows(t, what: str) -> Tensor:
+    t = t.rows() if isinstance(t, FeatureBank) else t
+    if t.dim() != 2 or t.shape[0] < 1:
+        raise ValueError(f"{what}: expected feature rows [n, D], got {tuple(t.shape)}")
+    return t.detach().float()
+
+
+def manifold_metrics(real, fake, k: int = 3) -> Dict:
+    """-> {"precision", "recall", "density", "coverage"} of the fake rows [M, D] against the real rows [N, D] (tensors or FeatureBanks
+    on one device), from k-nearest-neighbour balls: rad2_real[j] is the squared distance from real row j to its k-th nearest OTHER real
+    row, rad2_fake alike.
+        precision = share of fake rows inside at least one real ball        (Kynkaanniemi et al. 2019)
+        recall    = share of real rows inside at least one fake ball
+        density   = number of real balls a fake row lies in, summed over the fake rows, / (k M)        (Naeem et al. 2020)
+        coverage  = share of real rows whose nearest fake row lies inside the real row's own ball
+    The published defaults are k = 3 for precision and recall and k = 5 for density and coverage; one k serves all four here, call
+    twice for both.  Four passes over pairwise distances that are never stored: knn_radius of each set, a scan of fake against real
+    and a scan of real against fake.  Both sets are first translated by the real set's column mean: distances do not change, but the
+    kernels form them as |q|^2 + |r|^2 - 2 q.r, which cancels badly for features that share a large offset (pooled Inception
+    features are non-negative)."""
+    real, fake = _feature_rows(real, "manifold_metrics"), _feature_rows(fake, "manifold_metrics")
+    if real.shape[1] != fake.shape[1] or real.device != fake.device:
+        raise ValueError(f"manifold_metrics: real is {tuple(real.shape)} on {real.device}, fake {tuple(fake.shape)} on {fake.device}")
+    k = int(k)
+    if not 1 <= k <= 8 or real.shape[0] < k + 1 or fake.shape[0] < k + 1:
+        raise ValueError(f"manifold_metrics: k {k} with {real.shape[0]} real and {fake.shape[0]} fake rows (1 <= k <= 8, k + 1 rows each)")
+    centre = real.double().mean(0).float()
+    real, fake = (real - centre).contiguous(), (fake - centre).contiguous()
+    rad_real, rad_fake = AF.knn_radius(real, k), AF.knn_radius(fake, k)
+    count_fr, _, _ = AF.manifold_scan(fake, real, rad_real)
+    count_rf, near_rf, _ = AF.manifold_scan(real, fake, rad_fake)
+    M = fake.shape[0]
+    return {"precision": float((count_fr > 0).double().mean()), "recall": float((count_rf > 0).double().mean()),
+            "density": float(count_fr.double().sum()) / (k * M), "coverage": float((near_rf <= rad_real).double().mean())}
+
+
+def kernel_distance(real, fake, subsets: int = 100, subset_size: int = 1000, seed: int = 0) -> Dict:
+    """-> {"kid", "kid_std"}: the Kernel Inception Distance, the unbiased estimate of the squared maximum mean discrepancy under the
+    kernel (x.y / D + 1)^3, as mean and standard deviation over `subsets` subsets of s = min(subset_size, N, M) rows of each set:
+        sum_{i != j} k(x_i, x_j) / (s (s - 1)) + sum_{i != j} k(y_i, y_j) / (s (s - 1)) - 2 sum_{i, j} k(x_i, y_j) / s^2.
+    The subsets are drawn without replacement by a host generator seeded with `seed` and gathered on the device; the three sums come
+    from functional.poly_kernel_sum.  Deterministic for a seed; the standard deviation of a single subset is 0."""
+    real, fake = _feature_rows(real, "kernel_distance"), _feature_rows(fake, "kernel_distance")
+    if real.shape[1] != fake.shape[1] or real.device != fake.device:
+        raise ValueError(f"kernel_distance: real is {tuple(real.shape)} on {real.device}, fake {tuple(fake.shape)} on {fake.device}")
+    N, M = real.shape[0], fake.shape[0]
+    s = min(int(subset_size), N, M)
+    if int(subsets) < 1 or s < 2:
+        raise ValueError(f"kernel_distance: {subsets} subsets of {s} rows (at least 1 subset of at least 2 rows)")
+    g = torch.Generator().manual_seed(int(seed))
+    sums = []
+    for _ in range(int(subsets)):
+        x = real[torch.randperm(N, generator=g)[:s].to(real.device)].contiguous()
+        y = fake[torch.randperm(M, generator=g)[:s].to(fake.device)].contiguous()
+        sums.append(torch.cat([AF.poly_kernel_sum(x, x, True), AF.poly_kernel_sum(y, y, True), AF.poly_kernel_sum(x, y)]))
+    t = torch.stack(sums).cpu()                                 # [subsets, 3] float64: the one synchronisation
+    est = (t[:, 0] + t[:, 1]) / (s * (s - 1)) - 2.0 * t[:, 2] / (s * s)
+    return {"kid": float(est.mean()), "kid_std": float(est.std(unbiased=False))}
 
 
 def frechet_distance(mu1: Tensor, cov1: Tensor, mu2: Tensor, cov2: Tensor) -> float:
@@ -178,7 +282,7 @@ def _eval_mode(*modules):
 
 
 class Evaluator:
-    """The loop around the two metrics.  `text_encoder(words, lengths) -> (word_embs, sent_embs)` and
+    """The loop around the metrics.  `text_encoder(words, lengths) -> (word_embs, sent_embs)` and
     `image_encoder.code_and_pooled(images) -> (cnn_code [B, E], pooled [B, P])` (networks.CNNEncoder, either backend; one trunk pass
     gives both); `generator` as GanTrainStep's.  Batches come in the reference's wire format
     (words, lengths, class_ids, img64, img128, img256)."""
@@ -203,15 +307,39 @@ class Evaluator:
         return fm
 
     @torch.no_grad()
+    def real_statistics(self, batches: Iterable) -> Tuple[FeatureMoments, FeatureBank]:
+        """feature moments AND feature rows of the batches' 256-pixel real images, from one trunk pass (the batches are listed first:
+        the bank's capacity is their row count)"""
+        batches = list(batches)
+        if not batches:
+            raise ValueError("Evaluator.real_statistics: no batches")
+        fm = bank = None
+        with _eval_mode(self.image_encoder):
+            for batch in batches:
+                _, pooled = self.image_encoder.code_and_pooled(batch[5].to(self.device))
+                if fm is None:
+                    fm = FeatureMoments(pooled.shape[1], self.device)
+                    bank = FeatureBank(pooled.shape[1], sum(int(b[5].shape[0]) for b in batches), self.device)
+                fm.update(pooled)
+                bank.update(pooled)
+        return fm, bank
+
+    @torch.no_grad()
     def evaluate(self, batches: Iterable, real: FeatureMoments, n_samples: int, R: int = 100, seed: int = 0,
-                 batch_size: Optional[int] = None, folds: int = 10, source: str = "fake") -> Dict:
+                 batch_size: Optional[int] = None, folds: int = 10, source: str = "fake", real_features: Optional[FeatureBank] = None,
+                 k: int = 3, kid_subsets: int = 100, kid_subset_size: int = 1000) -> Dict:
         """Generates up to n_samples images from the batches' captions (noise from a device generator seeded with `seed`), and returns
         {"r_precision", "r_precision_folds", "rank", "fid", "n"}.  A batch whose shortest caption has fewer than 2 words, or with fewer
         rows than batch_size (default: the first batch's), is skipped -- the reference's batch guard (train.py:112).
         source="real" puts the batches' own 256-pixel images in the generator's place: the ceiling of both numbers for this encoder
-        pair.  Deterministic for a seed."""
+        pair.  Deterministic for a seed.
+        With real_features (a FeatureBank of real images, e.g. from real_statistics) the generated pooled vectors are kept too and the
+        result gains "precision", "recall", "density", "coverage" (manifold_metrics with k) and "kid", "kid_std" (kernel_distance
+        with kid_subsets, kid_subset_size and seed).  Without it nothing more is stored or launched."""
         if source not in ("fake", "real"):
             raise ValueError(f"Evaluator.evaluate: source must be 'fake' or 'real', got {source!r}")
+        if real_features is not None and not isinstance(real_features, FeatureBank):
+            raise ValueError(f"Evaluator.evaluate: real_features must be a FeatureBank, got {type(real_features).__name__}")
         dev = self.device
         rng = torch.Generator(device=dev)
         rng.manual_seed(int(seed))
@@ -219,6 +347,7 @@ class Evaluator:
         codes: List[Tensor] = []
         sents: List[Tensor] = []
         cids: List[np.ndarray] = []
+        feats: List[Tensor] = []
         fm, n = None, 0
         with _eval_mode(self.G, self.text_encoder, self.image_encoder):
             for batch in batches:
@@ -241,6 +370,8 @@ class Evaluator:
                 keep = min(len(lens), n_samples - n)
                 fm = fm or FeatureMoments(pooled.shape[1], dev)
                 fm.update(pooled[:keep])
+                if real_features is not None:
+                    feats.append(pooled[:keep].detach().float())
                 codes.append(code[:keep])
                 sents.append(sent_embs[:keep])
                 cids.append(np.asarray(class_ids.detach().cpu() if isinstance(class_ids, Tensor) else class_ids).reshape(-1)[:keep])
@@ -250,4 +381,8 @@ class Evaluator:
         out = r_precision(torch.cat(codes), torch.cat(sents), np.concatenate(cids), R=R, seed=seed, folds=folds)
         out["fid"] = frechet_distance(real.mean(), real.cov(), fm.mean(), fm.cov())
         out["n"] = n
+        if real_features is not None:
+            fake_rows = torch.cat(feats)
+            out.update(manifold_metrics(real_features, fake_rows, k=k))
+            out.update(kernel_distance(real_features, fake_rows, subsets=kid_subsets, subset_size=kid_subset_size, seed=seed))
         return out

@@ -37,7 +37,8 @@ extern "C" {
  * trunk on channel slices (agan_bn_relu_slice_fwd, agan_bn_slice_bwd); the trainable general 2-D conv behind Layers.conv
  * (agan_conv2d_train_*: forward, data gradient and weight gradient of any small geometry); the batch preparation from device-resident
  * uint8 shards (agan_image_prep); the two halves of a Lloyd iteration behind the pseudo-caption clustering (agan_kmeans_*); the
- * reductions of a generator's evaluation (agan_moments_*, agan_retrieval_rank). */
+ * reductions of a generator's evaluation (agan_moments_*, agan_retrieval_rank; agan_knn_radius, agan_manifold_scan and
+ * agan_poly_kernel_sum for precision / recall, density / coverage and the kernel distance). */
 
 enum {
     AGAN_OK = 0,
@@ -693,6 +694,43 @@ typedef struct agan_ema_seg {
 } agan_ema_seg;
 int agan_ema_plan(agan_ema_seg* segs /* HOST, nseg entries */, int nseg);
 int agan_ema_update(const agan_ema_seg* table /* DEVICE */, int nseg, int total_blocks, int32_t* state, double decay, int warmup, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Reductions over the pairwise geometry of two feature sets (csrc/manifold.hip; evaluation.py: manifold_metrics -- improved precision
+ * and recall, Kynkaanniemi et al. 2019, density and coverage, Naeem et al. 2020 -- and kernel_distance -- KID, Binkowski et al. 2018).
+ * Rows are fp32, row-major, D wide.  One contraction skeleton on v_mfma_f32_32x32x2_f32 (exact fp32 products; there is no 16-bit mode)
+ * carries all three: a workgroup owns 128 query rows and walks the reference rows in chunks of 128, the scores stay in the accumulator
+ * registers and each entry's reduction is the epilogue: no n x m matrix exists in memory.  Where the blocks of query rows alone would
+ * not fill the chip the references are split into ranges of whole chunks over a second grid dimension (a function of the shape alone);
+ * the workgroups' partial results go through the workspace and a small pass merges them by the same rules.
+ *   d2(q, r) = max(0, |q|^2 + |r|^2 - 2 q.r), in fp32: the squared norms from a pass of their own, the dot product from the MFMA chain,
+ *   then one addition and one fused multiply-add.  The raw-norm form cancels when the rows share a large common offset: callers
+ *   translate both sets first (evaluation.manifold_metrics does).
+ *   agan_knn_radius: rad2[i] = the k-th smallest d2(x_i, x_j) over j != i.  The row itself is left out BY INDEX, so a duplicate row at
+ *     distance 0 counts as a neighbour (the published "(k + 1)-th smallest including self").  Every lane keeps the 8 smallest values of
+ *     its rows in registers; the partial lists of a row are merged as multisets, so the result does not depend on the tiling.
+ *     Domain: 1 <= k <= 8, n >= k + 1, 1 <= D <= 4096, n * D < 2^31.
+ *   agan_manifold_scan: count[i] = #{ j : d2(q_i, ref_j) <= rad2[j] }; near_d2[i] = min_j d2(q_i, ref_j) and near_idx[i] the LOWEST j
+ *     that attains it.  rad2 may be NULL: then nothing is counted and count is written as 0.  Domain: m, n >= 1, 1 <= D <= 4096,
+ *     m * D < 2^31, n * D < 2^31.
+ *   agan_poly_kernel_sum: *out = sum_ij ((x_i . y_j) / D + 1)^3, without the terms i == j when exclude_diagonal is set (the caller then
+ *     passes y == x; n != m is refused).  The dot product is the fp32 MFMA's and is converted to fp64 after it; quotient, sum, cube and
+ *     every addition are fp64.  Each workgroup leaves one fp64 partial in the workspace and a one-workgroup pass adds them in a fixed
+ *     order.  Domain: n, m >= 1, 1 <= D <= 4096, n * D < 2^31, m * D < 2^31.
+ * Tails in rows and D are handled inside the kernels (a D tail reads as zeros).  No address depends on feature data: non-finite
+ * features may give meaningless numbers, never a fault.  Anything outside the domains, or a missing pointer, is AGAN_EINVAL with a
+ * message before any launch (the *_ws_bytes queries then return 0); a workspace that is too small is AGAN_EWORKSPACE.  No atomics; every
+ * sum has one fixed order: two runs on the same inputs give the same bits.  Only enqueues on `stream`: no allocation, no synchronisation.
+ * ---------------------------------------------------------------------------------------------- */
+size_t agan_knn_radius_ws_bytes(int n, int D, int k);
+int agan_knn_radius(const float* x /* [n, D] */, int n, int D, int k, float* rad2 /* [n] */, void* ws, size_t ws_bytes, void* stream);
+size_t agan_manifold_scan_ws_bytes(int m, int n, int D);
+int agan_manifold_scan(const float* q /* [m, D] */, const float* ref /* [n, D] */, const float* rad2 /* [n] or NULL */, int m, int n, int D,
+                       int32_t* count /* [m] */, float* near_d2 /* [m] */, int32_t* near_idx /* [m] */, void* ws, size_t ws_bytes,
+                       void* stream);
+size_t agan_poly_kernel_sum_ws_bytes(int n, int m, int D);
+int agan_poly_kernel_sum(const float* x /* [n, D] */, const float* y /* [m, D] */, int n, int m, int D, int exclude_diagonal,
+                         double* out /* [1] */, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }
