@@ -7,6 +7,7 @@
 // to the compile-time TMAX so the inner loops have no bounds checks; every LDS read is a broadcast.
 // Algorithmic bytes/pixel: 4*(C read + C write + T write); HBM-bound (116 MB at gen3).
 #include "agan_common.h"
+#include "dispatch.h"
 
 using namespace agan;
 
@@ -305,20 +306,13 @@ int agan_attn_fwd_dt(const void* images, const float* words, const float* w, con
     AGAN_REQUIRE(C <= kMaxC, "attn_fwd: nc_in %d > %d", C, kMaxC);
     AGAN_REQUIRE(T <= 64, "attn_fwd: seq_len %d > 64", T);
     hipStream_t st = as_stream(stream);
-    if (T <= 16) hipLaunchKernelGGL((attn_proj_kernel<16>), dim3(cdiv(B * C, 4)), dim3(256), 0, st, words, w, proj, B, C, E, T);
-    else if (T <= 32) hipLaunchKernelGGL((attn_proj_kernel<32>), dim3(cdiv(B * C, 4)), dim3(256), 0, st, words, w, proj, B, C, E, T);
-    else hipLaunchKernelGGL((attn_proj_kernel<64>), dim3(cdiv(B * C, 4)), dim3(256), 0, st, words, w, proj, B, C, E, T);
-    dim3 grid(cdiv(HW, 256), B);
-#define AGAN_ATTN_FWD(TM)                                                                                                                        \
-    do {                                                                                                                                         \
-        if (dtype == AGAN_DT_BF16) hipLaunchKernelGGL((attn_fwd_kernel<TM, AGAN_DT_BF16>), grid, dim3(256), 0, st, images, proj, mask, scale, ctx, attn, C, T, HW); \
-        else if (dtype == AGAN_DT_F16) hipLaunchKernelGGL((attn_fwd_kernel<TM, AGAN_DT_F16>), grid, dim3(256), 0, st, images, proj, mask, scale, ctx, attn, C, T, HW); \
-        else hipLaunchKernelGGL((attn_fwd_kernel<TM>), grid, dim3(256), 0, st, images, proj, mask, scale, ctx, attn, C, T, HW);                      \
-    } while (0)
-    if (T <= 16) AGAN_ATTN_FWD(16);
-    else if (T <= 32) AGAN_ATTN_FWD(32);
-    else AGAN_ATTN_FWD(64);
-#undef AGAN_ATTN_FWD
+    const dim3 grid(cdiv(HW, 256), B);
+    with_tier<16, 32, 64>(T, [&](auto TM) {
+        hipLaunchKernelGGL((attn_proj_kernel<TM()>), dim3(cdiv(B * C, 4)), dim3(256), 0, st, words, w, proj, B, C, E, T);
+        with_dt(dtype, [&](auto DT) {
+            hipLaunchKernelGGL((attn_fwd_kernel<TM(), DT()>), grid, dim3(256), 0, st, images, proj, mask, scale, ctx, attn, C, T, HW);
+        });
+    });
     return check_launch("attn_fwd");
 }
 
@@ -349,27 +343,12 @@ int agan_attn_bwd_dt(const void* images, const float* words, const float* w, con
     float* dproj = static_cast<float*>(ws);
     float* part = dproj + (size_t)B * C * T;
     const int nblk = cdiv(HW, 256);
-    dim3 grid(nblk, B);
-#define AGAN_ATTN_BWD_DT(TM, DT)                                                                                                     \
-    do {                                                                                                                             \
-        const size_t smem_ = sizeof(float) * (kMaxC * TM * 5 + (TM == 16 ? 4 * 48 * kAttLd : 0));                                    \
-        static const hipError_t attr_ = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_kernel<TM, DT>),                  \
-                                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_);                 \
-        (void)attr_;                                                                                                                 \
-        hipLaunchKernelGGL((attn_bwd_kernel<TM, DT>), grid, dim3(256), smem_, st, images, proj, attn, dctx, dattn, scale, dimages, part, \
-                           C, T, HW);                                                                                                \
-    } while (0)
-#define AGAN_ATTN_BWD(TM)                                                       \
-    do {                                                                        \
-        if (dtype == AGAN_DT_BF16) AGAN_ATTN_BWD_DT(TM, AGAN_DT_BF16);          \
-        else if (dtype == AGAN_DT_F16) AGAN_ATTN_BWD_DT(TM, AGAN_DT_F16);       \
-        else AGAN_ATTN_BWD_DT(TM, AGAN_DT_F32);                                 \
-    } while (0)
-    if (T <= 16) AGAN_ATTN_BWD(16);
-    else if (T <= 32) AGAN_ATTN_BWD(32);
-    else AGAN_ATTN_BWD(64);
-#undef AGAN_ATTN_BWD
-#undef AGAN_ATTN_BWD_DT
+    const dim3 grid(nblk, B);
+    with_tier<16, 32, 64>(T, [&](auto TM) { with_dt(dtype, [&](auto DT) {
+        constexpr size_t smem = sizeof(float) * (kMaxC * TM() * 5 + (TM() == 16 ? 4 * 48 * kAttLd : 0));
+        allow_dynamic_lds<attn_bwd_kernel<TM(), DT()>>((int)smem);
+        hipLaunchKernelGGL((attn_bwd_kernel<TM(), DT()>), grid, dim3(256), smem, st, images, proj, attn, dctx, dattn, scale, dimages, part, C, T, HW);
+    }); });
     hipLaunchKernelGGL(attn_dproj_reduce_kernel, dim3(cdiv(B * C * T, 256)), dim3(256), 0, st, part, dproj, B, nblk, C * T);
     hipLaunchKernelGGL(attn_bwd_words_kernel, dim3(cdiv(B * E * T + C * E, 256)), dim3(256), 0, st, words, w, dproj, dwords, dw, B, C, E, T, accumulate);
     return check_launch("attn_bwd");

@@ -561,12 +561,6 @@ template <bool ANY16, class F> void with_width(int vw, F&& f) {
     else if (vw == 4) f(Int<4>{});
     else f(Int<1>{});
 }
-// f(Int<DT>) for one storage type (the caller has checked it)
-template <class F> void with_dt(int dt, F&& f) {
-    if (dt == AGAN_DT_F32) f(Int<AGAN_DT_F32>{});
-    else if (dt == AGAN_DT_BF16) f(Int<AGAN_DT_BF16>{});
-    else f(Int<AGAN_DT_F16>{});
-}
 // f(Int<ACT>) for an activation of agan_act_fwd / agan_act_bwd; false, and no call, for any other
 template <class F> bool bare_act(int act, F&& f) {
     if (act == AGAN_ACT_LRELU) f(Int<AGAN_ACT_LRELU>{});

@@ -2,14 +2,11 @@
 // the two-pass reductions, the block reduction of two doubles, and the finish of one channel's statistics.
 #pragma once
 #include "agan_common.h"
+#include "dispatch.h"
 
 #include <algorithm>
-#include <type_traits>
 
 namespace agan {
-
-// a run-time choice handed to a generic lambda as a type: f(Int<N>{}) instantiates the kernel for N
-template <int N> using Int = std::integral_constant<int, N>;
 
 constexpr int kThreads = 256;                    // threads per workgroup of the one-launch kernels
 constexpr int kSmallN = 8192;                    // channels of n = B*HW <= kSmallN values take ONE launch, the values held in registers

@@ -432,57 +432,47 @@ __global__ __launch_bounds__(256) void sum_slabs_few_kernel_t(const float* __res
     if (amax) amax_commit(mx, amax);
 }
 
-// out = sum of nsplit slabs (+ bias, + out, activation, mask), ODT = storage type of out / lrelu_mask
-template <int ODT>
-void launch_sum_slabs_t(const float* ws, int nsplit, size_t n, size_t slab, const float* bias, int C, int HW, void* out, int accumulate,
-                        int act, const void* lrelu_mask, float* amax, hipStream_t st) {
-    if (nsplit <= 8) {
-        const int blocks = (int)std::min<size_t>(cdivz(n / 4 + 1, 256), 32768);
-        AGAN_LAUNCH(sum_slabs_few_kernel_t<ODT>, dim3(blocks), dim3(256), 0, st, ws, nsplit, n, slab, bias, C, HW, out, accumulate, act,
-                    lrelu_mask, amax);
-    } else {
-        const int blocks = (int)std::min<size_t>(cdivz(n / 4 + 1, 32), 8192);
-        AGAN_LAUNCH(sum_slabs_kernel_t<ODT>, dim3(blocks), dim3(256), 0, st, ws, nsplit, n, slab, bias, C, HW, out, accumulate, act,
-                    lrelu_mask, amax);
-    }
-}
+// out = sum of nsplit slabs (+ bias, + out, activation, mask); out_dtype = storage type of out / lrelu_mask
 void launch_sum_slabs(const float* ws, int nsplit, size_t n, size_t slab, const float* bias, int C, int HW, void* out, int accumulate,
                       int act, const void* lrelu_mask, float* amax, hipStream_t st, int out_dtype = AGAN_DT_F32) {
-    if (out_dtype == AGAN_DT_F32) launch_sum_slabs_t<AGAN_DT_F32>(ws, nsplit, n, slab, bias, C, HW, out, accumulate, act, lrelu_mask, amax, st);
-    else if (out_dtype == AGAN_DT_BF16) launch_sum_slabs_t<AGAN_DT_BF16>(ws, nsplit, n, slab, bias, C, HW, out, accumulate, act, lrelu_mask, amax, st);
-    else launch_sum_slabs_t<AGAN_DT_F16>(ws, nsplit, n, slab, bias, C, HW, out, accumulate, act, lrelu_mask, amax, st);
+    with_dt(out_dtype, [&](auto ODT) {
+        if (nsplit <= 8) {
+            const int blocks = (int)std::min<size_t>(cdivz(n / 4 + 1, 256), 32768);
+            AGAN_LAUNCH(sum_slabs_few_kernel_t<ODT()>, dim3(blocks), dim3(256), 0, st, ws, nsplit, n, slab, bias, C, HW, out, accumulate, act,
+                        lrelu_mask, amax);
+        } else {
+            const int blocks = (int)std::min<size_t>(cdivz(n / 4 + 1, 32), 8192);
+            AGAN_LAUNCH(sum_slabs_kernel_t<ODT()>, dim3(blocks), dim3(256), 0, st, ws, nsplit, n, slab, bias, C, HW, out, accumulate, act,
+                        lrelu_mask, amax);
+        }
+    });
 }
 
-template <int BN, int WM, int WN>
+// the tile forms of the k-table gather for a cout tile of bn channels: f(Int<BN>, Int<WM>, Int<WN>)
+template <class F> void with_gather_tile(int bn, F&& f) {
+    if (bn == 128) f(Int<128>{}, Int<2>{}, Int<2>{});
+    else if (bn == 64) f(Int<64>{}, Int<2>{}, Int<2>{});
+    else f(Int<32>{}, Int<4>{}, Int<1>{});
+}
 void launch_gather(const float* in, const float* wk, const float* bias, void* dst, const int2* ktab, const Geom& g,
                    const GatherPlan& p, int act, const void* lrelu_mask, hipStream_t st, int out_dtype = AGAN_DT_F32) {
-    dim3 grid(p.mtiles, p.ntiles, p.ncls * p.ksplit);
-    if (out_dtype == AGAN_DT_BF16)
-        AGAN_LAUNCH((conv_gather_f32_kernel<128, BN, WM, WN, AGAN_DT_BF16>), grid, dim3(256), 0, st, in, wk, bias, dst, ktab, g, p.ksplit,
-                           p.kchunk, p.slab, act, lrelu_mask);
-    else if (out_dtype == AGAN_DT_F16)
-        AGAN_LAUNCH((conv_gather_f32_kernel<128, BN, WM, WN, AGAN_DT_F16>), grid, dim3(256), 0, st, in, wk, bias, dst, ktab, g, p.ksplit,
-                           p.kchunk, p.slab, act, lrelu_mask);
-    else
-        AGAN_LAUNCH((conv_gather_f32_kernel<128, BN, WM, WN>), grid, dim3(256), 0, st, in, wk, bias, dst, ktab, g, p.ksplit,
-                           p.kchunk, p.slab, act, lrelu_mask);
+    const dim3 grid(p.mtiles, p.ntiles, p.ncls * p.ksplit);
+    with_gather_tile(p.bn, [&](auto BN, auto WM, auto WN) { with_dt(out_dtype, [&](auto ODT) {
+        AGAN_LAUNCH((conv_gather_f32_kernel<128, BN(), WM(), WN(), ODT()>), grid, dim3(256), 0, st, in, wk, bias, dst, ktab, g, p.ksplit, p.kchunk,
+                    p.slab, act, lrelu_mask);
+    }); });
 }
 
 // the general 2-D conv (agan_conv2d_fwd / agan_conv2d_dgrad): one unsplit launch, fp32 output, K tile kGatherBK
 static void launch_gather_2d(const float* in, const float* wk, const float* bias, float* out, const int2* ktab, const Geom& g,
                              const float* relu_mask, hipStream_t st) {
     const int bn = g.Cout >= 96 ? 128 : (g.Cout >= 48 ? 64 : 32);
-    dim3 grid(cdiv(g.Mtot, 128), cdiv(g.Cout, bn), g.OS * g.OS);
+    const dim3 grid(cdiv(g.Mtot, 128), cdiv(g.Cout, bn), g.OS * g.OS);
     const int kchunk = cdiv(g.K, kGatherBK) * kGatherBK;
-    if (bn == 128)
-        AGAN_LAUNCH((conv_gather_f32_kernel<128, 128, 2, 2, AGAN_DT_F32, true>), grid, dim3(256), 0, st, in, wk, bias, (void*)out, ktab, g, 1,
+    with_gather_tile(bn, [&](auto BN, auto WM, auto WN) {
+        AGAN_LAUNCH((conv_gather_f32_kernel<128, BN(), WM(), WN(), AGAN_DT_F32, true>), grid, dim3(256), 0, st, in, wk, bias, (void*)out, ktab, g, 1,
                     kchunk, (size_t)0, (int)AGAN_ACT_NONE, (const void*)relu_mask);
-    else if (bn == 64)
-        AGAN_LAUNCH((conv_gather_f32_kernel<128, 64, 2, 2, AGAN_DT_F32, true>), grid, dim3(256), 0, st, in, wk, bias, (void*)out, ktab, g, 1,
-                    kchunk, (size_t)0, (int)AGAN_ACT_NONE, (const void*)relu_mask);
-    else
-        AGAN_LAUNCH((conv_gather_f32_kernel<128, 32, 4, 1, AGAN_DT_F32, true>), grid, dim3(256), 0, st, in, wk, bias, (void*)out, ktab, g, 1,
-                    kchunk, (size_t)0, (int)AGAN_ACT_NONE, (const void*)relu_mask);
+    });
 }
 
 // ================================================================================================
@@ -1255,11 +1245,7 @@ int agan_conv_gather_dt(const void* in_v, const void* wkv, const float* bias, vo
             const GatherPlan& p = r.direct;
             slab = p.slab;
             const int2* ktab = reinterpret_cast<const int2*>(ktable);
-            e = launch_main(st, r.split, "conv_gather", [&] {
-                if (p.bn == 128) launch_gather<128, 2, 2>(in, wk, bias, dst, ktab, g, p, act, lrelu_mask_v, st, out_dtype);
-                else if (p.bn == 64) launch_gather<64, 2, 2>(in, wk, bias, dst, ktab, g, p, act, lrelu_mask_v, st, out_dtype);
-                else launch_gather<32, 4, 1>(in, wk, bias, dst, ktab, g, p, act, lrelu_mask_v, st, out_dtype);
-            });
+            e = launch_main(st, r.split, "conv_gather", [&] { launch_gather(in, wk, bias, dst, ktab, g, p, act, lrelu_mask_v, st, out_dtype); });
         }
     }
     if (e || r.split == 1) return e;
@@ -1369,14 +1355,12 @@ int agan_conv_wgrad_dt(const void* x_v, const void* dy_v, float* dw, const agan_
             float* part = via_sum ? wsf : reduced;
             const int2* ktab = reinterpret_cast<const int2*>(ktable);
             dim3 grid(p.itiles, p.jtiles, p.ncls * p.psplit);
-#define AGAN_WG(BI, BJ) AGAN_LAUNCH((conv_wgrad_f32_kernel<BI, BJ>), grid, dim3(256), 0, st, x, dy, part, ktab, g, p.psplit, p.pchunk, p.slab, acc_in_kernel)
             const int e = launch_main(st, r.split, "conv_wgrad", [&] {
-                if (p.bi == 128 && p.bj == 128) AGAN_WG(128, 128);
-                else if (p.bi == 128) AGAN_WG(128, 64);
-                else if (p.bj == 128) AGAN_WG(64, 128);
-                else AGAN_WG(64, 64);
+                with_bool(p.bi == 128, [&](auto I128) { with_bool(p.bj == 128, [&](auto J128) {
+                    AGAN_LAUNCH((conv_wgrad_f32_kernel<I128() ? 128 : 64, J128() ? 128 : 64>), grid, dim3(256), 0, st, x, dy, part, ktab, g, p.psplit, p.pchunk,
+                                p.slab, acc_in_kernel);
+                }); });
             });
-#undef AGAN_WG
             if (e) return e;
             if (via_sum) {
                 launch_sum_slabs(part, p.psplit, (size_t)p.ncls * g.Cout * g.K, p.slab, nullptr, 1, 1, reduced, (accumulate && !up) ? 1 : 0,

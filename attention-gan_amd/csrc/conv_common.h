@@ -1,9 +1,9 @@
 // Shared pieces of the convolution engine (geometry, reduction-index table, raw-buffer access, tap folding, launch plans).
 #pragma once
 #include "agan_common.h"
+#include "dispatch.h"
 
 #include <algorithm>
-#include <type_traits>
 
 namespace agan {
 namespace conv {
@@ -29,6 +29,12 @@ struct FastDiv {
     unsigned mul, shift;
     __device__ __forceinline__ int div(int n) const { return (int)((__umulhi(mul, (unsigned)n) + (unsigned)n) >> shift); }
 };
+// ceil(log2(v)) for v >= 1: the tile planners' power-of-two extents
+inline int pow2ceil_log(int v) {
+    int l = 0;
+    while ((1 << l) < v) ++l;
+    return l;
+}
 __host__ __device__ inline FastDiv make_fastdiv(unsigned d) {
     FastDiv f;
     unsigned l = 0;

@@ -466,88 +466,6 @@ __global__ __launch_bounds__(256, (WC == 2 ? 1 : kP16Occ)) void conv_p16_kernel(
     }
 }
 
-template <int ET, int GK, int BN, bool IN16, bool OUT16, int WC = 1, int LPX = 7>
-void launch_ni(const void* in, const void* wk, const float* bias, void* dst, const Geom& g, const P16Plan& p, int act, const void* mask,
-               hipStream_t st) {
-    dim3 grid(p.mtiles, p.ntiles, p.ncls * p.ksplit);
-    const unsigned short* w = static_cast<const unsigned short*>(wk);
-    const size_t smem = (size_t)p.smem_bytes;
-#define AGAN_P16_LAUNCH(NI_)                                                                                                             \
-    do {                                                                                                                                 \
-        static const hipError_t attr_ = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_p16_kernel<ET, GK, BN, IN16, OUT16, NI_, false, WC, LPX>), \
-                                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                     \
-        (void)attr_;                                                                                                                     \
-        AGAN_LAUNCH((conv_p16_kernel<ET, GK, BN, IN16, OUT16, NI_, false, WC, LPX>), grid, dim3(256), smem, st, in, w, bias, dst, g, p, act, mask); \
-    } while (0)
-    if (p.NI == 1) AGAN_P16_LAUNCH(1);
-    else AGAN_P16_LAUNCH(2);
-#undef AGAN_P16_LAUNCH
-}
-// both column-parity classes in one workgroup (GK 1 on a stride-2 lattice, 64- or 128-channel tiles, one staging item per thread)
-template <int ET, int BN, bool IN16, bool OUT16>
-void launch_px2(const void* in, const void* wk, const float* bias, void* dst, const Geom& g, const P16Plan& p, int act, const void* mask,
-                hipStream_t st) {
-    dim3 grid(p.mtiles, p.ntiles, p.ncls * p.ksplit);
-    const unsigned short* w = static_cast<const unsigned short*>(wk);
-    const size_t smem = (size_t)p.smem_bytes;
-    static const hipError_t attr_ = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_p16_kernel<ET, 1, BN, IN16, OUT16, 1, true>),
-                                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)attr_;
-    AGAN_LAUNCH((conv_p16_kernel<ET, 1, BN, IN16, OUT16, 1, true>), grid, dim3(256), smem, st, in, w, bias, dst, g, p, act, mask);
-}
-template <int ET, int GK, int BN, int WC, int LPX>
-void launch_io(const void* in, const void* wk, const float* bias, void* dst, const Geom& g, const P16Plan& p, int act, const void* mask,
-               hipStream_t st, bool in16, bool out16) {
-    if (in16 && out16) launch_ni<ET, GK, BN, true, true, WC, LPX>(in, wk, bias, dst, g, p, act, mask, st);
-    else if (in16) launch_ni<ET, GK, BN, true, false, WC, LPX>(in, wk, bias, dst, g, p, act, mask, st);
-    else if (out16) launch_ni<ET, GK, BN, false, true, WC, LPX>(in, wk, bias, dst, g, p, act, mask, st);
-    else launch_ni<ET, GK, BN, false, false, WC, LPX>(in, wk, bias, dst, g, p, act, mask, st);
-}
-template <int ET, int GK, int BN>
-void launch_dt(const void* in, const void* wk, const float* bias, void* dst, const Geom& g, const P16Plan& p, int act, const void* mask,
-               hipStream_t st, bool in16, bool out16) {
-    if constexpr (GK == 1 && BN >= 64 && BN <= 128) {
-        if (p.px2) {
-            if (in16 && out16) launch_px2<ET, BN, true, true>(in, wk, bias, dst, g, p, act, mask, st);
-            else if (in16) launch_px2<ET, BN, true, false>(in, wk, bias, dst, g, p, act, mask, st);
-            else if (out16) launch_px2<ET, BN, false, true>(in, wk, bias, dst, g, p, act, mask, st);
-            else launch_px2<ET, BN, false, false>(in, wk, bias, dst, g, p, act, mask, st);
-            return;
-        }
-    }
-    // the register-tile forms (round 4): 64 channels x 128 pixels per wave
-    if constexpr (BN == 128) {
-        if (p.wc == 2) { launch_io<ET, GK, 128, 2, 8>(in, wk, bias, dst, g, p, act, mask, st, in16, out16); return; }      // 128 channels x 256 pixels
-    }
-    if constexpr (BN == 256) {
-        launch_io<ET, GK, 256, 2, 7>(in, wk, bias, dst, g, p, act, mask, st, in16, out16);                                 // 256 channels x 128 pixels
-        return;
-    } else {
-        launch_io<ET, GK, BN, 1, 7>(in, wk, bias, dst, g, p, act, mask, st, in16, out16);
-    }
-}
-template <int ET, int GK>
-void launch_bn(const void* in, const void* wk, const float* bias, void* dst, const Geom& g, const P16Plan& p, int act, const void* mask,
-               hipStream_t st, bool in16, bool out16) {
-    if (p.bn == 256) launch_dt<ET, GK, 256>(in, wk, bias, dst, g, p, act, mask, st, in16, out16);
-    else if (p.bn == 128) launch_dt<ET, GK, 128>(in, wk, bias, dst, g, p, act, mask, st, in16, out16);
-    else if (p.bn == 64) launch_dt<ET, GK, 64>(in, wk, bias, dst, g, p, act, mask, st, in16, out16);
-    else launch_dt<ET, GK, 32>(in, wk, bias, dst, g, p, act, mask, st, in16, out16);
-}
-template <int ET>
-void launch_gk(const void* in, const void* wk, const float* bias, void* dst, const Geom& g, const P16Plan& p, int act, const void* mask,
-               hipStream_t st, bool in16, bool out16) {
-    if (p.gk == 0) launch_bn<ET, 0>(in, wk, bias, dst, g, p, act, mask, st, in16, out16);
-    else if (p.gk == 1) launch_bn<ET, 1>(in, wk, bias, dst, g, p, act, mask, st, in16, out16);
-    else launch_bn<ET, 2>(in, wk, bias, dst, g, p, act, mask, st, in16, out16);
-}
-
-int pow2ceil_log_(int v) {
-    int l = 0;
-    while ((1 << l) < v) ++l;
-    return l;
-}
-
 }  // namespace
 
 namespace agan {
@@ -577,8 +495,8 @@ static P16Plan plan_impl(const Geom& g, bool in16, bool allow_px2, int tile = 0)
     p.px2 = (p.wc == 1 && allow_px2 && p.gk == 1 && g.OS == 2 && p.bn >= 64 && g.OY1 >= g.OY0) ? 1 : 0;
     const int lp = p.px2 ? 6 : (tile == 1 ? 8 : 7);
     p.lp = lp;
-    p.twl = std::min(5, pow2ceil_log_(g.OWs));
-    p.thl = std::min(lp - p.twl, pow2ceil_log_(g.OHs));
+    p.twl = std::min(5, pow2ceil_log(g.OWs));
+    p.thl = std::min(lp - p.twl, pow2ceil_log(g.OHs));
     const int TW = 1 << p.twl, TH = 1 << p.thl;
     p.TB = (1 << lp) >> (p.twl + p.thl);
     p.tiles_x = cdiv(g.OWs, TW);
@@ -637,8 +555,36 @@ P16Plan plan_p16(const Geom& g, bool in16) {
 
 void launch_p16_gather(const void* in, const void* wk, const float* bias, void* dst, const Geom& g, const P16Plan& p, int prec, int act,
                        const void* lrelu_mask, hipStream_t st, bool in16, bool out16) {
-    if (prec == AGAN_PREC_F16) launch_gk<1>(in, wk, bias, dst, g, p, act, lrelu_mask, st, in16, out16);
-    else launch_gk<0>(in, wk, bias, dst, g, p, act, lrelu_mask, st, in16, out16);
+    const dim3 grid(p.mtiles, p.ntiles, p.ncls * p.ksplit);
+    const unsigned short* w = static_cast<const unsigned short*>(wk);
+    const size_t smem = (size_t)p.smem_bytes;
+    // every mode but fp16 takes the bf16 form (the caller has checked: a one-plane mode)
+    with_prec16(prec == AGAN_PREC_F16 ? AGAN_PREC_F16 : AGAN_PREC_BF16, [&](auto ET, auto) {
+    with_tier<0, 1, 2>(p.gk, [&](auto GK) {
+    const auto tile = [&](auto BN) {
+    with_bool(in16, [&](auto IN16) { with_bool(out16, [&](auto OUT16) {
+        const auto launch = [&](auto NI, auto PX2, auto WC, auto LPX) {
+            constexpr auto kernel = conv_p16_kernel<ET(), GK(), BN(), IN16(), OUT16(), NI(), PX2(), WC(), LPX()>;
+            allow_dynamic_lds<kernel>(160 * 1024);
+            AGAN_LAUNCH(kernel, grid, dim3(256), smem, st, in, w, bias, dst, g, p, act, lrelu_mask);
+        };
+        // both column-parity classes in one workgroup (GK 1 on a stride-2 lattice, 64- or 128-channel tiles, one staging item per thread)
+        if constexpr (GK() == 1 && BN() >= 64 && BN() <= 128) {
+            if (p.px2) { launch(Int<1>{}, Bool<true>{}, Int<1>{}, Int<7>{}); return; }
+        }
+        with_bool(p.NI == 1, [&](auto ONE) {
+            using NI = Int<ONE() ? 1 : 2>;
+            // the register-tile forms (round 4), 64 channels x 128 pixels per wave: 128 channels x 256 pixels, 256 channels x 128 pixels
+            if constexpr (BN() == 128) {
+                if (p.wc == 2) { launch(NI{}, Bool<false>{}, Int<2>{}, Int<8>{}); return; }
+            }
+            if constexpr (BN() == 256) launch(NI{}, Bool<false>{}, Int<2>{}, Int<7>{});
+            else launch(NI{}, Bool<false>{}, Int<1>{}, Int<7>{});
+        });
+    }); });
+    };
+    if (!with_int<256, 128, 64>(p.bn, tile)) tile(Int<32>{});
+    }); });
 }
 
 }  // namespace conv

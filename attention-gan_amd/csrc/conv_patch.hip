@@ -983,47 +983,6 @@ __global__ __launch_bounds__(256) void pack_patch_jobs_kernel(const agan_pack_jo
                              local % nbn, local / nbn, tile);
 }
 
-template <int ET, int NPL, int BN>
-void launch_nt(const float* in, const void* wk, const float* bias, float* dst, const Geom& g, const PatchPlan& pp_in, const PatchGather& p,
-               int act, const float* mask, hipStream_t st, const float* in_scale, float* out_amax) {
-    PatchPlan pp = pp_in;                 // + the multiply-high constants of this launch's tile decode
-    pp.g_ntiles = p.ntiles; pp.g_ncls = p.ncls;
-    pp.dNT = make_fastdiv((unsigned)p.ntiles); pp.dNCLS = make_fastdiv((unsigned)p.ncls); pp.dMT = make_fastdiv((unsigned)pp.mtiles);
-    pp.dTX = make_fastdiv((unsigned)pp.tiles_x); pp.dTY = make_fastdiv((unsigned)pp.tiles_y);
-    pp.dNPH = make_fastdiv((unsigned)pp.NPH); pp.dNPH2 = make_fastdiv((unsigned)(2 * pp.NPH));
-    dim3 grid(pp.mtiles, p.ntiles, p.ncls * p.ksplit);
-    const unsigned short* w = static_cast<const unsigned short*>(wk);
-    constexpr int PB = (NPL >= 3 ? 16 : 32) * 2 + 16;
-    const int plane = (pp.PP + 7) / 8 * 8 * PB;
-    const size_t smem = (size_t)2 * NPL * plane;
-    if (pp.NT == 9) {
-        static const hipError_t a9 = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_patch_kernel2<ET, NPL, BN, 9>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)a9;
-        AGAN_LAUNCH((conv_patch_kernel2<ET, NPL, BN, 9>), grid, dim3(256), smem, st, in, w, bias, dst, g, pp, p.ksplit, p.stages_per_split, p.slab, act, mask, plane, in_scale, out_amax);
-    } else {
-        static const hipError_t a4 = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_patch_kernel2<ET, NPL, BN, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)a4;
-        AGAN_LAUNCH((conv_patch_kernel2<ET, NPL, BN, 4>), grid, dim3(256), smem, st, in, w, bias, dst, g, pp, p.ksplit, p.stages_per_split, p.slab, act, mask, plane, in_scale, out_amax);
-    }
-}
-template <int ET, int NPL>
-void launch_bn(const float* in, const void* wk, const float* bias, float* dst, const Geom& g, const PatchPlan& pp, const PatchGather& p,
-               int act, const float* mask, hipStream_t st, const float* in_scale, float* out_amax) {
-    if (p.bn == 128) launch_nt<ET, NPL, 128>(in, wk, bias, dst, g, pp, p, act, mask, st, in_scale, out_amax);
-    else if (p.bn == 64) launch_nt<ET, NPL, 64>(in, wk, bias, dst, g, pp, p, act, mask, st, in_scale, out_amax);
-    else launch_nt<ET, NPL, 32>(in, wk, bias, dst, g, pp, p, act, mask, st, in_scale, out_amax);
-}
-
-template <int ET, int NPL, int BJ, bool X16 = false, bool Y16 = false>
-void launch_wg_nt(const void* x, const void* dy, float* part, const Geom& g, const PatchPlan& pp, const PatchWgrad& p, hipStream_t st,
-                  const float* xs = nullptr, const float* ys = nullptr) {
-    dim3 grid(p.jtiles, pp.nstages, p.ncls * p.psplit);
-    if (pp.NT == 9)
-        AGAN_LAUNCH((conv_patch_wgrad_kernel<ET, NPL, BJ, 9, X16, Y16>), grid, dim3(256), 0, st, x, dy, part, g, pp, p.psplit, p.tiles_per_split, p.slab, xs, ys);
-    else
-        AGAN_LAUNCH((conv_patch_wgrad_kernel<ET, NPL, BJ, 4, X16, Y16>), grid, dim3(256), 0, st, x, dy, part, g, pp, p.psplit, p.tiles_per_split, p.slab, xs, ys);
-}
-// one-plane modes with typed activation storage
 // can the row-block staging take this weight gradient?  (8-pixel chunks inside tile rows, whole 16-byte blocks per tensor row, one x
 // item per thread)
 static bool wg_block16_ok(const Geom& g, const PatchPlan& pp) {
@@ -1033,30 +992,6 @@ static bool wg_block16_ok(const Geom& g, const PatchPlan& pp) {
     const int tb = 128 >> (pp.twl + pp.thl);
     return (kCH / 8) * tb * pp.PH * nxb <= 256;
 }
-template <int ET, int BJ>
-void launch_wg_b16(const void* x, const void* dy, float* part, const Geom& g, const PatchPlan& pp, const PatchWgrad& p, hipStream_t st) {
-    dim3 grid(p.jtiles, pp.nstages, p.ncls * p.psplit);
-    if (pp.NT == 9)
-        AGAN_LAUNCH((conv_patch_wgrad_kernel<ET, 1, BJ, 9, true, true, true>), grid, dim3(256), 0, st, x, dy, part, g, pp, p.psplit, p.tiles_per_split, p.slab, (const float*)nullptr, (const float*)nullptr);
-    else
-        AGAN_LAUNCH((conv_patch_wgrad_kernel<ET, 1, BJ, 4, true, true, true>), grid, dim3(256), 0, st, x, dy, part, g, pp, p.psplit, p.tiles_per_split, p.slab, (const float*)nullptr, (const float*)nullptr);
-}
-template <int ET, int BJ>
-void launch_wg_dt(const void* x, const void* dy, float* part, const Geom& g, const PatchPlan& pp, const PatchWgrad& p, hipStream_t st, bool x16,
-                  bool y16) {
-    if (x16 && y16 && wg_block16_ok(g, pp)) launch_wg_b16<ET, BJ>(x, dy, part, g, pp, p, st);
-    else if (x16 && y16) launch_wg_nt<ET, 1, BJ, true, true>(x, dy, part, g, pp, p, st);
-    else if (x16) launch_wg_nt<ET, 1, BJ, true, false>(x, dy, part, g, pp, p, st);
-    else if (y16) launch_wg_nt<ET, 1, BJ, false, true>(x, dy, part, g, pp, p, st);
-    else launch_wg_nt<ET, 1, BJ>(x, dy, part, g, pp, p, st);
-}
-
-inline int pow2ceil_log(int v) {
-    int l = 0;
-    while ((1 << l) < v) ++l;
-    return l;
-}
-
 }  // namespace
 
 namespace {
@@ -1085,12 +1020,9 @@ namespace agan {
 namespace conv {
 
 int prec_planes(int prec) {
-    switch (prec) {
-        case AGAN_PREC_BF16: case AGAN_PREC_F16: return 1;
-        case AGAN_PREC_BF16X3: case AGAN_PREC_F16X3: return 2;
-        case AGAN_PREC_BF16X6: return 3;
-    }
-    return 0;
+    int planes = 0;
+    with_prec16(prec, [&](auto, auto NPL) { planes = NPL(); });
+    return planes;
 }
 
 // Can the patch kernels run this geometry?  (taps 2x2 / 3x3 per phase, images of at least 4x4 lattice points, tensors < 2^30)
@@ -1202,16 +1134,10 @@ int pack_weight_patch(const float* w, void* wk, int mode, int cout, int cin, int
     const FastDiv drow = make_fastdiv((unsigned)((pack_n_is_cout(mode) ? kCH : kPackN) * kh * kw));
     PackPlanLite pl;
     pl.IS = pp.IS; pl.NPH = pp.NPH; pl.NT = pp.NT; pl.nsteps = pp.nsteps;
-#define AGAN_PK(ET, NPL) AGAN_LAUNCH((pack_patch_weight_kernel<ET, NPL>), blocks, dim3(256), 0, st, w, o, mode, cout, cin, kh, kw, ncls, K, R, S, Nld, pl, drow, dkk)
-    switch (prec) {
-        case AGAN_PREC_BF16: AGAN_PK(0, 1); break;
-        case AGAN_PREC_F16: AGAN_PK(1, 1); break;
-        case AGAN_PREC_BF16X3: AGAN_PK(0, 2); break;
-        case AGAN_PREC_BF16X6: AGAN_PK(0, 3); break;
-        case AGAN_PREC_F16X3: AGAN_PK(1, 2); break;
-        default: return AGAN_EINVAL;
-    }
-#undef AGAN_PK
+    const bool known = with_prec16(prec, [&](auto ET, auto NPL) {
+        AGAN_LAUNCH((pack_patch_weight_kernel<ET(), NPL()>), blocks, dim3(256), 0, st, w, o, mode, cout, cin, kh, kw, ncls, K, R, S, Nld, pl, drow, dkk);
+    });
+    if (!known) return AGAN_EINVAL;
     return check_launch("pack_weight/patch");
 }
 
@@ -1224,16 +1150,10 @@ int pack_job_blocks_patch(int mode, int cout, int cin, int kh, int kw) {
 }
 
 int pack_weights_patch(const agan_pack_job* jobs, int njobs, int total_blocks, int prec, hipStream_t st) {
-#define AGAN_PKJ(ET, NPL) AGAN_LAUNCH((pack_patch_jobs_kernel<ET, NPL>), dim3(total_blocks), dim3(256), 0, st, jobs, njobs)
-    switch (prec) {
-        case AGAN_PREC_BF16: AGAN_PKJ(0, 1); break;
-        case AGAN_PREC_F16: AGAN_PKJ(1, 1); break;
-        case AGAN_PREC_BF16X3: AGAN_PKJ(0, 2); break;
-        case AGAN_PREC_BF16X6: AGAN_PKJ(0, 3); break;
-        case AGAN_PREC_F16X3: AGAN_PKJ(1, 2); break;
-        default: return AGAN_EINVAL;
-    }
-#undef AGAN_PKJ
+    const bool known = with_prec16(prec, [&](auto ET, auto NPL) {
+        AGAN_LAUNCH((pack_patch_jobs_kernel<ET(), NPL()>), dim3(total_blocks), dim3(256), 0, st, jobs, njobs);
+    });
+    if (!known) return AGAN_EINVAL;
     return check_launch("pack_weights/patch");
 }
 
@@ -1257,17 +1177,25 @@ PatchWgrad plan_patch_wgrad(const Geom& g, const PatchPlan& pp, int prec) {
 
 void launch_patch_wgrad(const void* x, const void* dy, float* part, const Geom& g, const PatchPlan& pp, const PatchWgrad& p, int prec,
                         hipStream_t st, const float* x_scale, const float* dy_scale, bool x16, bool y16) {
-    if (x16 || y16) {          // (the caller has checked: one-plane mode, storage type = operand type)
-        if (prec == AGAN_PREC_BF16) { if (p.bj == 128) launch_wg_dt<0, 128>(x, dy, part, g, pp, p, st, x16, y16); else launch_wg_dt<0, 64>(x, dy, part, g, pp, p, st, x16, y16); }
-        else { if (p.bj == 128) launch_wg_dt<1, 128>(x, dy, part, g, pp, p, st, x16, y16); else launch_wg_dt<1, 64>(x, dy, part, g, pp, p, st, x16, y16); }
-        return;
-    }
-    switch (prec) {
-        case AGAN_PREC_F16X3: if (p.bj == 128) launch_wg_nt<1, 2, 128>(x, dy, part, g, pp, p, st, x_scale, dy_scale); else launch_wg_nt<1, 2, 64>(x, dy, part, g, pp, p, st, x_scale, dy_scale); break;
-        case AGAN_PREC_BF16: if (p.bj == 128) launch_wg_nt<0, 1, 128>(x, dy, part, g, pp, p, st); else launch_wg_nt<0, 1, 64>(x, dy, part, g, pp, p, st); break;
-        case AGAN_PREC_F16: if (p.bj == 128) launch_wg_nt<1, 1, 128>(x, dy, part, g, pp, p, st); else launch_wg_nt<1, 1, 64>(x, dy, part, g, pp, p, st); break;
-        case AGAN_PREC_BF16X3: if (p.bj == 128) launch_wg_nt<0, 2, 128>(x, dy, part, g, pp, p, st); else launch_wg_nt<0, 2, 64>(x, dy, part, g, pp, p, st); break;
-        default: launch_wg_nt<0, 3, 64>(x, dy, part, g, pp, p, st); break;
+    const dim3 grid(p.jtiles, pp.nstages, p.ncls * p.psplit);
+    const bool any16 = x16 || y16, b16 = x16 && y16 && wg_block16_ok(g, pp);      // b16: the row-block staging of two 16-bit tensors
+    const bool scaled = !any16 && prec == AGAN_PREC_F16X3;
+    const float* xs = scaled ? x_scale : nullptr;
+    const float* ys = scaled ? dy_scale : nullptr;
+    const auto launch = [&](auto ET, auto NPL) {
+        // 128-channel tiles but for the three-plane mode; typed storage (X16 / Y16) only in the one-plane modes, B16 only with both
+        with_bool(NPL() < 3 && p.bj == 128, [&](auto WIDE) { with_bool(pp.NT == 9, [&](auto NINE) {
+        with_bool(x16, [&](auto X16) { with_bool(y16, [&](auto Y16) { with_bool(b16, [&](auto B16) {
+            if constexpr (!(NPL() == 3 && WIDE()) && (NPL() == 1 || !(X16() || Y16())) && (!B16() || (X16() && Y16())))
+                AGAN_LAUNCH((conv_patch_wgrad_kernel<ET(), NPL(), WIDE() ? 128 : 64, NINE() ? 9 : 4, X16(), Y16(), B16()>), grid, dim3(256), 0, st, x, dy,
+                            part, g, pp, p.psplit, p.tiles_per_split, p.slab, xs, ys);
+        }); }); });
+        }); });
+    };
+    if (any16) {          // (the caller has checked: one-plane mode, storage type = operand type)
+        with_prec16(prec == AGAN_PREC_BF16 ? AGAN_PREC_BF16 : AGAN_PREC_F16, launch);
+    } else if (!with_prec16(prec, launch)) {
+        launch(Int<0>{}, Int<3>{});
     }
 }
 
@@ -1288,16 +1216,30 @@ void launch_patch_wgrad_unpack(const float* red, float* dw, int cout, int cin, i
     launch_patch_wgrad_unpack(red, dw, cout, cin, kh, kw, up, pp.NPH, pp.NT, p.Kp, accumulate, st);
 }
 
-void launch_patch_gather(const float* in, const void* wk, const float* bias, float* dst, const Geom& g, const PatchPlan& pp,
+void launch_patch_gather(const float* in, const void* wk, const float* bias, float* dst, const Geom& g, const PatchPlan& pp_in,
                          const PatchGather& p, int prec, int act, const float* lrelu_mask, hipStream_t st, const float* in_amax,
                          float* out_amax) {
-    switch (prec) {
-        case AGAN_PREC_BF16: launch_bn<0, 1>(in, wk, bias, dst, g, pp, p, act, lrelu_mask, st, nullptr, out_amax); break;
-        case AGAN_PREC_F16: launch_bn<1, 1>(in, wk, bias, dst, g, pp, p, act, lrelu_mask, st, nullptr, out_amax); break;
-        case AGAN_PREC_BF16X3: launch_bn<0, 2>(in, wk, bias, dst, g, pp, p, act, lrelu_mask, st, nullptr, out_amax); break;
-        case AGAN_PREC_F16X3: launch_bn<1, 2>(in, wk, bias, dst, g, pp, p, act, lrelu_mask, st, in_amax, out_amax); break;
-        default: launch_bn<0, 3>(in, wk, bias, dst, g, pp, p, act, lrelu_mask, st, nullptr, out_amax); break;
-    }
+    PatchPlan pp = pp_in;                 // + the multiply-high constants of this launch's tile decode
+    pp.g_ntiles = p.ntiles; pp.g_ncls = p.ncls;
+    pp.dNT = make_fastdiv((unsigned)p.ntiles); pp.dNCLS = make_fastdiv((unsigned)p.ncls); pp.dMT = make_fastdiv((unsigned)pp.mtiles);
+    pp.dTX = make_fastdiv((unsigned)pp.tiles_x); pp.dTY = make_fastdiv((unsigned)pp.tiles_y);
+    pp.dNPH = make_fastdiv((unsigned)pp.NPH); pp.dNPH2 = make_fastdiv((unsigned)(2 * pp.NPH));
+    const dim3 grid(pp.mtiles, p.ntiles, p.ncls * p.ksplit);
+    const unsigned short* w = static_cast<const unsigned short*>(wk);
+    const float* in_scale = prec == AGAN_PREC_F16X3 ? in_amax : nullptr;
+    const auto launch = [&](auto ET, auto NPL) {
+        constexpr int PB = (NPL() >= 3 ? 16 : 32) * 2 + 16;
+        const int plane = (pp.PP + 7) / 8 * 8 * PB;
+        const size_t smem = (size_t)2 * NPL() * plane;
+        const auto tile = [&](auto BN) { with_bool(pp.NT == 9, [&](auto NINE) {
+            constexpr auto kernel = conv_patch_kernel2<ET(), NPL(), BN(), NINE() ? 9 : 4>;
+            allow_dynamic_lds<kernel>(160 * 1024);
+            AGAN_LAUNCH(kernel, grid, dim3(256), smem, st, in, w, bias, dst, g, pp, p.ksplit, p.stages_per_split, p.slab, act, lrelu_mask, plane, in_scale,
+                        out_amax);
+        }); };
+        if (!with_int<128, 64>(p.bn, tile)) tile(Int<32>{});
+    };
+    if (!with_prec16(prec, launch)) launch(Int<0>{}, Int<3>{});      // (whatever else comes here runs as AGAN_PREC_BF16X6)
 }
 
 }  // namespace conv

@@ -562,57 +562,29 @@ void launch_gather_small_n(const void* in, const float* wk, const float* bias, f
         AGAN_LAUNCH(linear_small_n_kernel, dim3(g.Mtot), dim3(256), 0, st, static_cast<const float*>(in), wk, bias, out, g.K, g.Nld, g.Cout);
         return;
     }
-    if (strip_ok(g)) {
+    const bool strip = strip_ok(g);
+    if (strip || dgrad4_strip_ok(g)) {
         // few strips (small images): split the channels over the four waves of a workgroup (the kernel's CS)
         const int nstrips = g.B * g.IH * (g.IW >> 2);
         const bool split = nstrips <= 64 * 1024 && g.Cin >= 8;      // (measured: at 1536 waves the split is neutral to slower)
         const dim3 sg(split ? cdiv(nstrips, 64) : cdiv(nstrips, 256));
-#define AGAN_STRIP2(NC_, CS_)                                                                                                             \
-    do {                                                                                                                                  \
-        if (in_dtype == AGAN_DT_BF16) AGAN_LAUNCH((conv_small_strip_kernel<AGAN_DT_BF16, NC_, CS_>), sg, dim3(256), 0, st, in, wk, bias, out, g); \
-        else if (in_dtype == AGAN_DT_F16) AGAN_LAUNCH((conv_small_strip_kernel<AGAN_DT_F16, NC_, CS_>), sg, dim3(256), 0, st, in, wk, bias, out, g); \
-        else AGAN_LAUNCH((conv_small_strip_kernel<AGAN_DT_F32, NC_, CS_>), sg, dim3(256), 0, st, in, wk, bias, out, g);                  \
-    } while (0)
-#define AGAN_STRIP(NC_) do { if (split) AGAN_STRIP2(NC_, 4); else AGAN_STRIP2(NC_, 1); } while (0)
-        if (g.Cout <= 2) AGAN_STRIP(2);
-        else if (g.Cout == 3) AGAN_STRIP(3);
-        else AGAN_STRIP(4);
-#undef AGAN_STRIP
-#undef AGAN_STRIP2
+        with_dt(in_dtype, [&](auto DT) { with_tier<2, 3, 4>(g.Cout, [&](auto NC) { with_bool(split, [&](auto SPLIT) {
+            constexpr int CS = SPLIT() ? 4 : 1;
+            if (strip) AGAN_LAUNCH((conv_small_strip_kernel<DT(), NC(), CS>), sg, dim3(256), 0, st, in, wk, bias, out, g);
+            else AGAN_LAUNCH((conv_small_dgrad4_strip_kernel<DT(), NC(), CS>), sg, dim3(256), 0, st, in, wk, bias, out, g);
+        }); }); });
         return;
     }
-    if (dgrad4_strip_ok(g)) {
-        const int nstrips = g.B * g.IH * (g.IW >> 2);
-        const bool split = nstrips <= 64 * 1024 && g.Cin >= 8;      // (measured: at 1536 waves the split is neutral to slower)
-        const dim3 sg(split ? cdiv(nstrips, 64) : cdiv(nstrips, 256));
-#define AGAN_STRIP2(NC_, CS_)                                                                                                             \
-    do {                                                                                                                                  \
-        if (in_dtype == AGAN_DT_BF16) AGAN_LAUNCH((conv_small_dgrad4_strip_kernel<AGAN_DT_BF16, NC_, CS_>), sg, dim3(256), 0, st, in, wk, bias, out, g); \
-        else if (in_dtype == AGAN_DT_F16) AGAN_LAUNCH((conv_small_dgrad4_strip_kernel<AGAN_DT_F16, NC_, CS_>), sg, dim3(256), 0, st, in, wk, bias, out, g); \
-        else AGAN_LAUNCH((conv_small_dgrad4_strip_kernel<AGAN_DT_F32, NC_, CS_>), sg, dim3(256), 0, st, in, wk, bias, out, g);           \
-    } while (0)
-#define AGAN_STRIP(NC_) do { if (split) AGAN_STRIP2(NC_, 4); else AGAN_STRIP2(NC_, 1); } while (0)
-        if (g.Cout <= 2) AGAN_STRIP(2);
-        else if (g.Cout == 3) AGAN_STRIP(3);
-        else AGAN_STRIP(4);
-#undef AGAN_STRIP
-#undef AGAN_STRIP2
-        return;
-    }
-    dim3 grid(cdiv(g.Mtot, 256), g.OS * g.OS);
-#define AGAN_SN(RS_, S_)                                                                                                                  \
-    do {                                                                                                                                  \
-        if (in_dtype == AGAN_DT_BF16) AGAN_LAUNCH((conv_small_n_kernel<RS_, S_, AGAN_DT_BF16>), grid, dim3(256), 0, st, in, wk, bias, out, g); \
-        else if (in_dtype == AGAN_DT_F16) AGAN_LAUNCH((conv_small_n_kernel<RS_, S_, AGAN_DT_F16>), grid, dim3(256), 0, st, in, wk, bias, out, g); \
-        else AGAN_LAUNCH((conv_small_n_kernel<RS_, S_>), grid, dim3(256), 0, st, in, wk, bias, out, g);                              \
-    } while (0)
-    switch (g.RS) {
-        case 1: AGAN_SN(1, 1); break;
-        case 4: AGAN_SN(4, 2); break;
-        case 9: AGAN_SN(9, 3); break;
-        default: AGAN_SN(16, 4); break;
-    }
-#undef AGAN_SN
+    const dim3 grid(cdiv(g.Mtot, 256), g.OS * g.OS);
+    with_dt(in_dtype, [&](auto DT) {
+        auto launch = [&](auto RS, auto S) { AGAN_LAUNCH((conv_small_n_kernel<RS(), S(), DT()>), grid, dim3(256), 0, st, in, wk, bias, out, g); };
+        switch (g.RS) {
+            case 1: launch(Int<1>{}, Int<1>{}); break;
+            case 4: launch(Int<4>{}, Int<2>{}); break;
+            case 9: launch(Int<9>{}, Int<3>{}); break;
+            default: launch(Int<16>{}, Int<4>{}); break;
+        }
+    });
 }
 
 bool small_n_wgrad_supported(const Geom& g) { return g.Cout <= 4 && g.OS == 1 && g.R == 3 && g.S == 3 && g.Mtot >= 4096; }
@@ -630,23 +602,16 @@ SmallWgradPlan plan_wgrad_small_n(const Geom& g) {
 }
 
 void launch_wgrad_small_n(const void* x, const float* dy, float* part, const Geom& g, const SmallWgradPlan& p, hipStream_t st, int x_dtype) {
-    if (strip_ok(g) && (p.pchunk & 255) == 0) {     // the plan's pixel chunks are whole waves of strips (multiples of 256 pixels)
-        const dim3 sg(g.Cin, p.nchunk);
-#define AGAN_STRIP(NC_)                                                                                                                   \
-    do {                                                                                                                                  \
-        if (x_dtype == AGAN_DT_BF16) AGAN_LAUNCH((wgrad_small_strip_kernel<AGAN_DT_BF16, NC_>), sg, dim3(256), 0, st, x, dy, part, g, p.pchunk >> 2, p.slab); \
-        else if (x_dtype == AGAN_DT_F16) AGAN_LAUNCH((wgrad_small_strip_kernel<AGAN_DT_F16, NC_>), sg, dim3(256), 0, st, x, dy, part, g, p.pchunk >> 2, p.slab); \
-        else AGAN_LAUNCH((wgrad_small_strip_kernel<AGAN_DT_F32, NC_>), sg, dim3(256), 0, st, x, dy, part, g, p.pchunk >> 2, p.slab);    \
-    } while (0)
-        if (g.Cout <= 2) AGAN_STRIP(2);
-        else if (g.Cout == 3) AGAN_STRIP(3);
-        else AGAN_STRIP(4);
-#undef AGAN_STRIP
-        return;
-    }
-    if (x_dtype == AGAN_DT_BF16) AGAN_LAUNCH((wgrad_small_n_kernel<9, 3, AGAN_DT_BF16>), dim3(g.Cin, p.nchunk), dim3(256), 0, st, x, dy, part, g, p.pchunk, p.slab);
-    else if (x_dtype == AGAN_DT_F16) AGAN_LAUNCH((wgrad_small_n_kernel<9, 3, AGAN_DT_F16>), dim3(g.Cin, p.nchunk), dim3(256), 0, st, x, dy, part, g, p.pchunk, p.slab);
-    else AGAN_LAUNCH((wgrad_small_n_kernel<9, 3>), dim3(g.Cin, p.nchunk), dim3(256), 0, st, x, dy, part, g, p.pchunk, p.slab);
+    const dim3 sg(g.Cin, p.nchunk);
+    with_dt(x_dtype, [&](auto DT) {
+        if (strip_ok(g) && (p.pchunk & 255) == 0) {     // the plan's pixel chunks are whole waves of strips (multiples of 256 pixels)
+            with_tier<2, 3, 4>(g.Cout, [&](auto NC) {
+                AGAN_LAUNCH((wgrad_small_strip_kernel<DT(), NC()>), sg, dim3(256), 0, st, x, dy, part, g, p.pchunk >> 2, p.slab);
+            });
+        } else {
+            AGAN_LAUNCH((wgrad_small_n_kernel<9, 3, DT()>), sg, dim3(256), 0, st, x, dy, part, g, p.pchunk, p.slab);
+        }
+    });
 }
 
 }  // namespace conv

@@ -400,54 +400,6 @@ __global__ __launch_bounds__(PC ? 512 : 256, 1) void conv_wgrad_rows_kernel(cons
     }
 }
 
-int pow2ceil_log_w(int v) {
-    int l = 0;
-    while ((1 << l) < v) ++l;
-    return l;
-}
-
-template <int ET, int NPL, int GK, bool CI2, bool X16, bool Y16, bool UPS>
-void launch_rows(const void* x, const void* dy, float* part, const Geom& g, const RowsPlan& p, hipStream_t st, const float* xs, const float* ys) {
-    // staging items per thread (16-byte LDS blocks): the plan checks the geometry against these
-    constexpr int NIX = ET == 2 ? (CI2 ? 16 : 8) : (GK == 2 ? 10 : (CI2 ? 8 : 4));
-    constexpr int NIY = ET == 2 ? (CI2 ? 9 : 18) : (GK == 2 ? 6 : (CI2 ? 5 : 10));
-    dim3 grid(p.jtiles, p.ngroups, p.psplit);
-#define AGAN_ROWS_LAUNCH(PC_)                                                                                                                         \
-    do {                                                                                                                                              \
-        static const hipError_t attr_ = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_rows_kernel<ET, NPL, GK, CI2, X16, Y16, NIX, NIY, PC_, UPS>), \
-                                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                                  \
-        (void)attr_;                                                                                                                                  \
-        AGAN_LAUNCH((conv_wgrad_rows_kernel<ET, NPL, GK, CI2, X16, Y16, NIX, NIY, PC_, UPS>), grid, dim3(PC_ ? 512 : 256), (size_t)p.smem_bytes, st, x, dy, \
-                           part, g, p, xs, ys);                                                                                                       \
-    } while (0)
-    if constexpr (NPL == 1 && ET != 2) {
-        if (p.pc) { AGAN_ROWS_LAUNCH(true); return; }
-    }
-    AGAN_ROWS_LAUNCH(false);
-#undef AGAN_ROWS_LAUNCH
-}
-template <int ET, int NPL, bool X16, bool Y16>
-void launch_rows_gk(const void* x, const void* dy, float* part, const Geom& g, const RowsPlan& p, hipStream_t st, const float* xs, const float* ys) {
-    if (p.gk == 2) {
-        if constexpr (ET != 2) launch_rows<ET, NPL, 2, false, X16, Y16, false>(x, dy, part, g, p, st, xs, ys);      // (fp32: conv3x3 only, see the plan)
-    } else if (p.ups) {
-        if constexpr (ET != 2) {
-            if (p.ci2) launch_rows<ET, NPL, 0, true, X16, Y16, true>(x, dy, part, g, p, st, xs, ys);
-            else launch_rows<ET, NPL, 0, false, X16, Y16, true>(x, dy, part, g, p, st, xs, ys);
-        }
-    } else {
-        if (p.ci2) launch_rows<ET, NPL, 0, true, X16, Y16, false>(x, dy, part, g, p, st, xs, ys);
-        else launch_rows<ET, NPL, 0, false, X16, Y16, false>(x, dy, part, g, p, st, xs, ys);
-    }
-}
-template <int ET>
-void launch_rows_dt(const void* x, const void* dy, float* part, const Geom& g, const RowsPlan& p, hipStream_t st, bool x16, bool y16) {
-    if (x16 && y16) launch_rows_gk<ET, 1, true, true>(x, dy, part, g, p, st, nullptr, nullptr);
-    else if (x16) launch_rows_gk<ET, 1, true, false>(x, dy, part, g, p, st, nullptr, nullptr);
-    else if (y16) launch_rows_gk<ET, 1, false, true>(x, dy, part, g, p, st, nullptr, nullptr);
-    else launch_rows_gk<ET, 1, false, false>(x, dy, part, g, p, st, nullptr, nullptr);
-}
-
 }  // namespace
 
 namespace agan {
@@ -492,8 +444,8 @@ RowsPlan plan_rows_wgrad(const Geom& gf, int prec, bool x16, bool y16, bool up) 
     if (f32 && (p.gk != 0 || g.OW < 16)) return p;
     p.ci2 = (p.gk == 0 && g.Cout <= 64) ? 1 : 0;
     const int tpl = 7;
-    p.twl = std::min(p.gk == 2 ? 5 : 6, pow2ceil_log_w(g.OW));
-    p.thl = std::min(tpl - p.twl, pow2ceil_log_w(g.OH));
+    p.twl = std::min(p.gk == 2 ? 5 : 6, pow2ceil_log(g.OW));
+    p.thl = std::min(tpl - p.twl, pow2ceil_log(g.OH));
     p.tbl = tpl - p.twl - p.thl;
     const int TW = 1 << p.twl, TH = 1 << p.thl, TB = 1 << p.tbl;
     p.tiles_x = cdiv(g.OW, TW);
@@ -517,7 +469,7 @@ RowsPlan plan_rows_wgrad(const Geom& gf, int prec, bool x16, bool y16, bool up) 
     p.pc = (!f32 && planes == 1 && 2 * p.plane_bytes <= 160 * 1024) ? 1 : 0;      // producer / consumer waves on two LDS buffers
     p.smem_bytes = (p.pc ? 2 : 1) * planes * p.plane_bytes;
     if (p.smem_bytes > 160 * 1024) return p;
-    p.nxbl = pow2ceil_log_w(IS * TW / PXB);
+    p.nxbl = pow2ceil_log(IS * TW / PXB);
     p.nxitems = nci * p.XRT << p.nxbl;
     p.NBY = TW / PXB + 2 * p.halo;
     p.nyitems = p.bj * TB * TH * p.NBY;
@@ -550,13 +502,34 @@ RowsPlan plan_rows_wgrad(const Geom& gf, int prec, bool x16, bool y16, bool up) 
 void launch_rows_wgrad(const void* x, const void* dy, float* part, const Geom& gf, const RowsPlan& p, int prec, hipStream_t st,
                        const float* x_scale, const float* dy_scale, bool x16, bool y16) {
     const Geom g = rows_geom(gf, p.ups != 0);
-    switch (prec) {
-        case AGAN_PREC_F32: launch_rows_gk<2, 1, false, false>(x, dy, part, g, p, st, nullptr, nullptr); break;
-        case AGAN_PREC_BF16: launch_rows_dt<0>(x, dy, part, g, p, st, x16, y16); break;
-        case AGAN_PREC_F16: launch_rows_dt<1>(x, dy, part, g, p, st, x16, y16); break;
-        case AGAN_PREC_BF16X3: launch_rows_gk<0, 2, false, false>(x, dy, part, g, p, st, nullptr, nullptr); break;
-        default: launch_rows_gk<1, 2, false, false>(x, dy, part, g, p, st, x_scale, dy_scale); break;      // AGAN_PREC_F16X3
-    }
+    const dim3 grid(p.jtiles, p.ngroups, p.psplit);
+    // the layer form f(Int<GK>, Bool<CI2>, Bool<UPS>): conv4x4 stride 2, or conv3x3 (plain or the upsample conv) on 32 or 2 x 32 channels
+    const auto with_form = [&](auto&& f) {
+        if (p.gk == 2) f(Int<2>{}, Bool<false>{}, Bool<false>{});
+        else with_bool(p.ci2, [&](auto CI2) { with_bool(p.ups, [&](auto UPS) { f(Int<0>{}, CI2, UPS); }); });
+    };
+    // ET 2: fp32 operands (conv3x3 only, see the plan)
+    const auto launch = [&](auto ET, auto NPL, const float* xs, const float* ys) {
+        constexpr bool kOne16 = NPL() == 1 && ET() != 2;      // one-plane 16-bit modes: typed storage, producer / consumer waves
+        with_form([&](auto GK, auto CI2, auto UPS) {
+        with_bool(kOne16 && x16, [&](auto X16) { with_bool(kOne16 && y16, [&](auto Y16) { with_bool(kOne16 && p.pc, [&](auto PC) {
+            if constexpr ((ET() != 2 || (GK() == 0 && !UPS())) && (kOne16 || !(X16() || Y16() || PC()))) {
+                // staging items per thread (16-byte LDS blocks): the plan checks the geometry against these
+                constexpr int NIX = ET() == 2 ? (CI2() ? 16 : 8) : (GK() == 2 ? 10 : (CI2() ? 8 : 4));
+                constexpr int NIY = ET() == 2 ? (CI2() ? 9 : 18) : (GK() == 2 ? 6 : (CI2() ? 5 : 10));
+                constexpr auto kernel = conv_wgrad_rows_kernel<ET(), NPL(), GK(), CI2(), X16(), Y16(), NIX, NIY, PC(), UPS()>;
+                allow_dynamic_lds<kernel>(160 * 1024);
+                AGAN_LAUNCH(kernel, grid, dim3(PC() ? 512 : 256), (size_t)p.smem_bytes, st, x, dy, part, g, p, xs, ys);
+            }
+        }); }); });
+        });
+    };
+    if (prec == AGAN_PREC_F32) return launch(Int<2>{}, Int<1>{}, nullptr, nullptr);
+    // the unscaled modes; whatever else comes here runs as AGAN_PREC_F16X3 on scaled operands
+    const bool plain = prec == AGAN_PREC_BF16 || prec == AGAN_PREC_F16 || prec == AGAN_PREC_BF16X3;
+    with_prec16(plain ? prec : AGAN_PREC_F16X3, [&](auto ET, auto NPL) {
+        if constexpr (NPL() <= 2) launch(ET, NPL, plain ? nullptr : x_scale, plain ? nullptr : dy_scale);
+    });
 }
 
 }  // namespace conv

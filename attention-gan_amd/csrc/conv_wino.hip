@@ -843,8 +843,7 @@ WinoPlan plan_wino(const Geom& g) {
 namespace {
 template <auto Kernel, WinoKind K>
 void launch_gather_kernel(dim3 grid, const float* in, const float* U, float* out, const Geom& g, const WinoPlan& p, hipStream_t st) {
-    static const hipError_t a = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, wino_traits(K).lds_cap);
-    (void)a;
+    allow_dynamic_lds<Kernel>(wino_traits(K).lds_cap);
     AGAN_LAUNCH(Kernel, grid, dim3(256), (size_t)p.smem_bytes, st, in, U, out, g, p);
 }
 }  // namespace
@@ -899,8 +898,7 @@ WinoWgradPlan plan_wino_wgrad(const Geom& g) {
 }
 
 void launch_wino_wgrad(const float* x, const float* dy, float* part, const Geom& g, const WinoWgradPlan& p, hipStream_t st) {
-    static const hipError_t a = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wino_wgrad_f32_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)a;
+    allow_dynamic_lds<conv_wino_wgrad_f32_kernel>(160 * 1024);
     AGAN_LAUNCH(conv_wino_wgrad_f32_kernel, dim3(p.jtiles * p.itiles * p.psplit), dim3(256), (size_t)p.smem_bytes, st, x, dy, part, g, p);
 }
 

@@ -8,6 +8,7 @@
 // conflict-free.  The backward recomputes the forward of its pair instead of storing B*B*(S*T + D*T) intermediates.
 // Region features are read coalesced along r (NCHW pixel axis) by the region-owning threads.
 #include "agan_common.h"
+#include "dispatch.h"
 
 using namespace agan;
 
@@ -873,19 +874,16 @@ __global__ __launch_bounds__(kNT) void func_attn_bwd_kernel(const float* __restr
 template <int TMAX, int DR = kNT>
 constexpr size_t pair_smem_bytes() { return sizeof(PairSmem<TMAX, DR>); }
 
-// shapes the MFMA pair kernels take (everything else runs the thread-per-row kernels); AGAN_PAIR_VALU=1 in the environment forces
-// the latter (A/B measurements)
-inline bool pair_mfma_ok(int D, int T, int S) {
-    static const bool off = [] { const char* v = getenv("AGAN_PAIR_VALU"); return v && v[0] == '1'; }();
-    return !off && T <= kMW && D <= kMD && (D & 63) == 0 && S <= kMS - 3 && S >= 16;
+// shapes the MFMA pair kernels take (everything else runs the thread-per-row kernels)
+inline bool pair_mfma_ok(int D, int T, int S) { return T <= kMW && D <= kMD && (D & 63) == 0 && S <= kMS - 3 && S >= 16; }
+// the form of the thread-per-row pair kernels for a shape: f(Int<TMAX>, Int<DR>)
+template <class F> void with_pair_form(int D, int T, F&& f) {
+    if (T <= 12 && D <= 256) f(Int<12>{}, Int<256>{});
+    else with_tier<16, 32>(T, [&](auto TM) { f(TM, Int<kNT>{}); });
 }
 
 // the [B][B] + 2[B] matrix of the contrastive kernel exceeds the default 64 KB dynamic-LDS limit at B >= 127 (kMaxB = 128)
-inline void allow_ce_smem() {      // (once per process: one process drives one GPU)
-    static const hipError_t attr_ = hipFuncSetAttribute(reinterpret_cast<const void*>(contrastive_ce_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                        (int)((kMaxB * kMaxB + 2 * kMaxB) * sizeof(float)));
-    (void)attr_;
-}
+inline void allow_ce_smem() { allow_dynamic_lds<contrastive_ce_kernel>((int)((kMaxB * kMaxB + 2 * kMaxB) * sizeof(float))); }
 
 }  // namespace
 
@@ -907,25 +905,18 @@ int agan_words_loss_fwd(const float* feat, const float* wemb, const int64_t* len
     float* featT = save + (size_t)B * B;              // [B][S][D], kept for the backward
     float* featP = pair_mfma_ok(D, T, S) ? featT + (size_t)B * D * S : nullptr;
     hipLaunchKernelGGL(feat_transpose_kernel, dim3(cdiv(featP ? kMS : S, 32), cdiv(D, 32), B), dim3(256), 0, st, feat, featT, featP, D, S, kMS);
-#define AGAN_PAIR_FWD(TM, DRR)                                                                                                          \
-    do {                                                                                                                               \
-        static const hipError_t attr_ = hipFuncSetAttribute(reinterpret_cast<const void*>(words_pair_fwd_kernel<TM, DRR>),             \
-                                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)pair_smem_bytes<TM, DRR>()); \
-        (void)attr_;                                                                                                                   \
-        const size_t smem_ = pair_smem_bytes<TM, DRR>();                                                                               \
-        hipLaunchKernelGGL((words_pair_fwd_kernel<TM, DRR>), grid, dim3(kNT), smem_, st, feat, featT, wemb, lens, gamma1,  \
-                           gamma2, gamma3, sim, attn_maps, B, D, T, S);                                                                \
-    } while (0)
     if (pair_mfma_ok(D, T, S)) {
-        static const hipError_t attr_ = hipFuncSetAttribute(reinterpret_cast<const void*>(words_pair_fwd_mfma_kernel),
-                                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(PairMfmaSmem<false>));
-        (void)attr_;
+        allow_dynamic_lds<words_pair_fwd_mfma_kernel>((int)sizeof(PairMfmaSmem<false>));
         hipLaunchKernelGGL(words_pair_fwd_mfma_kernel, grid, dim3(kNT), sizeof(PairMfmaSmem<false>), st, feat, featT, wemb, lens, gamma1, gamma2,
                            gamma3, sim, attn_maps, B, D, T, S);
-    } else if (T <= 12 && D <= 256) AGAN_PAIR_FWD(12, 256);
-    else if (T <= 16) AGAN_PAIR_FWD(16, kNT);
-    else AGAN_PAIR_FWD(32, kNT);
-#undef AGAN_PAIR_FWD
+    } else {
+        with_pair_form(D, T, [&](auto TM, auto DR) {
+            constexpr size_t smem = pair_smem_bytes<TM(), DR()>();
+            allow_dynamic_lds<words_pair_fwd_kernel<TM(), DR()>>((int)smem);
+            hipLaunchKernelGGL((words_pair_fwd_kernel<TM(), DR()>), grid, dim3(kNT), smem, st, feat, featT, wemb, lens, gamma1, gamma2, gamma3, sim,
+                               attn_maps, B, D, T, S);
+        });
+    }
     allow_ce_smem();
     hipLaunchKernelGGL(contrastive_ce_kernel, dim3(1), dim3(256), (size_t)(B * B + 2 * B) * sizeof(float), st, sim, class_ids, labels, lambda, loss, save, B);
     return check_launch("words_loss_fwd");
@@ -949,25 +940,18 @@ int agan_words_loss_bwd(const float* feat, const float* wemb, const int64_t* len
     float* part_f = static_cast<float*>(ws);
     float* part_w = part_f + (size_t)B * B * D * S;
     dim3 grid(B, B);
-#define AGAN_PAIR_BWD(TM, DRR)                                                                                                          \
-    do {                                                                                                                               \
-        static const hipError_t attr_ = hipFuncSetAttribute(reinterpret_cast<const void*>(words_pair_bwd_kernel<TM, DRR>),             \
-                                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)pair_smem_bytes<TM, DRR>()); \
-        (void)attr_;                                                                                                                   \
-        const size_t smem_ = pair_smem_bytes<TM, DRR>();                                                                               \
-        hipLaunchKernelGGL((words_pair_bwd_kernel<TM, DRR>), grid, dim3(kNT), smem_, st, feat, save + (size_t)B * B, wemb, lens, save,   \
-                           dloss, gamma1, gamma2, gamma3, part_f, part_w, B, D, T, S);                                                 \
-    } while (0)
     if (pair_mfma_ok(D, T, S)) {
-        static const hipError_t attr_ = hipFuncSetAttribute(reinterpret_cast<const void*>(words_pair_bwd_mfma_kernel),
-                                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(PairMfmaSmem<true>));
-        (void)attr_;
+        allow_dynamic_lds<words_pair_bwd_mfma_kernel>((int)sizeof(PairMfmaSmem<true>));
         hipLaunchKernelGGL(words_pair_bwd_mfma_kernel, grid, dim3(kNT), sizeof(PairMfmaSmem<true>), st, feat, save + (size_t)B * B, wemb, lens,
                            save, dloss, gamma1, gamma2, gamma3, part_f, part_w, B, D, T, S);
-    } else if (T <= 12 && D <= 256) AGAN_PAIR_BWD(12, 256);
-    else if (T <= 16) AGAN_PAIR_BWD(16, kNT);
-    else AGAN_PAIR_BWD(32, kNT);
-#undef AGAN_PAIR_BWD
+    } else {
+        with_pair_form(D, T, [&](auto TM, auto DR) {
+            constexpr size_t smem = pair_smem_bytes<TM(), DR()>();
+            allow_dynamic_lds<words_pair_bwd_kernel<TM(), DR()>>((int)smem);
+            hipLaunchKernelGGL((words_pair_bwd_kernel<TM(), DR()>), grid, dim3(kNT), smem, st, feat, save + (size_t)B * B, wemb, lens, save, dloss,
+                               gamma1, gamma2, gamma3, part_f, part_w, B, D, T, S);
+        });
+    }
     hipLaunchKernelGGL(pair_slab_sum_kernel, dim3(std::min(cdiv(D * S, 256), 64), B), dim3(256), 0, st, part_f, dfeat, B, D * S);
     hipLaunchKernelGGL(pair_slab_sum_kernel, dim3(std::min(cdiv(D * T, 256), 64), B), dim3(256), 0, st, part_w, dwemb, B, D * T);
     return check_launch("words_loss_bwd");
@@ -1004,13 +988,11 @@ int agan_func_attention_fwd(const float* query, const float* context, float gamm
     AGAN_REQUIRE(query && context && wctx && attn, "func_attention_fwd: null pointer");
     AGAN_REQUIRE(B >= 1 && D >= 1 && D <= kNT && S >= 1 && S <= kNT && L >= 1 && L <= 32, "func_attention: shape out of range");
     hipStream_t st = as_stream(stream);
-    if (L <= 16) {
-        static const hipError_t attr_16_ = hipFuncSetAttribute(reinterpret_cast<const void*>(func_attn_fwd_kernel<16>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pair_smem_bytes<16>()); (void)attr_16_;
-        hipLaunchKernelGGL((func_attn_fwd_kernel<16>), dim3(B), dim3(kNT), pair_smem_bytes<16>(), st, query, context, gamma1, scale, wctx, attn, D, L, S);
-    } else {
-        static const hipError_t attr_32_ = hipFuncSetAttribute(reinterpret_cast<const void*>(func_attn_fwd_kernel<32>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pair_smem_bytes<32>()); (void)attr_32_;
-        hipLaunchKernelGGL((func_attn_fwd_kernel<32>), dim3(B), dim3(kNT), pair_smem_bytes<32>(), st, query, context, gamma1, scale, wctx, attn, D, L, S);
-    }
+    with_tier<16, 32>(L, [&](auto TM) {
+        constexpr size_t smem = pair_smem_bytes<TM()>();
+        allow_dynamic_lds<func_attn_fwd_kernel<TM()>>((int)smem);
+        hipLaunchKernelGGL((func_attn_fwd_kernel<TM()>), dim3(B), dim3(kNT), smem, st, query, context, gamma1, scale, wctx, attn, D, L, S);
+    });
     return check_launch("func_attention_fwd");
 }
 
@@ -1019,13 +1001,11 @@ int agan_func_attention_bwd(const float* query, const float* context, const floa
     AGAN_REQUIRE(query && context && dquery && dcontext, "func_attention_bwd: null pointer");
     AGAN_REQUIRE(B >= 1 && D >= 1 && D <= kNT && S >= 1 && S <= kNT && L >= 1 && L <= 32, "func_attention_bwd: shape out of range");
     hipStream_t st = as_stream(stream);
-    if (L <= 16) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(func_attn_bwd_kernel<16>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pair_smem_bytes<16>());
-        hipLaunchKernelGGL((func_attn_bwd_kernel<16>), dim3(B), dim3(kNT), pair_smem_bytes<16>(), st, query, context, dwctx, dattn, gamma1, scale, dquery, dcontext, D, L, S);
-    } else {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(func_attn_bwd_kernel<32>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pair_smem_bytes<32>());
-        hipLaunchKernelGGL((func_attn_bwd_kernel<32>), dim3(B), dim3(kNT), pair_smem_bytes<32>(), st, query, context, dwctx, dattn, gamma1, scale, dquery, dcontext, D, L, S);
-    }
+    with_tier<16, 32>(L, [&](auto TM) {
+        constexpr size_t smem = pair_smem_bytes<TM()>();
+        allow_dynamic_lds<func_attn_bwd_kernel<TM()>>((int)smem);
+        hipLaunchKernelGGL((func_attn_bwd_kernel<TM()>), dim3(B), dim3(kNT), smem, st, query, context, dwctx, dattn, gamma1, scale, dquery, dcontext, D, L, S);
+    });
     return check_launch("func_attention_bwd");
 }
 

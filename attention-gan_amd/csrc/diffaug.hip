@@ -22,6 +22,7 @@
 #include <algorithm>
 
 #include "agan_common.h"
+#include "dispatch.h"
 
 namespace {
 using namespace agan;
@@ -263,15 +264,10 @@ size_t ws_bytes_of(long long N, const Geom& g) { return up16((size_t)N * g.P * s
 template <int V, bool BWD>
 void launch_apply(const Geom& g, unsigned blocks, hipStream_t st, const float* x0, const float* x1, int n0, const float* u,
                   const double* partial, float* out, int bps) {
-#define AGAN_APPLY(CC) \
-    hipLaunchKernelGGL((apply_kernel<CC, V, BWD>), dim3(blocks), dim3(kThreads), 0, st, x0, x1, n0, u, g, partial, out, bps)
-    switch (g.C) {
-        case 1: AGAN_APPLY(1); break;
-        case 2: AGAN_APPLY(2); break;
-        case 3: AGAN_APPLY(3); break;
-        default: AGAN_APPLY(4); break;
-    }
-#undef AGAN_APPLY
+    const auto launch = [&](auto CC) {
+        hipLaunchKernelGGL((apply_kernel<CC(), V, BWD>), dim3(blocks), dim3(kThreads), 0, st, x0, x1, n0, u, g, partial, out, bps);
+    };
+    if (!with_int<1, 2, 3>(g.C, launch)) launch(Int<4>{});
 }
 
 template <bool BWD>

@@ -12,6 +12,7 @@
 // Each row runs its own length: the forward direction t = 0 .. len-1, the reverse one t = len-1 .. 0, both from h = c = 0.
 // lstm_wgrad_kernel reduces dW_hh and db_hh over (b, t) in a fixed order, one thread per output element.
 #include "agan_common.h"
+#include "dispatch.h"
 
 using namespace agan;
 
@@ -233,6 +234,11 @@ unsigned blocks_for(size_t n) { return (unsigned)((n + kThreads - 1) / kThreads)
 
 bool lstm_shape_ok(int B, int T, int H, int D) { return B > 0 && T > 0 && (D == 1 || D == 2) && H >= 16 && H <= 128 && H % 16 == 0; }
 
+// f(Int<H>) for a hidden size; the recurrent kernels run 4 * H threads (one per gate row)
+template <class F> void with_hidden(int H, F&& f) {
+    if (!with_int<16, 32, 48, 64, 80, 96, 112>(H, f)) f(Int<128>{});
+}
+
 }  // namespace
 
 extern "C" {
@@ -254,18 +260,6 @@ int agan_embedding_bwd(const int64_t* ids, int ids_ld, const float* dy, float* d
     return check_launch("embedding_bwd");
 }
 
-#define AGAN_LSTM_DISPATCH(KERNEL, ...)                                                                                              \
-    switch (H) {                                                                                                                    \
-        case 16: hipLaunchKernelGGL(KERNEL<16>, grid, dim3(64), 0, as_stream(stream), __VA_ARGS__); break;                          \
-        case 32: hipLaunchKernelGGL(KERNEL<32>, grid, dim3(128), 0, as_stream(stream), __VA_ARGS__); break;                         \
-        case 48: hipLaunchKernelGGL(KERNEL<48>, grid, dim3(192), 0, as_stream(stream), __VA_ARGS__); break;                         \
-        case 64: hipLaunchKernelGGL(KERNEL<64>, grid, dim3(256), 0, as_stream(stream), __VA_ARGS__); break;                         \
-        case 80: hipLaunchKernelGGL(KERNEL<80>, grid, dim3(320), 0, as_stream(stream), __VA_ARGS__); break;                         \
-        case 96: hipLaunchKernelGGL(KERNEL<96>, grid, dim3(384), 0, as_stream(stream), __VA_ARGS__); break;                         \
-        case 112: hipLaunchKernelGGL(KERNEL<112>, grid, dim3(448), 0, as_stream(stream), __VA_ARGS__); break;                       \
-        default: hipLaunchKernelGGL(KERNEL<128>, grid, dim3(512), 0, as_stream(stream), __VA_ARGS__); break;                        \
-    }
-
 int agan_lstm_fwd(const float* xg0, const float* xg1, const float* whh0, const float* whh1, const float* bhh0, const float* bhh1,
                   const int32_t* lens, float* out, float* hN, float* gates, float* cells, int B, int T, int H, int D, void* stream) {
     AGAN_REQUIRE(lstm_shape_ok(B, T, H, D), "lstm_fwd: unsupported shape (B %d, T %d, H %d, D %d): needs B, T >= 1, D in {1, 2}, H a "
@@ -274,7 +268,10 @@ int agan_lstm_fwd(const float* xg0, const float* xg1, const float* whh0, const f
     AGAN_REQUIRE(D == 1 || (xg1 && whh1 && bhh1), "lstm_fwd: null pointer for the reverse direction");
     AGAN_REQUIRE((gates == nullptr) == (cells == nullptr), "lstm_fwd: gates and cells are saved together or not at all");
     const dim3 grid((unsigned)cdiv(B, kRows), (unsigned)D);
-    AGAN_LSTM_DISPATCH(lstm_fwd_kernel, xg0, xg1, whh0, whh1, bhh0, bhh1, lens, out, hN, gates, cells, B, T, D)
+    with_hidden(H, [&](auto HH) {
+        hipLaunchKernelGGL(lstm_fwd_kernel<HH()>, grid, dim3(4 * HH()), 0, as_stream(stream), xg0, xg1, whh0, whh1, bhh0, bhh1, lens, out, hN, gates,
+                           cells, B, T, D);
+    });
     return check_launch("lstm_fwd");
 }
 
@@ -285,7 +282,9 @@ int agan_lstm_bwd(const float* dout, const float* dhN, const float* whh0, const 
     AGAN_REQUIRE(whh0 && gates && cells && lens && dg0, "lstm_bwd: null pointer");
     AGAN_REQUIRE(D == 1 || (whh1 && dg1), "lstm_bwd: null pointer for the reverse direction");
     const dim3 grid((unsigned)cdiv(B, kRows), (unsigned)D);
-    AGAN_LSTM_DISPATCH(lstm_bwd_kernel, dout, dhN, whh0, whh1, gates, cells, lens, dg0, dg1, B, T, D)
+    with_hidden(H, [&](auto HH) {
+        hipLaunchKernelGGL(lstm_bwd_kernel<HH()>, grid, dim3(4 * HH()), 0, as_stream(stream), dout, dhN, whh0, whh1, gates, cells, lens, dg0, dg1, B, T, D);
+    });
     return check_launch("lstm_bwd");
 }
 

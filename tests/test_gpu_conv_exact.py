@@ -79,6 +79,10 @@ CASES = [
     ("same", 2, 8, 50, 50, 3, "b"),         # rows of 50 are not whole 4-pixel strips: conv_small_n <9, 3> / gather32 / wgrad_small_n
     ("down", 2, 3, 64, 64, 16, "b"),        # RGB input: gather32 (Cin <= 4) / conv_small_dgrad4_strip / conv_wgrad_f32
     ("down", 2, 16, 16, 16, 1, ""),         # conv_small_n <16, 4> / gather32 / conv_wgrad_f32
+    ("same", 1, 8, 64, 64, 2, ""),          # 2 channels: conv_small_strip <NC 2, channels split> / gather32 / wgrad_small_strip <NC 2>
+    ("same", 1, 5, 64, 64, 4, ""),          # 4 channels: conv_small_strip <NC 4, one channel group> / gather32 / wgrad_small_strip <NC 4>
+    ("down", 1, 2, 8, 8, 8, ""),            # data gradient to 2 channels: conv_small_dgrad4_strip <NC 2, channels split>
+    ("down", 1, 4, 8, 8, 6, ""),            # data gradient to 4 channels: conv_small_dgrad4_strip <NC 4, one channel group>
     ("linear", 6, 40, 1, 1, 1, "b"),        # nn.Linear to 1 output: linear_small_n / gather32 / conv_wgrad_f32
     ("linear", 5, 256, 1, 1, 100, "b"),     # nn.Linear 256 -> 100 as 1x1 maps, tiles spanning images: gather128 / gather128 / conv_wgrad_f32
     # ---- row-block gather, patch kernels, row-resident weight gradient -----------------------------------------------------------------------

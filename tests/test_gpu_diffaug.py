@@ -23,7 +23,7 @@ HF = importlib.import_module("attention-gan_amd.backend.functional")
 L = importlib.import_module("attention-gan_amd.backend.lib")
 
 DEV = torch.device("cuda", 0)
-SHAPES = [(1, 1, 5, 7), (3, 3, 5, 7), (2, 4, 24, 40), (5, 3, 64, 64), (2, 3, 128, 128)]
+SHAPES = [(1, 1, 5, 7), (3, 3, 5, 7), (2, 2, 6, 8), (2, 4, 24, 40), (5, 3, 64, 64), (2, 3, 128, 128)]
 IDS = ["x".join(map(str, s)) for s in SHAPES]
 ALMOST_ONE = 1.0 - 2.0 ** -24
 EDGES = (0.0, 0.5, ALMOST_ONE)         # translation: -S, 0, +S; cutout: clipped at the low border, fully inside, clipped at the high border

@@ -255,11 +255,11 @@ def test_attention_all_masked_row_is_nan_and_metric_shape():
     assert_close(attn[:1], ref_attn, TOL.tight, "attn @128x128")
 
 
-@pytest.mark.parametrize("C,T_,H,W", [(40, 16, 9, 9), (64, 1, 20, 15), (8, 7, 4, 4), (32, 10, 64, 64), (17, 20, 6, 5)])
+@pytest.mark.parametrize("C,T_,H,W", [(40, 16, 9, 9), (64, 1, 20, 15), (8, 7, 4, 4), (32, 10, 64, 64), (17, 20, 6, 5), (16, 40, 5, 6)])
 def test_attention_backward_shape_limits_vs_oracle(C, T_, H, W):
     """AttentionModule forward + backward against the oracle at the limits of the backward's MFMA pixel reduction (seq_len <= 16):
     channel counts that do not fill the last 16-channel chunk, the 64-channel maximum, one word, pixel counts that leave most
-    of a 256-pixel workgroup dead, the metric's 64x64 stage; and one seq_len > 16 case on the butterfly path."""
+    of a 256-pixel workgroup dead, the metric's 64x64 stage; and one case each of 16 < seq_len <= 32 and seq_len > 32 on the butterfly path."""
     gen = torch.Generator().manual_seed(C * 31 + T_)
     B, E = 3, 24
     m = ATT.AttentionModule(C, E).to(DEV)
@@ -310,6 +310,18 @@ def test_func_attention_backward_vs_golden():
         (ref * probe(ref.shape, 0.3 + 0.1 * which)).sum().backward()
         assert_close(q2.grad, qo.grad, TOL.tight, f"d query (output {which} only)")
         assert_close(c2.grad, co.grad, TOL.tight, f"d context (output {which} only)")
+    # 17..32 query positions: the second form of both kernels (the fixture's 7 take the 16-position one); a 3 x 5 context
+    gen = torch.Generator().manual_seed(20)
+    query, context = torch.randn(2, 32, 20, generator=gen), torch.randn(2, 32, 3, 5, generator=gen)
+    q3, c3 = query.to(DEV).requires_grad_(True), context.to(DEV).requires_grad_(True)
+    qo, co = query.clone().requires_grad_(True), context.clone().requires_grad_(True)
+    (w3, a3), (wo, ao) = ATT.func_attention(q3, c3, 4.0), O.func_attention(qo, co, 4.0)
+    ((w3 * probe(w3.shape, 0.3).to(DEV)).sum() + (a3 * probe(a3.shape, 0.4).to(DEV)).sum()).backward()
+    ((wo * probe(wo.shape, 0.3)).sum() + (ao * probe(ao.shape, 0.4)).sum()).backward()
+    assert_close(w3, wo, TOL.tight, "wctx (20 positions)")
+    assert_close(a3, ao, TOL.tight, "attn (20 positions)")
+    assert_close(q3.grad, qo.grad, TOL.tight, "d query (20 positions)")
+    assert_close(c3.grad, co.grad, TOL.tight, "d context (20 positions)")
 
 
 # ------------------------------------------------------------------------------------------------ generator / discriminators

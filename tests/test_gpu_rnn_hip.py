@@ -60,6 +60,11 @@ CASES = {
     "D1": (24, 10, 32, 64, False, "random", 10),
     "H16": (6, 7, 24, 32, True, "random", 7),
     "wide-captions": (9, 14, 32, 64, True, "short", 14),
+    # the hidden sizes the recurrent kernels are built for besides the 128 / 64 / 16 / 32 above (one direction: H = nhidden)
+    "H48": (2, 3, 24, 48, False, "full", 3),
+    "H80": (2, 3, 24, 80, False, "full", 3),
+    "H96": (2, 3, 24, 96, False, "full", 3),
+    "H112": (2, 3, 24, 112, False, "full", 3),
 }
 
 
