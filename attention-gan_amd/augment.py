@@ -2,10 +2,15 @@
 include/agan.h (agan_diffaug_*) restated in plain torch ops.
 
 `diffaug_reference` is the ORACLE of the HIP kernels (backend/functional.py: diffaug), not a second product path: any dtype, any
-device, differentiable by autograd.  The training step never calls it."""
+device, differentiable by autograd.  The training step never calls it.
+
+Adaptive discriminator augmentation (Karras et al. 2020): with q and p every stage is applied per sample with probability p (the
+gated entries agan_diffaug_gated_*), `AdaController` keeps p in device memory and steers it by two small HIP launches
+(agan_ada_observe / agan_ada_update), and `ada_reference` restates the controller in Python integers and doubles, as its oracle."""
 from __future__ import annotations
 
-from typing import Optional, Tuple, Union
+import struct
+from typing import Dict, Optional, Tuple, Union
 
 import torch
 from torch import Tensor
@@ -72,16 +77,36 @@ def color_terms(x: Tensor, u: Tensor):
     return v, w, M, c * (w - M) + M
 
 
-def diffaug_reference(x: Tensor, u: Tensor, policy: Union[str, int, None]) -> Tensor:
+def gate_masks(q: Tensor, p) -> Tensor:
+    """bool [N, 3]: stage k of sample n passes its gate iff q[n, k] < p, compared in fp32 (include/agan.h); p: a number or a
+    one-element tensor.  A NaN p passes nothing."""
+    q32 = q.detach().to(torch.float32)
+    p32 = p.detach().to(device=q32.device, dtype=torch.float32).reshape(()) if isinstance(p, Tensor) else torch.tensor(float(p), dtype=torch.float32, device=q32.device)
+    return q32[:, :3] < p32
+
+
+def diffaug_reference(x: Tensor, u: Tensor, policy: Union[str, int, None], q: Optional[Tensor] = None, p=None) -> Tensor:
     """The transform of include/agan.h on x [N, C, H, W] with uniforms u [N, 8]: colour, translation, cutout, each if its bit is set.
-    The integer offsets come from the fp32 values of u (products formed in fp32) whatever x's dtype is."""
+    The integer offsets come from the fp32 values of u (products formed in fp32) whatever x's dtype is.
+
+    With q [N, 4] and p (the gated entries, agan_diffaug_gated_*): stage k runs for sample n iff its bit is set and q[n, k] < p in
+    fp32; a sample whose gate is off keeps the stage's input, selected by torch.where, so its values pass unchanged."""
     policy = parse_policy(policy)
     if x.dim() != 4 or u.dim() != 2 or u.shape[0] != x.shape[0] or u.shape[1] != 8:
         raise ValueError(f"diffaug_reference: expected x [N, C, H, W] and u [N, 8], got {tuple(x.shape)} and {tuple(u.shape)}")
+    if (q is None) != (p is None):
+        raise ValueError("diffaug_reference: q and p come together or not at all")
     N, C, H, W = x.shape
+    if q is not None and (q.dim() != 2 or tuple(q.shape) != (N, 4)):
+        raise ValueError(f"diffaug_reference: q must be [{N}, 4], got {tuple(q.shape)}")
+    gates = None if q is None else gate_masks(q, p).to(x.device)
+
+    def gated(k: int, staged: Tensor, before: Tensor) -> Tensor:
+        return staged if gates is None else torch.where(gates[:, k].view(N, 1, 1, 1), staged, before)
+
     z = x
     if policy & COLOR:
-        z = color_terms(z, u)[3]
+        z = gated(0, color_terms(z, u)[3], z)
     ys = torch.arange(H, device=x.device).view(1, H, 1)
     xs = torch.arange(W, device=x.device).view(1, 1, W)
     if policy & TRANSLATION:
@@ -90,11 +115,139 @@ def diffaug_reference(x: Tensor, u: Tensor, policy: Union[str, int, None]) -> Te
         inside = ((sy >= 0) & (sy < H) & (sx >= 0) & (sx < W)).view(N, 1, H, W)
         rows = sy.clamp(0, H - 1).view(N, 1, H, 1).expand(N, C, H, W)
         cols = sx.clamp(0, W - 1).view(N, 1, 1, W).expand(N, C, H, W)
-        z = torch.where(inside, z.gather(2, rows).gather(3, cols), torch.zeros((), dtype=z.dtype, device=z.device))
+        z = gated(1, torch.where(inside, z.gather(2, rows).gather(3, cols), torch.zeros((), dtype=z.dtype, device=z.device)), z)
     if policy & CUTOUT:
         oy, ox = cutout_offsets(u, H, W)
         ch, cw = int(0.5 * H + 0.5), int(0.5 * W + 0.5)
         y0, x0 = (oy - ch // 2).view(N, 1, 1), (ox - cw // 2).view(N, 1, 1)
         cut = ((ys >= y0) & (ys < y0 + ch) & (xs >= x0) & (xs < x0 + cw)).view(N, 1, H, W)
-        z = torch.where(cut, torch.zeros((), dtype=z.dtype, device=z.device), z)
+        z = gated(2, torch.where(cut, torch.zeros((), dtype=z.dtype, device=z.device), z), z)
     return z
+
+
+# --------------------------------------------------------------------------------------------------------------
+# the controller of p (include/agan.h: agan_ada_observe / agan_ada_update)
+# --------------------------------------------------------------------------------------------------------------
+ADA_WORDS = ("sum", "count", "calls", "adjustments", "p", "r_t")           # words 0..5 of the device state, in order
+
+
+def _f32(v: float) -> float:
+    """v rounded to fp32, as a Python float"""
+    return struct.unpack("<f", struct.pack("<f", float(v)))[0]
+
+
+def ada_new_state(p: float = 0.0) -> Dict:
+    return {"sum": 0, "count": 0, "calls": 0, "adjustments": 0, "p": _f32(p), "r_t": 0.0}
+
+
+def ada_tally(score, threshold: float = 0.5) -> Tuple[int, int]:
+    """(#(score > threshold) - #(score < threshold), n) of agan_ada_observe, in Python integers; a NaN counts in n only.  The
+    comparison is the fp32 one: scores and threshold are taken at their fp32 values."""
+    vals = torch.as_tensor(score).detach().to(torch.float32).reshape(-1).cpu()
+    t = torch.tensor(float(threshold), dtype=torch.float32)
+    return int((vals > t).sum()) - int((vals < t).sum()), int(vals.numel())
+
+
+def ada_reference(state: Dict, slots, interval: int, target: float, rate: float, p_max: float) -> Dict:
+    """One agan_ada_update call in plain Python integers and doubles -- the ORACLE of the kernel, not a product path.  `state`: the
+    dict of ada_new_state (words 0..5), changed in place and returned; `slots`: one (tally, n) pair per discriminator as ada_tally
+    gives them, None or n == 0 for a discriminator that has not observed since the last call."""
+    for slot in slots:
+        if slot is not None and int(slot[1]) > 0:
+            state["sum"] += int(slot[0])
+            state["count"] += int(slot[1])
+    state["calls"] += 1
+    if state["calls"] < int(interval):
+        return state
+    total, count = state["sum"], state["count"]
+    state["sum"] = state["count"] = state["calls"] = 0
+    if count <= 0:
+        return state
+    r = float(total) / float(count)
+    d = float(count) * float(rate)
+    p = float(state["p"])
+    if r > target:
+        p = p + d
+    elif r < target:
+        p = p - d
+    p = min(max(p, 0.0), float(p_max))
+    state["p"], state["r_t"] = _f32(p), _f32(r)
+    state["adjustments"] += 1
+    return state
+
+
+class AdaController:
+    """The augmentation probability p in device memory and the two launches that steer it (adaptive discriminator augmentation,
+    Karras et al. 2020): observe(i, score) tallies sign(D_i(real) - threshold) into discriminator i's slot, update() folds the slots
+    into the window and, every `interval` calls, moves p by  (real scores in the window) * rate  towards r_t > target.  `self.p` is
+    a float32 VIEW of the state's word 4: what backend.functional.diffaug is handed; nothing is read on the host until sync().
+
+    rate = 1 / (kimg * 1000 * n_discriminators): every real image is scored by each discriminator, so count * rate is
+    "real images seen in the window / (kimg * 1000)", the paper's step.  With target=None p is a constant: observe() and update()
+    launch nothing.  The configuration is the constructor's; the state dicts carry words 0..5 only."""
+
+    def __init__(self, device, n_discriminators: int, p: float = 0.0, target: Optional[float] = None, interval: int = 4,
+                 kimg: float = 500.0, p_max: float = 1.0, threshold: float = 0.5):
+        if not 1 <= int(n_discriminators) <= 4:
+            raise ValueError(f"AdaController: {n_discriminators} discriminators outside 1..4")
+        if not 0.0 < float(p_max) <= 1.0:
+            raise ValueError(f"AdaController: p_max {p_max} outside (0, 1]")
+        if not 0.0 <= float(p) <= float(p_max):
+            raise ValueError(f"AdaController: p {p} outside [0, p_max = {p_max}]")
+        if int(interval) < 1:
+            raise ValueError(f"AdaController: interval {interval} below 1")
+        if not float(kimg) > 0.0:
+            raise ValueError(f"AdaController: kimg {kimg} is not positive")
+        if target is not None and not -1.0 <= float(target) <= 1.0:
+            raise ValueError(f"AdaController: target {target} outside [-1, 1], the range of r_t")
+        self.n, self.interval, self.p_max, self.threshold = int(n_discriminators), int(interval), float(p_max), float(threshold)
+        self.target = None if target is None else float(target)
+        self.kimg = float(kimg)
+        self.rate = 1.0 / (self.kimg * 1000.0 * self.n)
+        self.p0 = _f32(p)
+        self.state = torch.zeros(16, dtype=torch.int32, device=device)
+        self.p = self.state[4:5].view(torch.float32)
+        self.p.fill_(self.p0)
+
+    @property
+    def adaptive(self) -> bool:
+        return self.target is not None
+
+    def slot(self, i: int) -> Tensor:
+        if not 0 <= i < self.n:
+            raise IndexError(f"AdaController: discriminator {i} of {self.n}")
+        return self.state[8 + 2 * i:10 + 2 * i]
+
+    def observe(self, i: int, score: Tensor) -> None:
+        if self.adaptive:
+            from .backend import functional as HF
+            HF.ada_observe_(score, self.slot(i), self.threshold)
+
+    def update(self) -> None:
+        if self.adaptive:
+            from .backend import functional as HF
+            HF.ada_update_(self.state, self.n, self.interval, self.target, self.rate, self.p_max)
+
+    def _words(self) -> Dict:
+        w = self.state[:6].cpu()                            # the one host read
+        f = w[4:6].view(torch.float32)
+        return {"sum": int(w[0]), "count": int(w[1]), "calls": int(w[2]), "adjustments": int(w[3]), "p": float(f[0]), "r_t": float(f[1])}
+
+    def sync(self) -> Dict:
+        w = self._words()
+        return {"p": w["p"], "r_t": w["r_t"], "adjustments": w["adjustments"]}
+
+    def state_dict(self) -> Dict:
+        return self._words()
+
+    def load_state_dict(self, sd: Dict) -> None:
+        """Words 0..5; the observation slots restart empty.  The configuration stays the constructor's."""
+        w = torch.zeros(16, dtype=torch.int32)
+        for k, name in enumerate(ADA_WORDS[:4]):
+            w[k] = int(sd[name])
+        w[4:6].view(torch.float32).copy_(torch.tensor([float(sd["p"]), float(sd["r_t"])], dtype=torch.float32))
+        self.state.copy_(w)
+
+    def reset(self) -> None:
+        self.state.zero_()
+        self.p.fill_(self.p0)

@@ -1747,18 +1747,21 @@ def image_prep(planes, rows: Optional[Tensor], flip: Optional[Tensor], out=None)
 # --------------------------------------------------------------------------------------------------------------
 # differentiable augmentation (augment.py; include/agan.h: agan_diffaug_*)
 # --------------------------------------------------------------------------------------------------------------
-def _diffaug_bwd(dy: Tensor, u: Tensor, policy: int) -> Tensor:
+def _diffaug_bwd(dy: Tensor, u: Tensor, policy: int, q: Optional[Tensor] = None, p: Optional[Tensor] = None) -> Tensor:
     N, C, H, W = dy.shape
     dx = torch.empty_like(dy)
     nbytes = L.load().agan_diffaug_ws_bytes(N, C, H, W)
     ws, wsp = _ws(nbytes, dy)
-    _kmeans_call("agan_diffaug_bwd", _p(dy), _p(u), policy, _p(dx), N, C, H, W, wsp, nbytes, _stream())
+    if q is None:
+        _kmeans_call("agan_diffaug_bwd", _p(dy), _p(u), policy, _p(dx), N, C, H, W, wsp, nbytes, _stream())
+    else:
+        _kmeans_call("agan_diffaug_gated_bwd", _p(dy), _p(u), _p(q), _p(p), policy, _p(dx), N, C, H, W, wsp, nbytes, _stream())
     return dx
 
 
 class _DiffAugFn(Function):
     @staticmethod
-    def forward(ctx, u, policy, *xs):
+    def forward(ctx, u, policy, q, p, *xs):
         x0 = xs[0]
         x1 = xs[1] if len(xs) > 1 else None
         n0, C, H, W = x0.shape
@@ -1766,32 +1769,48 @@ class _DiffAugFn(Function):
         y = torch.empty((n0 + n1, C, H, W), dtype=torch.float32, device=x0.device)
         nbytes = L.load().agan_diffaug_ws_bytes(n0 + n1, C, H, W)
         ws, wsp = _ws(nbytes, x0)
-        _kmeans_call("agan_diffaug_fwd", _p(x0), _p(x1), n0, n1, _p(u), policy, _p(y), C, H, W, wsp, nbytes, _stream())
-        ctx.save_for_backward(u)
+        if q is None:
+            _kmeans_call("agan_diffaug_fwd", _p(x0), _p(x1), n0, n1, _p(u), policy, _p(y), C, H, W, wsp, nbytes, _stream())
+        else:
+            _kmeans_call("agan_diffaug_gated_fwd", _p(x0), _p(x1), n0, n1, _p(u), _p(q), _p(p), policy, _p(y), C, H, W, wsp, nbytes,
+                         _stream())
+        # (p is kept as the tensor it is, not through save_for_backward: the controller advances it in place between the forward
+        # and the next step, never between a forward and ITS backward, and a version check would refuse the graph-replayed update)
+        if q is None:
+            ctx.save_for_backward(u)
+        else:
+            ctx.save_for_backward(u, q)
+        ctx.p = p
         ctx.policy, ctx.sizes = policy, (n0, n1)
         return y
 
     @staticmethod
     @once_differentiable
     def backward(ctx, dy):
-        u, = ctx.saved_tensors
+        u, q = ctx.saved_tensors if len(ctx.saved_tensors) == 2 else (ctx.saved_tensors[0], None)
+        p = ctx.p
         n0, n1 = ctx.sizes
-        need = list(ctx.needs_input_grad[2:])
+        need = list(ctx.needs_input_grad[4:])
         dy = _dev(dy, "diffaug dy")
         if all(need):                                     # one call over the whole batch, split per source
-            dx = _diffaug_bwd(dy, u, ctx.policy)
+            dx = _diffaug_bwd(dy, u, ctx.policy, q, p)
             grads = [dx] if n1 == 0 else [dx[:n0], dx[n0:]]
         else:                                             # only the samples of the source that asks
             bounds = [(0, n0), (n0, n0 + n1)]
-            grads = [_diffaug_bwd(dy[lo:hi], u[lo:hi], ctx.policy) if want else None for want, (lo, hi) in zip(need, bounds)]
-        return (None, None, *grads)
+            grads = [_diffaug_bwd(dy[lo:hi], u[lo:hi], ctx.policy, None if q is None else q[lo:hi], p) if want else None
+                     for want, (lo, hi) in zip(need, bounds)]
+        return (None, None, None, None, *grads)
 
 
-def diffaug(xs, u: Tensor, policy: int) -> Tensor:
+def diffaug(xs, u: Tensor, policy: int, q: Optional[Tensor] = None, p: Optional[Tensor] = None) -> Tensor:
     """DiffAugment of include/agan.h (agan_diffaug_fwd; augment.diffaug_reference states it in torch ops) on one [N, C, H, W] tensor
     or a PAIR of equal-shaped ones, whose samples come out concatenated in ONE tensor (the [real; fake] batch of
     NonSaturatingDiscLoss, written by the augmentation itself).  u: [N, 8] uniforms in [0, 1) for all samples of the result, policy:
-    the bit mask of augment.parse_policy.  Differentiable in the images: the backward kernel runs for the sources that require grad."""
+    the bit mask of augment.parse_policy.  Differentiable in the images: the backward kernel runs for the sources that require grad.
+
+    With `q` [N, 4] (uniforms) and `p` (a ONE-element fp32 device tensor) the gated entries run (agan_diffaug_gated_*): stage k of
+    sample n is applied iff its policy bit is set and q[n, k] < p.  p is read by the kernels when they run -- forward and backward read
+    the value of THEIR moment -- so a controller may change it in place between steps, inside a captured graph too."""
     xs = (xs,) if isinstance(xs, Tensor) else tuple(xs)
     if not 1 <= len(xs) <= 2:
         raise ValueError(f"diffaug: expected one tensor or a pair, got {len(xs)}")
@@ -1802,7 +1821,40 @@ def diffaug(xs, u: Tensor, policy: int) -> Tensor:
     u = _dev(u, "diffaug u")
     if u.device != xs[0].device or tuple(u.shape) != (n, 8):
         raise ValueError(f"diffaug: u must be [{n}, 8] on {xs[0].device}, got {tuple(u.shape)} on {u.device}")
-    return _DiffAugFn.apply(u, int(policy), *xs)
+    if (q is None) != (p is None):
+        raise ValueError("diffaug: q and p come together (the gated form) or not at all")
+    if q is not None:
+        q = _dev(q, "diffaug q")
+        if q.device != xs[0].device or tuple(q.shape) != (n, 4):
+            raise ValueError(f"diffaug: q must be [{n}, 4] on {xs[0].device}, got {tuple(q.shape)} on {q.device}")
+        if not p.is_cuda or p.device != xs[0].device or p.dtype != torch.float32 or p.numel() != 1:
+            raise ValueError(f"diffaug: p must be a one-element float32 tensor on {xs[0].device}, got {p.dtype} {tuple(p.shape)} on {p.device}")
+    return _DiffAugFn.apply(u, int(policy), q, p, *xs)
+
+
+# --------------------------------------------------------------------------------------------------------------
+# the controller of the augmentation probability (augment.py: AdaController; include/agan.h: agan_ada_*)
+# --------------------------------------------------------------------------------------------------------------
+def _ada_words(t: Tensor, words: int, what: str) -> None:
+    if not t.is_cuda or t.dtype != torch.int32 or not t.is_contiguous() or t.numel() < words:
+        raise L.AganError(f"{what} must be a contiguous int32 device tensor of at least {words} elements")
+
+
+def ada_observe_(score: Tensor, slot_view: Tensor, threshold: float = 0.5) -> None:
+    """slot_view[0] = #(score > threshold) - #(score < threshold), slot_view[1] = score.numel(), written by one small launch on the
+    current stream (include/agan.h: agan_ada_observe).  slot_view: the two int32 words of one discriminator's observation slot."""
+    score = _dev(score.detach(), "ada_observe_ score").reshape(-1)
+    _ada_words(slot_view, 2, "ada_observe_: the slot")
+    if slot_view.device != score.device:
+        raise L.AganError(f"ada_observe_: scores on {score.device}, slot on {slot_view.device}")
+    _kmeans_call("agan_ada_observe", _p(score), int(score.numel()), float(threshold), _p(slot_view), _stream())
+
+
+def ada_update_(state: Tensor, nslots: int, interval: int, target: float, rate: float, p_max: float) -> None:
+    """One controller call on the 16-word state (include/agan.h: agan_ada_update): fold the observation slots into the window; at the
+    end of every `interval`-th call move p (word 4) by count * rate towards r_t > target.  One one-thread launch, no host read."""
+    _ada_words(state, L.ADA_STATE_WORDS, "ada_update_: state")
+    _kmeans_call("agan_ada_update", _p(state), int(nslots), int(interval), float(target), float(rate), float(p_max), _stream())
 
 
 # --------------------------------------------------------------------------------------------------------------

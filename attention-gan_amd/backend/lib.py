@@ -22,7 +22,8 @@ DT_F32, DT_BF16, DT_F16 = 0, 1, 2          # include/agan.h: AGAN_DT_* (storage 
 AMAX_SLOT = 256        # floats per amax slot (include/agan.h: AGAN_AMAX_SLOT)
 EINVAL, EWORKSPACE = -1, -2                # include/agan.h: AGAN_EINVAL, AGAN_EWORKSPACE
 DIFFAUG_COLOR, DIFFAUG_TRANSLATION, DIFFAUG_CUTOUT = 1, 2, 4      # include/agan.h: AGAN_DIFFAUG_*
-ABI_VERSION = 101      # include/agan.h: AGAN_VERSION this binding was written against (argument lists changed between versions)
+ADA_STATE_WORDS, ADA_P_WORD, ADA_SLOT_WORD = 16, 4, 8           # include/agan.h: AGAN_ADA_*
+ABI_VERSION = 101     # include/agan.h: AGAN_VERSION this binding was written against (argument lists changed between versions)
 
 
 class ConvGeom(Structure):
@@ -162,6 +163,10 @@ _SIGNATURES = {
     "agan_diffaug_ws_bytes": (c_size_t, [c_int] * 4),
     "agan_diffaug_fwd": (c_int, [_P, _P, c_int, c_int, _P, c_int, _P, c_int, c_int, c_int, _P, c_size_t, _P]),
     "agan_diffaug_bwd": (c_int, [_P, _P, c_int, _P, c_int, c_int, c_int, c_int, _P, c_size_t, _P]),
+    "agan_diffaug_gated_fwd": (c_int, [_P, _P, c_int, c_int, _P, _P, _P, c_int, _P, c_int, c_int, c_int, _P, c_size_t, _P]),
+    "agan_diffaug_gated_bwd": (c_int, [_P, _P, _P, _P, c_int, _P, c_int, c_int, c_int, c_int, _P, c_size_t, _P]),
+    "agan_ada_observe": (c_int, [_P, c_int, c_float, _P, _P]),
+    "agan_ada_update": (c_int, [_P, c_int, c_int, c_double, c_double, c_double, _P]),
     "agan_ema_plan": (c_int, [_P, c_int]),
     "agan_ema_update": (c_int, [_P, c_int, c_int, _P, c_double, c_int, _P]),
     "agan_adam_step": (c_int, [_P, _P, _P, _P, c_size_t, _P, c_double, c_double, c_double, c_double, c_float, _P]),

@@ -19,6 +19,11 @@
 // Colour arithmetic, forward:  v = x + b;  m = mean_C(v);  w = fma(s, v, (1 - s) m);  z = fma(c, w, (1 - c) M)   -- the issue's
 // s (v - m) + m and c (w - M) + M regrouped so that s = 1 and c = 1 are the identity bit for bit.  Backward:  dw = fma(c, g, (1 - c) G),
 // dx = fma(s, dw, (1 - s) mean_C(dw)).  No atomics, no allocation, no synchronisation; the workspace is written before it is read.
+//
+// The gated entries (agan_diffaug_gated_*) are the same kernels with GATED = true: a sample's policy is the call's policy with the bit
+// of every stage k cleared whose uniform q[n][k] is not below *p (three scalar loads and compares per workgroup -- a workgroup lies
+// inside one sample, so the gate is wave-uniform).  Whatever the ungated kernels decide from the policy, these decide from that
+// per-sample mask: the sum workgroups of a sample without colour return before loading, and its apply workgroups never touch the partials.
 #include <algorithm>
 
 #include "agan_common.h"
@@ -47,22 +52,43 @@ struct Sample {
 
 __device__ __forceinline__ int offset_of(float u, int count, int top) { return min(max((int)(u * (float)count), 0), top); }
 
-__device__ __forceinline__ Sample sample_of(const Geom& g, const float* __restrict__ u, int n) {
+// the pointers of the gated entries (unused, and null, where GATED is false)
+struct Gate {
+    const float* q;                    // [N, 4] uniforms
+    const float* p;                    // one fp32, device memory
+};
+
+// sample n's own policy: the stages whose bit is set AND whose uniform lies below *p (fp32 compare; false for a NaN)
+template <bool GATED>
+__device__ __forceinline__ int policy_of(const Geom& g, const Gate& gate, int n) {
+    if constexpr (!GATED) return g.policy;
+    else {
+        const float p = *gate.p;
+        const float* qn = gate.q + (size_t)n * 4;
+        int pol = 0;
+        if (qn[0] < p) pol |= AGAN_DIFFAUG_COLOR;
+        if (qn[1] < p) pol |= AGAN_DIFFAUG_TRANSLATION;
+        if (qn[2] < p) pol |= AGAN_DIFFAUG_CUTOUT;
+        return pol & g.policy;
+    }
+}
+
+__device__ __forceinline__ Sample sample_of(const Geom& g, const float* __restrict__ u, int n, int policy) {
     const float* un = u + (size_t)n * 8;
     Sample p;
     p.ty = p.tx = 0;
     p.cy0 = p.cy1 = p.cx0 = p.cx1 = 0;
     p.b = 0.f, p.s = 1.f, p.c = 1.f;
-    if (g.policy & AGAN_DIFFAUG_COLOR) {
+    if (policy & AGAN_DIFFAUG_COLOR) {
         p.b = un[0] - 0.5f;
         p.s = 2.f * un[1];
         p.c = un[2] + 0.5f;
     }
-    if (g.policy & AGAN_DIFFAUG_TRANSLATION) {
+    if (policy & AGAN_DIFFAUG_TRANSLATION) {
         p.ty = offset_of(un[3], 2 * g.Sy + 1, 2 * g.Sy) - g.Sy;
         p.tx = offset_of(un[4], 2 * g.Sx + 1, 2 * g.Sx) - g.Sx;
     }
-    if (g.policy & AGAN_DIFFAUG_CUTOUT) {
+    if (policy & AGAN_DIFFAUG_CUTOUT) {
         const int oy = offset_of(un[5], g.H + 1 - g.ch % 2, g.H - g.ch % 2);
         const int ox = offset_of(un[6], g.W + 1 - g.cw % 2, g.W - g.cw % 2);
         p.cy0 = max(0, oy - g.ch / 2), p.cy1 = min(g.H, oy - g.ch / 2 + g.ch);
@@ -83,17 +109,20 @@ __device__ __forceinline__ const float* sample_ptr(const float* x0, const float*
 }
 
 // partial[n * P + chunk] = fp64 sum of the chunk's elements; `masked`: only the positions the forward keeps (the backward's sum of g)
-template <bool VEC>
+// (GATED: a sample whose colour gate is off needs no sum -- its workgroups leave at once and write nothing)
+template <bool VEC, bool GATED>
 __global__ __launch_bounds__(kThreads) void sum_kernel(const float* __restrict__ x0, const float* __restrict__ x1, int n0,
                                                        const float* __restrict__ u, const Geom g, int masked,
-                                                       double* __restrict__ partial) {
+                                                       double* __restrict__ partial, const Gate gate) {
     __shared__ double red[kThreads / kWave];
     const int n = blockIdx.x / g.P, blk = blockIdx.x % g.P;
+    const int policy = policy_of<GATED>(g, gate, n);
+    if (GATED && !(policy & AGAN_DIFFAUG_COLOR)) return;
     const float* __restrict__ src = sample_ptr(x0, x1, n0, n, g.E);
     const int lo = min(g.E, blk * g.chunk);                            // (blk * chunk < E + 4 P: no overflow)
     const int cnt = min(g.chunk, g.E - lo);
     Sample p;
-    if (masked) p = sample_of(g, u, n);
+    if (masked) p = sample_of(g, u, n, policy);
     double acc = 0.0;
     if (VEC) {                                                          // E, chunk, lo and cnt are multiples of 4, and so is W
         for (int k = 4 * (int)threadIdx.x; k < cnt; k += 4 * kThreads) {
@@ -133,16 +162,17 @@ __global__ __launch_bounds__(kThreads) void sum_kernel(const float* __restrict__
 }
 
 // V pixels side by side in all C channels per thread.  Forward: out = y, sources (x0, x1); backward: out = dx, source x0 = dy.
-template <int C, int V, bool BWD>
+template <int C, int V, bool BWD, bool GATED>
 __global__ __launch_bounds__(kThreads) void apply_kernel(const float* __restrict__ x0, const float* __restrict__ x1, int n0,
                                                          const float* __restrict__ u, const Geom g, const double* __restrict__ partial,
-                                                         float* __restrict__ out, int blocks_per_sample) {
+                                                         float* __restrict__ out, int blocks_per_sample, const Gate gate) {
     __shared__ double s_part[kMaxPartials];
     __shared__ float s_mean;
     const int t = threadIdx.x;
     const int n = blockIdx.x / blocks_per_sample, blk = blockIdx.x % blocks_per_sample;
-    const Sample p = sample_of(g, u, n);
-    const bool color = (g.policy & AGAN_DIFFAUG_COLOR) != 0;
+    const int policy = policy_of<GATED>(g, gate, n);
+    const Sample p = sample_of(g, u, n, policy);
+    const bool color = (policy & AGAN_DIFFAUG_COLOR) != 0;            // (workgroup-uniform: the barriers below are safe)
     float mean = 0.f;                                                   // forward: M = mean(x) + b; backward: G = mean(g)
     if (color) {
         if (t < g.P) s_part[t] = partial[(size_t)n * g.P + t];
@@ -261,24 +291,27 @@ Geom geom_of(int C, int H, int W, int policy) {
 
 size_t ws_bytes_of(long long N, const Geom& g) { return up16((size_t)N * g.P * sizeof(double)); }
 
-template <int V, bool BWD>
+template <int V, bool BWD, bool GATED>
 void launch_apply(const Geom& g, unsigned blocks, hipStream_t st, const float* x0, const float* x1, int n0, const float* u,
-                  const double* partial, float* out, int bps) {
+                  const double* partial, float* out, int bps, const Gate& gate) {
     const auto launch = [&](auto CC) {
-        hipLaunchKernelGGL((apply_kernel<CC(), V, BWD>), dim3(blocks), dim3(kThreads), 0, st, x0, x1, n0, u, g, partial, out, bps);
+        hipLaunchKernelGGL((apply_kernel<CC(), V, BWD, GATED>), dim3(blocks), dim3(kThreads), 0, st, x0, x1, n0, u, g, partial, out, bps,
+                           gate);
     };
     if (!with_int<1, 2, 3>(g.C, launch)) launch(Int<4>{});
 }
 
+// gate == nullptr: the ungated entries
 template <bool BWD>
-int run(const char* what, const float* x0, const float* x1, int n0, int n1, const float* u, int policy, float* out, int C, int H, int W,
-        void* ws, size_t ws_bytes, void* stream) {
+int run(const char* what, const float* x0, const float* x1, int n0, int n1, const float* u, const Gate* gate, int policy, float* out, int C,
+        int H, int W, void* ws, size_t ws_bytes, void* stream) {
     AGAN_REQUIRE(n0 >= 1 && n1 >= 0 && H >= 1 && W >= 1, "%s: bad shape (N %d + %d, C %d, H %d, W %d)", what, n0, n1, C, H, W);
     AGAN_REQUIRE(C >= 1 && C <= 4, "%s: C %d outside 1..4", what, C);
     AGAN_REQUIRE(policy >= 0 && policy <= 7, "%s: policy %d outside 0..7", what, policy);
     const long long N = (long long)n0 + n1;
     AGAN_REQUIRE(in_domain(N, C, H, W), "%s: N * C * H * W is 2^31 or more (N %lld, C %d, H %d, W %d)", what, N, C, H, W);
     AGAN_REQUIRE(x0 && u && out && (n1 == 0 || x1), "%s: null pointer", what);
+    AGAN_REQUIRE(!gate || (gate->q && gate->p), "%s: null q or p", what);
     const Geom g = geom_of(C, H, W, policy);
     const size_t need = ws_bytes_of(N, g);
     AGAN_REQUIRE(ws, "%s: no workspace (agan_diffaug_ws_bytes: %zu bytes)", what, need);
@@ -292,15 +325,16 @@ int run(const char* what, const float* x0, const float* x1, int n0, int n1, cons
     uintptr_t bases = reinterpret_cast<uintptr_t>(x0) | reinterpret_cast<uintptr_t>(out);
     if (n1) bases |= reinterpret_cast<uintptr_t>(x1);
     const bool vec = W % 4 == 0 && bases % 16 == 0;
-    if (policy & AGAN_DIFFAUG_COLOR) {
-        const unsigned blocks = (unsigned)(N * g.P);
-        if (vec) hipLaunchKernelGGL(sum_kernel<true>, dim3(blocks), dim3(kThreads), 0, st, x0, x1, n0, u, g, BWD ? 1 : 0, partial);
-        else hipLaunchKernelGGL(sum_kernel<false>, dim3(blocks), dim3(kThreads), 0, st, x0, x1, n0, u, g, BWD ? 1 : 0, partial);
-    }
     const int bps = cdiv(vec ? g.HW / 4 : g.HW, kThreads);
-    const unsigned blocks = (unsigned)(N * bps);
-    if (vec) launch_apply<4, BWD>(g, blocks, st, x0, x1, n0, u, partial, out, bps);
-    else launch_apply<1, BWD>(g, blocks, st, x0, x1, n0, u, partial, out, bps);
+    const Gate gt = gate ? *gate : Gate{nullptr, nullptr};
+    with_bool(gate != nullptr, [&](auto GATED) {
+        with_bool(vec, [&](auto VEC) {
+            if (policy & AGAN_DIFFAUG_COLOR)
+                hipLaunchKernelGGL((sum_kernel<VEC(), GATED()>), dim3((unsigned)(N * g.P)), dim3(kThreads), 0, st, x0, x1, n0, u, g,
+                                   BWD ? 1 : 0, partial, gt);
+            launch_apply<VEC() ? 4 : 1, BWD, GATED()>(g, (unsigned)(N * bps), st, x0, x1, n0, u, partial, out, bps, gt);
+        });
+    });
     return check_launch(what);
 }
 
@@ -312,10 +346,22 @@ extern "C" size_t agan_diffaug_ws_bytes(int N, int C, int H, int W) {
 
 extern "C" int agan_diffaug_fwd(const float* x0, const float* x1, int n0, int n1, const float* u, int policy, float* y, int C, int H, int W,
                                 void* ws, size_t ws_bytes, void* stream) {
-    return run<false>("diffaug_fwd", x0, x1, n0, x1 ? n1 : 0, u, policy, y, C, H, W, ws, ws_bytes, stream);
+    return run<false>("diffaug_fwd", x0, x1, n0, x1 ? n1 : 0, u, nullptr, policy, y, C, H, W, ws, ws_bytes, stream);
 }
 
 extern "C" int agan_diffaug_bwd(const float* dy, const float* u, int policy, float* dx, int N, int C, int H, int W, void* ws,
                                 size_t ws_bytes, void* stream) {
-    return run<true>("diffaug_bwd", dy, nullptr, N, 0, u, policy, dx, C, H, W, ws, ws_bytes, stream);
+    return run<true>("diffaug_bwd", dy, nullptr, N, 0, u, nullptr, policy, dx, C, H, W, ws, ws_bytes, stream);
+}
+
+extern "C" int agan_diffaug_gated_fwd(const float* x0, const float* x1, int n0, int n1, const float* u, const float* q, const float* p,
+                                      int policy, float* y, int C, int H, int W, void* ws, size_t ws_bytes, void* stream) {
+    const Gate gate{q, p};
+    return run<false>("diffaug_gated_fwd", x0, x1, n0, x1 ? n1 : 0, u, &gate, policy, y, C, H, W, ws, ws_bytes, stream);
+}
+
+extern "C" int agan_diffaug_gated_bwd(const float* dy, const float* u, const float* q, const float* p, int policy, float* dx, int N, int C,
+                                      int H, int W, void* ws, size_t ws_bytes, void* stream) {
+    const Gate gate{q, p};
+    return run<true>("diffaug_gated_bwd", dy, nullptr, N, 0, u, &gate, policy, dx, C, H, W, ws, ws_bytes, stream);
 }

@@ -14,7 +14,7 @@ import torch
 from torch import Tensor
 from torch.nn import Module
 
-from ..augment import parse_policy
+from ..augment import AdaController, parse_policy
 from ..backend import functional as HF
 from ..dataparallel import GradBuckets, any_rank, averaged_buffers, broadcast_module_, rank_of, world_size
 from ..losses.disc_loss import NonSaturatingDiscLoss
@@ -133,8 +133,9 @@ class ModelTrainer:
 
 
 # what the generator's forward leaves for the rest of the step
-# (aug_u: the augmentation's uniforms [3 * len(Ds), B, 8], None without a policy)
-_Forward = collections.namedtuple("_Forward", "labels mask fakes attn mu logvar aug_u")
+# (aug_u: the augmentation's uniforms [3 * len(Ds), B, 8], None without a policy; aug_q: the per-stage gate uniforms
+# [3 * len(Ds), B, 4], None unless the augmentation has a probability)
+_Forward = collections.namedtuple("_Forward", "labels mask fakes attn mu logvar aug_u aug_q")
 
 
 def _forked(streams, i: int, main):
@@ -165,14 +166,36 @@ class GanTrainStep(ModelTrainer):
     the live ones by ONE launch right after the generator's Adam step -- in step(), inside capture()'s graph and inside the Adam
     graph of capture_segments() alike; warm-up steps count.  generate_images(use_ema=True) and evaluate(use_ema=True) sample it;
     state_dict() carries it as "generator_ema" and "ema".  With None (default) there is no copy, no launch and no checkpoint key.
+
+    `augment_p`, `ada_target`: apply every stage of `augment` to every sample with probability p instead of always (adaptive
+    discriminator augmentation, Karras et al. 2020; both need a non-empty `augment`).  `augment_p` alone is a fixed probability;
+    `ada_target` lets p adapt, starting from `augment_p or 0.0`: every discriminator's real scores are tallied on its own stream
+    (r_t = E[sign(D(real) - 0.5)]), and ONE one-thread launch next to the averaging update -- after the generator's Adam step, in
+    step(), capture() and capture_segments() alike -- moves p every `ada_interval` steps by (real scores seen) / (ada_kimg * 1000 *
+    len(Ds)) up while r_t > ada_target and down while below, inside [0, ada_p_max].  p lives in device memory (self.ada.p, the
+    step's result "ada_p"); the kernels read it when they run, every augmentation call of a step reads the same value, and nothing
+    is read on the host (self.ada.sync() does, on request).  The gates are one more torch.rand draw from `self.rng` right after
+    aug_u: aug_q [3 * len(Ds), B, 4], slots as for aug_u.  state_dict() carries the controller's words as "ada" with `ada_target`
+    only; a checkpoint without the key loads with p at its initial value.  Under torch.distributed `augment_p` works and
+    `ada_target` is refused: whether r_t is per rank or all-reduced is not decided yet.
     """
 
     def __init__(self, generator: Module, discriminators: Sequence[Module], image_encoder: Optional[Callable] = None,
                  gen_lr: float = 2e-4, disc_lr: float = 2e-4, gamma1: float = 4.0, gamma2: float = 5.0, gamma3: float = 10.0,
                  wlambda: float = 5.0, slambda: float = 5.0, bucket_bytes: int = 64 << 20, group=None, seed: int = 0,
                  g_bucket_bytes: Optional[int] = None, augment: Optional[str] = None, ema: Optional[float] = None,
-                 ema_warmup: bool = True):
+                 ema_warmup: bool = True, augment_p: Optional[float] = None, ada_target: Optional[float] = None, ada_interval: int = 4,
+                 ada_kimg: float = 500.0, ada_p_max: float = 1.0):
         super().__init__()
+        if (augment_p is not None or ada_target is not None) and not parse_policy(augment):
+            raise ValueError("GanTrainStep: augment_p and ada_target need a non-empty augment policy")
+        if ada_target is not None and world_size(group) > 1:
+            raise ValueError("GanTrainStep: ada_target is single-process for now (how r_t is formed over ranks is not decided); "
+                             "augment_p works under torch.distributed")
+        # the augmentation's probability in device memory, with its controller when it adapts (augment.AdaController checks the values)
+        self.ada = (AdaController(next(generator.parameters()).device, len(discriminators), p=0.0 if augment_p is None else float(augment_p),
+                                  target=ada_target, interval=ada_interval, kimg=ada_kimg, p_max=ada_p_max)
+                    if augment_p is not None or ada_target is not None else None)
         if ema is not None and not 0.0 < float(ema) < 1.0:
             raise ValueError(f"GanTrainStep: ema must be a decay inside (0, 1) or None, got {ema}")
         self.augment = parse_policy(augment)                # bit mask; 0 = no augmentation
@@ -218,6 +241,8 @@ class GanTrainStep(ModelTrainer):
         # optional observer `f(tag, optimiser)` called right before each optimiser consumes its gradients (after the gradient
         # exchange), tag in {"D0", "D1", "D2", "G"}: tests read the flat gradient buffers through it
         self.on_gradients: Optional[Callable] = None
+        # optional observer `f(i, score)` of discriminator i's real scores as the controller of `ada_target` is handed them
+        self.on_real_scores: Optional[Callable] = None
 
     def _d_streams(self, n: int, device) -> List:
         if len(self._streams) != n:
@@ -225,7 +250,8 @@ class GanTrainStep(ModelTrainer):
         return self._streams
 
     def step(self, word_embs: Tensor, sent_embs: Tensor, lengths, class_ids, real_imgs: Sequence[Tensor],
-             noise: Optional[Tensor] = None, eps: Optional[Tensor] = None, aug_u: Optional[Tensor] = None) -> Dict[str, Tensor]:
+             noise: Optional[Tensor] = None, eps: Optional[Tensor] = None, aug_u: Optional[Tensor] = None,
+             aug_q: Optional[Tensor] = None) -> Dict[str, Tensor]:
         if word_embs.is_cuda and not (isinstance(lengths, Tensor) and lengths.is_cuda):
             # host-side caption lengths (the reference's DataLoader hands over a list / CPU tensor): ONE pinned, non-blocking
             # copy up front -- a blocking H2D copy in the middle of the step drains the launch pipeline (~4 ms per step)
@@ -235,12 +261,12 @@ class GanTrainStep(ModelTrainer):
             HF.amax_begin_step(word_embs.device)        # zeroed amax slots of this step (fp16 split mode only; one fill launch)
         prev_side = HF.set_wgrad_side_stream(self.overlap_weight_gradients and word_embs.is_cuda)
         try:
-            return self._step(word_embs, sent_embs, lengths, class_ids, real_imgs, noise, eps, aug_u)
+            return self._step(word_embs, sent_embs, lengths, class_ids, real_imgs, noise, eps, aug_u, aug_q)
         finally:
             HF.set_wgrad_side_stream(prev_side)
 
-    def _step(self, word_embs, sent_embs, lengths, class_ids, real_imgs, noise, eps, aug_u=None) -> Dict[str, Tensor]:
-        fw = self._gen_forward(word_embs, sent_embs, lengths, noise, eps, aug_u)
+    def _step(self, word_embs, sent_embs, lengths, class_ids, real_imgs, noise, eps, aug_u=None, aug_q=None) -> Dict[str, Tensor]:
+        fw = self._gen_forward(word_embs, sent_embs, lengths, noise, eps, aug_u, aug_q)
         out: Dict[str, Tensor] = {}
         # ---- discriminator updates (train.py:123-130) ----
         # The three updates are independent of each other (each D has its own weights, optimiser and images), so each runs on
@@ -263,6 +289,8 @@ class GanTrainStep(ModelTrainer):
         self._apply("G", self.g_opt, self.g_buckets.finish())
         if self.g_ema is not None:
             self.g_ema.update()
+        if self.ada is not None:
+            self.ada.update()                       # (every discriminator stream has been joined twice since the tallies)
         # loss histories stay device tensors: no .item() host sync inside the step (reference syncs at train.py:130,144-145)
         self.d_losses.append(out[f"d_loss{len(self.Ds) - 1}"])
         self.g_losses.append(out[f"g_loss{len(self.Ds) - 1}"])
@@ -271,7 +299,7 @@ class GanTrainStep(ModelTrainer):
         return self._results(fw, out)
 
     # -- the phases of the step: _step() runs them eagerly, capture_segments() records each into a graph of its own --------
-    def _gen_forward(self, word_embs, sent_embs, lengths, noise, eps, aug_u=None) -> "_Forward":
+    def _gen_forward(self, word_embs, sent_embs, lengths, noise, eps, aug_u=None, aug_q=None) -> "_Forward":
         b = word_embs.shape[0]
         labels = self._make_match_labels(b)
         mask = self._make_mask(lengths, word_embs.shape[2])
@@ -285,14 +313,23 @@ class GanTrainStep(ModelTrainer):
             aug_u = torch.rand(3 * len(self.Ds), b, 8, dtype=torch.float32, device=word_embs.device, generator=self.rng)
         elif tuple(aug_u.shape) != (3 * len(self.Ds), b, 8):
             raise ValueError(f"aug_u must be [{3 * len(self.Ds)}, {b}, 8], got {tuple(aug_u.shape)}")
-        return _Forward(labels, mask, *self.G(noise, sent_embs, word_embs, mask, eps), aug_u)
+        if self.ada is None:
+            aug_q = None
+        elif aug_q is None:                                 # the gates' uniforms: same place, same generator, right after aug_u
+            aug_q = torch.rand(3 * len(self.Ds), b, 4, dtype=torch.float32, device=word_embs.device, generator=self.rng)
+        elif tuple(aug_q.shape) != (3 * len(self.Ds), b, 4):
+            raise ValueError(f"aug_q must be [{3 * len(self.Ds)}, {b}, 4], got {tuple(aug_q.shape)}")
+        return _Forward(labels, mask, *self.G(noise, sent_embs, word_embs, mask, eps), aug_u, aug_q)
 
     def _augmenter(self, fw: "_Forward", first: int, count: int) -> Optional[Callable]:
         """What the losses apply to the images before D: slots first .. first + count - 1 of the step's uniforms, one per tensor."""
         if fw.aug_u is None:
             return None
         u = fw.aug_u[first:first + count].reshape(-1, 8)    # (adjacent slots: a view, no launch)
-        return lambda xs: HF.diffaug(xs, u, self.augment)
+        if fw.aug_q is None:
+            return lambda xs: HF.diffaug(xs, u, self.augment)
+        q, p = fw.aug_q[first:first + count].reshape(-1, 4), self.ada.p
+        return lambda xs: HF.diffaug(xs, u, self.augment, q, p)
 
     def _d_backward(self, i: int, fw: "_Forward", real_imgs, out: Dict[str, Tensor], arm: bool = False) -> None:
         """Discriminator i's gradients on the current stream; `arm`: its buckets exchange them from the backward's hooks."""
@@ -300,10 +337,19 @@ class GanTrainStep(ModelTrainer):
         if arm:
             self.d_buckets[i].arm()
         aug = self._augmenter(fw, 3 * i, 2)                 # (None without a policy: the call is then the one it always was)
-        loss = (self.disc_loss.get_loss(self.Ds[i], fw.fakes[i].detach(), real_imgs[i]) if aug is None else
-                self.disc_loss.get_loss(self.Ds[i], fw.fakes[i].detach(), real_imgs[i], augment=aug))
+        if self.ada is not None and self.ada.adaptive:      # the real scores' signs go to discriminator i's slot, on this stream
+            loss = self.disc_loss.get_loss(self.Ds[i], fw.fakes[i].detach(), real_imgs[i], augment=aug,
+                                           observe=lambda score: self._observe(i, score))
+        else:
+            loss = (self.disc_loss.get_loss(self.Ds[i], fw.fakes[i].detach(), real_imgs[i]) if aug is None else
+                    self.disc_loss.get_loss(self.Ds[i], fw.fakes[i].detach(), real_imgs[i], augment=aug))
         loss.backward()
         out[f"d_loss{i}"] = loss.detach()
+
+    def _observe(self, i: int, score: Tensor) -> None:
+        if self.on_real_scores is not None:
+            self.on_real_scores(i, score)
+        self.ada.observe(i, score)
 
     def _g_backward(self, fw: "_Forward", word_embs, sent_embs, lengths, class_ids, out: Dict[str, Tensor],
                     streams: Optional[List] = None, arm: bool = False) -> None:
@@ -351,14 +397,15 @@ class GanTrainStep(ModelTrainer):
             self.on_gradients(tag, opt)
         opt.step(scale)
 
-    @staticmethod
-    def _results(fw: "_Forward", out: Dict[str, Tensor]) -> Dict[str, Tensor]:
+    def _results(self, fw: "_Forward", out: Dict[str, Tensor]) -> Dict[str, Tensor]:
+        if self.ada is not None and self.ada.adaptive:
+            out["ada_p"] = self.ada.p                       # the LIVE device view: read it after the step, clone it to keep a value
         out["fake_imgs"] = [f.detach() for f in fw.fakes]
         out["attn_maps"] = [a.detach() for a in fw.attn]
         out["mu"], out["logvar"] = fw.mu.detach(), fw.logvar.detach()
         return out
 
-    def _warm_up(self, who: str, word_embs, sent_embs, lengths, real_imgs, warmup: int, noise, eps, aug_u=None) -> None:
+    def _warm_up(self, who: str, word_embs, sent_embs, lengths, real_imgs, warmup: int, noise, eps, aug_u=None, aug_q=None) -> None:
         """What both captures do first: `warmup` real train steps off the default stream, then the host-side tables."""
         if not (isinstance(lengths, Tensor) and lengths.is_cuda and lengths.dtype == torch.int64):
             raise ValueError(f"{who}(): lengths must be an int64 device tensor")
@@ -366,35 +413,38 @@ class GanTrainStep(ModelTrainer):
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):                      # warm-up off the default stream: tables, caches, allocator pools
             for _ in range(max(1, warmup)):
-                self.step(word_embs, sent_embs, lengths, None, real_imgs, noise, eps, aug_u)
+                self.step(word_embs, sent_embs, lengths, None, real_imgs, noise, eps, aug_u, aug_q)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         HF.build_pack_tables()                             # the batched re-pack's job tables: host work, not capturable
 
     # -- whole-step HIP graph ----------------------------------------------------------------------------------------
     def capture(self, word_embs: Tensor, sent_embs: Tensor, lengths: Tensor, real_imgs: Sequence[Tensor], warmup: int = 2,
-                noise: Optional[Tensor] = None, eps: Optional[Tensor] = None, aug_u: Optional[Tensor] = None) -> "GraphedStep":
+                noise: Optional[Tensor] = None, eps: Optional[Tensor] = None, aug_u: Optional[Tensor] = None,
+                aug_q: Optional[Tensor] = None) -> "GraphedStep":
         """Capture one full train step (all four optimiser updates, every stream) into a HIP graph.
 
         The arguments become the graph's STATIC input buffers: copy each new batch into them (`.copy_()`) and call `replay()`.
         `lengths` must be a device int64 tensor (no host reads inside the step); noise and the CA-net eps are drawn inside the
         graph (graph-safe Philox state) unless static `noise` / `eps` buffers are given, and so are the augmentation's uniforms
-        (`aug_u`, with an `augment` policy); BatchNorm counters and the Adam step
-        counters live in device memory, so replays keep advancing exactly like eager steps.  The warm-up steps are real
+        (`aug_u`, with an `augment` policy; `aug_q`, the gates' uniforms, with `augment_p` / `ada_target`); BatchNorm counters, the
+        Adam step counters and the augmentation probability with its controller's window live in device memory, so replays keep
+        advancing -- and adapting -- exactly like eager steps.  The warm-up steps are real
         training steps.  Single-process only: with world_size > 1 run the eager `step()`."""
         if self.g_buckets.active:
             raise RuntimeError("capture(): the all-reduce path is not captured; use step() under torch.distributed")
-        self._warm_up("capture", word_embs, sent_embs, lengths, real_imgs, warmup, noise, eps, aug_u)
+        self._warm_up("capture", word_embs, sent_embs, lengths, real_imgs, warmup, noise, eps, aug_u, aug_q)
         graph = torch.cuda.CUDAGraph()
         if self.rng.device.type == "cuda":
             graph.register_generator_state(self.rng)       # noise / eps draws inside the graph advance this generator on replay
         with torch.cuda.graph(graph):
-            out = self.step(word_embs, sent_embs, lengths, None, real_imgs, noise, eps, aug_u)
+            out = self.step(word_embs, sent_embs, lengths, None, real_imgs, noise, eps, aug_u, aug_q)
         return GraphedStep(graph, out, self.g_ema)
 
     # -- segment-wise HIP graphs for world > 1 --------------------------------------------------------------------------
     def capture_segments(self, word_embs: Tensor, sent_embs: Tensor, lengths: Tensor, real_imgs: Sequence[Tensor], warmup: int = 2,
-                         noise: Optional[Tensor] = None, eps: Optional[Tensor] = None, aug_u: Optional[Tensor] = None) -> "SegmentedStep":
+                         noise: Optional[Tensor] = None, eps: Optional[Tensor] = None, aug_u: Optional[Tensor] = None,
+                         aug_q: Optional[Tensor] = None) -> "SegmentedStep":
         """The train step as NINE HIP graphs with the gradient exchange launched between them -- the form for world_size > 1, where
         the whole-step graph of capture() cannot be used (the RCCL collectives are not captured) and an eager step costs every rank
         ~11 ms of Python per 27 ms step on host cores the 8 ranks share:
@@ -408,7 +458,7 @@ class GanTrainStep(ModelTrainer):
         first -- and nothing overlaps the generator's 28 MB.  The arguments become static input buffers exactly as for capture();
         the graphs share one memory pool and must be replayed in capture order (SegmentedStep.replay does).  Results are
         bit-identical to the eager step (tests/test_gpu_dataparallel.py, one-rank `nccl` rehearsal)."""
-        self._warm_up("capture_segments", word_embs, sent_embs, lengths, real_imgs, warmup, noise, eps, aug_u)
+        self._warm_up("capture_segments", word_embs, sent_embs, lengths, real_imgs, warmup, noise, eps, aug_u, aug_q)
         # memory pools: graphs that share a pool must never run concurrently (a later capture re-uses the temporaries an earlier one
         # freed).  The three discriminator updates replay CONCURRENTLY on their own streams, so each gets a private pool for its two
         # graphs; the generator's graphs, which run alone, share one.
@@ -431,7 +481,7 @@ class GanTrainStep(ModelTrainer):
                 g0.register_generator_state(self.rng)
             with torch.cuda.graph(g0, pool=pool, capture_error_mode=mode):
                 HF.amax_begin_step(word_embs.device)
-                fw = self._gen_forward(word_embs, sent_embs, lengths, noise, eps, aug_u)
+                fw = self._gen_forward(word_embs, sent_embs, lengths, noise, eps, aug_u, aug_q)
             seg.gen_forward = g0
             out: Dict[str, Tensor] = {}
             # ---- discriminator updates: backward graph, (exchange), Adam graph ----
@@ -455,6 +505,8 @@ class GanTrainStep(ModelTrainer):
                 self.g_opt.step(self.g_buckets.scale)
                 if self.g_ema is not None:
                     self.g_ema.update()
+                if self.ada is not None:
+                    self.ada.update()
             seg.g_backward, seg.g_adam = gg, gadam
             seg.out = self._results(fw, out)
         finally:
@@ -488,6 +540,8 @@ class GanTrainStep(ModelTrainer):
             sd["generator_ema"] = e.pop("shadow")
             sd["ema"] = e
             averaged.append((self.G_ema, sd["generator_ema"]))
+        if self.ada is not None and self.ada.adaptive:
+            sd["ada"] = self.ada.state_dict()              # (one host read; single-process by construction)
         if all_ranks and w > 1:
             import torch.distributed as dist
             for m, msd in averaged:
@@ -534,6 +588,11 @@ class GanTrainStep(ModelTrainer):
                                                         float(sd["ema"]["decay"]), self.g_ema.decay)
             else:
                 self.g_ema.copy_from_live()
+        if self.ada is not None and self.ada.adaptive:
+            if "ada" in sd:
+                self.ada.load_state_dict(sd["ada"])
+            else:
+                self.ada.reset()                           # a checkpoint of a run without adaptation: p at its initial value
         for d, o, ds, os_ in zip(self.Ds, self.d_opts, sd["discriminators"], sd["d_optims"]):
             d.load_state_dict(ds)
             o.load_state_dict(os_)

@@ -670,6 +670,58 @@ int agan_diffaug_bwd(const float* dy /* [N, C, H, W] */, const float* u /* [N, 8
                      int H, int W, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The same transform with every stage applied PER SAMPLE with probability p (adaptive discriminator augmentation, Karras et al. 2020;
+ * augment.py: diffaug_reference(..., q, p); backend/functional.py: diffaug(..., q, p)).  THIS text defines the gates.
+ *
+ * q is [N, 4] fp32 uniforms in [0, 1), slot 3 reserved; p points to ONE fp32 in DEVICE memory, read by the kernels when they run (so a
+ * captured HIP graph follows a p that other kernels change between replays).  For sample n, stage k (0 = COLOR, 1 = TRANSLATION,
+ * 2 = CUTOUT) runs iff its policy bit is set AND q[n][k] < *p, an fp32 compare: q == p is off, *p = NaN gates everything off, *p >= 1
+ * gates nothing off.  A stage that is gated off is skipped for that sample exactly as if its policy bit were off for that sample
+ * alone: with all three off the sample's bits move unchanged (-0.0 and NaN payloads included); the colour stage is skipped, not run
+ * with b = 0, s = c = 1.  agan_diffaug_gated_bwd is the transpose under the same gates.
+ * Everything else is as for the ungated entries: the two sources of the forward, the workspace (agan_diffaug_ws_bytes), the 16-byte
+ * and the one-pixel access paths, no atomics, no allocation, no synchronisation, graph-capturable.  The workspace's contents on entry
+ * do not matter: the partial sums of a sample whose colour gate is off are neither written nor read, and its sum workgroups return
+ * before they load anything.  With *p >= 1 the results are the ungated entries' bytes.
+ * AGAN_EINVAL before any launch for a null q or p and for everything the ungated entries refuse; AGAN_EWORKSPACE likewise.
+ * ---------------------------------------------------------------------------------------------- */
+int agan_diffaug_gated_fwd(const float* x0 /* [n0, C, H, W] */, const float* x1 /* [n1, C, H, W] or NULL */, int n0, int n1,
+                           const float* u /* [n0 + n1, 8] */, const float* q /* [n0 + n1, 4] */, const float* p /* DEVICE, one fp32 */,
+                           int policy, float* y /* [n0 + n1, C, H, W] */, int C, int H, int W, void* ws, size_t ws_bytes, void* stream);
+int agan_diffaug_gated_bwd(const float* dy /* [N, C, H, W] */, const float* u /* [N, 8] */, const float* q /* [N, 4] */,
+                           const float* p /* DEVICE, one fp32 */, int policy, float* dx /* [N, C, H, W] */, int N, int C, int H, int W,
+                           void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The controller of that probability (csrc/ada.hip; augment.py: AdaController, ada_reference; backend/functional.py: ada_observe_,
+ * ada_update_).  p follows the overfitting signal r_t = E[sign(D(real) - threshold)]: up while r_t is above a target, down while below.
+ *
+ * state: 64 bytes of device memory owned by the caller, as int32 words:
+ *   [0] signed sum accumulated in the current window      [1] number of scores accumulated in the window
+ *   [2] update calls in the window                        [3] adjustments made so far
+ *   [4] p as fp32 bits                                    [5] the last r_t as fp32 bits
+ *   [6..7] reserved                                       [8 + 2 i], [9 + 2 i] observation slot of discriminator i, i < 4
+ * Word 4 IS the p the gated augmentation entries read: hand them state + 4.
+ *
+ * agan_ada_observe: one workgroup.  WRITES (does not accumulate) slot[0] = #(score > threshold) - #(score < threshold), slot[1] = n.  A NaN
+ * counts in n and in neither tally.  Integer arithmetic only: the result does not depend on the order of the reduction.  Every
+ * discriminator observes into its own slot, on its own stream; no two streams write one word.
+ * agan_ada_update: a one-thread kernel.  It adds every slot i < nslots with slot[1] > 0 into words 0 / 1 and zeroes those slots, then
+ * increments word 2.  When word 2 reaches `interval` it clears words 0..2 and, if the window's count is positive, forms in double
+ *     r = sum / count;    p = min(max(p + sgn(r - target) * count * rate, 0), p_max),   sgn(0) = 0
+ * stores (float)p and (float)r and increments word 3; a window with count == 0 leaves p, r_t and word 3 alone.  No host scalar other
+ * than the configuration enters, so a captured HIP graph keeps adapting on replay.
+ * Both kernels use plain vector loads and stores and no atomics: run-to-run identical.
+ * AGAN_EINVAL before any launch: observe for a null pointer, n < 1 or a NaN threshold; update for a null state, nslots outside 1..4,
+ * interval < 1, rate < 0 (or NaN), p_max outside (0, 1] or a NaN target.
+ * ---------------------------------------------------------------------------------------------- */
+#define AGAN_ADA_STATE_WORDS 16
+#define AGAN_ADA_P_WORD 4
+#define AGAN_ADA_SLOT_WORD 8
+int agan_ada_observe(const float* score /* [n] */, int n, float threshold, int32_t* slot /* 2 words */, void* stream);
+int agan_ada_update(int32_t* state /* 16 words */, int nslots, int interval, double target, double rate, double p_max, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Exponential moving average of a module's weights (csrc/ema.hip; optim.py: FlatEMA; backend/functional.py: ema_update_, ema_reference).
  * One call updates every segment of a DEVICE-resident table:  dst[i] = fma(omb, src[i] - dst[i], dst[i])  in fp32, src only read.
  * Segment i owns workgroups [first_block, next segment's first_block); the last one runs to total_blocks.  A segment moves 16 bytes per
