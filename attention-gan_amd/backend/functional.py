@@ -31,7 +31,7 @@ def set_precision(p: int) -> None:
         # the batched re-pack (packed_weight / _repack_group) refreshes EVERY registered pack of a layout family: forget the ones the
         # old mode registered (they re-register on their next use), or a later mode keeps re-packing layouts nothing reads
         for rng in _FLAT_RANGES:
-            rng[3], rng[4] = [], None
+            rng.forget()
     _PRECISION[0] = int(p)
 
 
@@ -228,11 +228,57 @@ def conv_geoms(kind: str, B: int, Cin: int, H: int, W: int, Cout: int, k: int):
 # step must not invalidate the discriminators' packed weights.  Writes through a raw pointer into memory that is not a
 # registered flat buffer bump the global epoch instead.  Without a cache dict every call re-packs.
 _WEIGHT_EPOCH = [0]
-_FLAT_RANGES: list = []          # [start address, end address, epoch]
+_FLAT_RANGES: list = []          # the registered _FlatRange records
+
+
+def _stamp(t: Tensor) -> Tuple[int, int]:
+    """what shows that a tensor changed without a raw-pointer write: new storage moves the address, an in-place edit the version"""
+    return t.data_ptr(), t._version
+
+
+class _FlatRange:
+    """A registered flat parameter buffer: its address range, the epoch that raw-pointer writes advance, the pack entries of its
+    views and their device job tables {layout family: (table, jobs, blocks)}.  `registered` turns False when the range is dropped:
+    an entry that still points here then finds its range by address again."""
+    __slots__ = ("start", "end", "epoch", "entries", "tables", "registered")
+
+    def __init__(self, start: int, end: int, epoch: int):
+        self.start, self.end, self.epoch, self.entries, self.tables, self.registered = start, end, epoch, [], {}, True
+
+    def written(self) -> None:
+        """a kernel wrote the buffer through its raw pointer: every pack of its views is stale"""
+        self.epoch += 1
+
+    def forget(self) -> None:
+        """drop every entry and job table; an entry registers again at its next use"""
+        for e in self.entries:
+            e.rng = None
+        self.entries, self.tables = [], {}
+
+
+class _PackEntry:
+    """One packed form of one weight: the value of the owning module's cache[(mode, prec)] and, while `rng` is a range, a member
+    of that range's `entries` -- the same object.  `ptr`, `tver`, `dims` say which tensor `wk` was packed from; `epoch` and
+    `flat_epoch` are the global epoch and the range's (-1 outside any range) at the time of the pack."""
+    __slots__ = ("rng", "mode", "prec", "dims", "ptr", "tver", "wk", "epoch", "flat_epoch")
+
+    def __init__(self, mode: int, prec: int):
+        self.rng, self.mode, self.prec, self.dims, self.ptr, self.tver, self.wk = None, mode, prec, None, 0, -1, None
+        self.epoch = self.flat_epoch = -1
+
+    def packed(self) -> None:
+        """`wk` was just written from the tensor the entry names"""
+        self.epoch, self.flat_epoch = _WEIGHT_EPOCH[0], self.rng.epoch if self.rng is not None else -1
 
 
 def bump_weight_epoch() -> None:
     _WEIGHT_EPOCH[0] += 1
+
+
+def _drop_ranges(gone) -> None:
+    for r in _FLAT_RANGES:
+        r.registered = not gone(r)
+    _FLAT_RANGES[:] = [r for r in _FLAT_RANGES if r.registered]
 
 
 def register_flat(flat: Tensor) -> None:
@@ -241,19 +287,19 @@ def register_flat(flat: Tensor) -> None:
     end = start + flat.numel() * flat.element_size()
     # a buffer registered earlier that overlaps this one has been freed (the allocator handed its memory out again): drop it,
     # and start above every epoch seen so far so that no cached pack of recycled memory can look fresh
-    top = max([r[2] for r in _FLAT_RANGES] + [0])
-    _FLAT_RANGES[:] = [r for r in _FLAT_RANGES if r[1] <= start or r[0] >= end]
-    _FLAT_RANGES.append([start, end, top + 1, [], None])     # [start, end, epoch, pack entries, device job table]
+    top = max([r.epoch for r in _FLAT_RANGES] + [0])
+    _drop_ranges(lambda r: r.start < end and r.end > start)
+    _FLAT_RANGES.append(_FlatRange(start, end, top + 1))
 
 
 def unregister_flat(flat: Tensor) -> None:
     start = flat.data_ptr()
-    _FLAT_RANGES[:] = [r for r in _FLAT_RANGES if r[0] != start]
+    _drop_ranges(lambda r: r.start == start)
 
 
-def _flat_range(ptr: int):
+def _flat_range(ptr: int) -> Optional[_FlatRange]:
     for r in _FLAT_RANGES:
-        if r[0] <= ptr < r[1]:
+        if r.start <= ptr < r.end:
             return r
     return None
 
@@ -262,46 +308,43 @@ _PACK_JOB_DTYPE = [("w", "<u8"), ("wk", "<u8"), ("mode", "<i4"), ("cout", "<i4")
                    ("first_block", "<i4")]          # include/agan.h: agan_pack_job
 
 
-def _pack_table(rng, prec: int):
+def _pack_table(rng: _FlatRange, prec: int):
     """device job table of a flat buffer's pack entries of ONE layout family (`prec`: the fp32 k-table layouts, or one of the 16-bit
-    patch layouts); built on the host, one H2D copy; rebuilt when an entry is added"""
-    import numpy as np
-    entries = [e for e in rng[3] if e["prec"] == prec]
-    if rng[4] is None:
-        rng[4] = {}
-    hit = rng[4].get(prec)
-    if hit is None or hit[1] != len(entries):
+    patch layouts); built on the host, one H2D copy; rebuilt when an entry was added or changed (packed_weight empties `tables`)"""
+    hit = rng.tables.get(prec)
+    if hit is None:
+        import numpy as np
         if torch.cuda.is_current_stream_capturing():
             raise L.AganError("packed-weight job table missing during HIP-graph capture: run a warm-up step and "
                               "build_pack_tables() first (GanTrainStep.capture does)")
         lib = L.load()
+        entries = [e for e in rng.entries if e.prec == prec]
         jobs = np.zeros(len(entries), dtype=_PACK_JOB_DTYPE)
         first = 0
         for i, e in enumerate(entries):
-            cout, cin, kh, kw = e["dims"]
-            jobs[i] = (e["ptr"], e["wk"].data_ptr(), e["mode"], cout, cin, kh, kw, first)
-            first += lib.agan_pack_job_blocks_prec(e["mode"], cout, cin, kh, kw, prec)
-        table = torch.from_numpy(jobs.view(np.uint8).copy()).to(entries[0]["wk"].device)
-        hit = rng[4][prec] = (table, len(entries), first)
+            jobs[i] = (e.ptr, e.wk.data_ptr(), e.mode, *e.dims, first)
+            first += lib.agan_pack_job_blocks_prec(e.mode, *e.dims, prec)
+        table = torch.from_numpy(jobs.view(np.uint8).copy()).to(entries[0].wk.device)
+        hit = rng.tables[prec] = (table, len(entries), first)
     return hit
 
 
 def build_pack_tables() -> None:
     """Build every missing job table now (host work + H2D copies), e.g. before capturing a HIP graph."""
     for rng in _FLAT_RANGES:
-        for prec in sorted({e["prec"] for e in rng[3]}):
+        for prec in sorted({e.prec for e in rng.entries}):
             _pack_table(rng, prec)
 
 
-def _repack_group(rng, prec: int) -> None:
+def _repack_group(rng: _FlatRange, prec: int) -> None:
     """Re-pack every registered packed weight of one flat buffer and one layout family in a single launch (agan_pack_weights).
     After an optimiser step all of them are stale at once, and most are a few KB: one launch instead of one ~10-17 us launch per
     tensor and mode (1.7 ms per step in the 16-bit modes before they took this path too)."""
     table, n, total = _pack_table(rng, prec)
     L.call("agan_pack_weights", _p(table), n, total, prec, _stream())
-    for e in rng[3]:
-        if e["prec"] == prec:
-            e["cache"][e["key"]] = ((e["ptr"], e["tver"], _WEIGHT_EPOCH[0], rng[2]) + e["dims"], e["wk"], rng)
+    for e in rng.entries:
+        if e.prec == prec:
+            e.packed()
 
 
 _EFF_PREC = {}
@@ -336,39 +379,43 @@ def wgrad_effective_precision(g: L.ConvGeom, pack_mode: int) -> int:
 
 
 def packed_weight(w: Tensor, mode: int, cache: Optional[dict] = None, prec: Optional[int] = None) -> Tensor:
-    cout, cin, kh, kw = w.shape
     if prec is None:
         prec = _PRECISION[0]
-    key = (mode, prec)
-    hit = cache.get(key) if cache is not None else None
-    ptr = w.data_ptr()
-    rng = hit[2] if (hit is not None and hit[0][0] == ptr) else _flat_range(ptr)
-    ver = (ptr, w._version, _WEIGHT_EPOCH[0], rng[2] if rng is not None else -1, cout, cin, kh, kw)
-    if hit is not None and hit[0] == ver:
-        return hit[1]
-    if hit is not None and rng is not None and hit[0][:2] == ver[:2] and hit[0][4:] == ver[4:] \
-            and any(e["cache"] is cache and e["key"] == key for e in rng[3]):
-        # same tensor, only the optimiser epoch moved: its whole group (same layout family) is stale -> one batched launch
-        _repack_group(rng, prec)
-        hit = cache[key]
-        if hit[0] == ver:
-            return hit[1]
-    n = L.load().agan_packed_weight_bytes(mode, cout, cin, kh, kw, prec)
-    if n == 0:
-        raise L.AganError(f"pack mode {mode} / precision {prec} does not take a {kh}x{kw} kernel")
-    reuse = hit is not None and hit[1].numel() == n and hit[1].device == w.device
-    wk = hit[1] if reuse else torch.empty(n, dtype=torch.uint8, device=w.device)
-    L.call("agan_pack_weight", _p(w), _p(wk), mode, cout, cin, kh, kw, prec, _stream())
-    if cache is not None:
-        cache[key] = (ver, wk, rng)
+    ent = cache.get((mode, prec)) if cache is not None else None
+    ptr, tver = _stamp(w)
+    # the range the entry knows, while that range is registered and the tensor has not moved; else the one at the tensor's address
+    rng = ent.rng if (ent is not None and ent.ptr == ptr and ent.rng is not None and ent.rng.registered) else _flat_range(ptr)
+    # packed from exactly this tensor, and listed under the range the tensor lies in now (written out: the hit path is ~2 calls per conv)
+    if ent is not None and ent.rng is rng and ent.ptr == ptr and ent.tver == tver and ent.dims == w.shape:
+        if ent.epoch == _WEIGHT_EPOCH[0] and ent.flat_epoch == (rng.epoch if rng is not None else -1):
+            return ent.wk                       # and no raw-pointer write since: fresh
         if rng is not None:
-            ent = next((e for e in rng[3] if e["cache"] is cache and e["key"] == key), None)
-            if ent is None:
-                ent = {"cache": cache, "key": key}
-                rng[3].append(ent)
-            ent.update(ptr=ptr, tver=w._version, dims=(cout, cin, kh, kw), mode=mode, wk=wk, prec=prec)
-            rng[4] = None                       # job tables are rebuilt at the next batched re-pack
-    return wk
+            # same tensor, only the optimiser epoch moved: its whole group (same layout family) is stale -> one batched launch
+            _repack_group(rng, prec)
+            return ent.wk
+    dims = tuple(w.shape)
+    n = L.load().agan_packed_weight_bytes(mode, *dims, prec)
+    if n == 0:
+        raise L.AganError(f"pack mode {mode} / precision {prec} does not take a {dims[2]}x{dims[3]} kernel")
+    if ent is None:
+        ent = _PackEntry(mode, prec)
+    if ent.wk is None or ent.wk.numel() != n or ent.wk.device != w.device:
+        ent.wk = torch.empty(n, dtype=torch.uint8, device=w.device)
+    L.call("agan_pack_weight", _p(w), _p(ent.wk), mode, *dims, prec, _stream())
+    if cache is not None:
+        cache[(mode, prec)] = ent
+        if ent.rng is not rng:                  # first pack, or the tensor now lies in another range: move the entry there
+            if ent.rng is not None:
+                ent.rng.entries.remove(ent)
+                ent.rng.tables = {}
+            ent.rng = rng
+            if rng is not None:
+                rng.entries.append(ent)
+        ent.ptr, ent.tver, ent.dims = ptr, tver, dims
+        ent.packed()
+        if rng is not None:
+            rng.tables = {}                     # job tables are rebuilt at the next batched re-pack
+    return ent.wk
 
 
 _KTABLE_CACHE = {}
@@ -1268,7 +1315,7 @@ def mark_flat_written(flat: Tensor) -> None:
     their launch; a replayed HIP graph that holds such a launch needs it said once per replay)."""
     rng = _flat_range(flat.data_ptr())
     if rng is not None:
-        rng[2] += 1
+        rng.written()
     else:
         bump_weight_epoch()
 
@@ -1306,7 +1353,7 @@ def ema_reference(src: Tensor, dst: Tensor, t: int, decay: float, warmup: bool =
 # Each conv's eval-mode BatchNorm folds into its weights and a per-channel bias (w' = w*gamma*invstd, b' = beta - mean*gamma*invstd,
 # invstd = 1/sqrt(running_var + eps)), followed by the ReLU epilogue of agan_conv2d_fwd.  The folded weights are packed once per
 # direction and cached on the module; a conv is re-folded when any of its five tensors changed -- in-place version bump
-# (load_state_dict, an in-place edit) or new storage (.to()): the invalidation rule of packed_weight.  The trunk runs in fp32 in every
+# (load_state_dict, an in-place edit) or new storage (.to()): what _stamp shows.  The trunk runs in fp32 in every
 # precision mode (agan_conv2d_effective_prec).  The layer plan (which tensors, slices, write/accumulate order) is
 # networks/inception_plan.py.
 def _conv2d_desc(op, B: int) -> "L.Conv2dDesc":
@@ -1351,11 +1398,11 @@ def _trunk_layer(module, op, device):
     """(folded bias, packed forward weight, packed data-gradient weight) of one conv of the plan, re-folded when stale"""
     m = module.get_submodule(op.name)
     ts = (m.conv.weight, m.bn.weight, m.bn.bias, m.bn.running_mean, m.bn.running_var)
-    ver = tuple((t.data_ptr(), t._version) for t in ts) + (float(m.bn.eps), str(device))
+    ver = tuple(_stamp(t) for t in ts) + (float(m.bn.eps), str(device))
     cache = module.__dict__.setdefault("_agan_trunk_fold", {})
-    hit = cache.get(op.name)
-    if hit is not None and hit[0] == ver:
-        return hit[1]
+    was, val = cache.get(op.name, (None, None))
+    if was == ver:
+        return val
     w, gamma, beta, mean, var = (_dev(t.detach(), f"trunk {op.name}") for t in ts)
     with torch.no_grad():
         scale = gamma * torch.rsqrt(var + m.bn.eps)
@@ -1495,11 +1542,11 @@ def _conv2d_raw_desc(op, B: int) -> "L.Conv2dDesc":
 def _trunk_train_weight(module, op, dgrad: int, device) -> Tensor:
     """the unfolded conv weight of one conv of the plan, packed for one direction; re-packed when the weight changed"""
     w = module.get_submodule(op.name).conv.weight
-    ver = (w.data_ptr(), w._version, str(device))
+    ver = _stamp(w) + (str(device),)
     cache = module.__dict__.setdefault("_agan_trunk_train_w", {})
-    hit = cache.get((op.name, dgrad))
-    if hit is not None and hit[0] == ver:
-        return hit[1]
+    was, wk = cache.get((op.name, dgrad), (None, None))
+    if was == ver:
+        return wk
     wk = conv2d_pack(_dev(w.detach(), f"trunk {op.name}"), _conv2d_raw_desc(op, 1), dgrad)
     cache[(op.name, dgrad)] = (ver, wk)
     return wk
@@ -1608,7 +1655,7 @@ def inception_trunk_train(image: Tensor, module) -> Tuple[Tensor, Tensor]:
 # caption encoder (networks/rnn_encoder.py::RNNEncoder, backend="hip"; train and eval mode)
 # --------------------------------------------------------------------------------------------------------------
 # embedding gather -> (the module's dropout) -> input projection per direction on `linear` (packed W_ih cached per direction by
-# packed_weight's rule; fp32: a linear layer is a 1x1 geometry, which every precision mode runs in fp32) -> one recurrence launch
+# packed_weight; fp32: a linear layer is a 1x1 geometry, which every precision mode runs in fp32) -> one recurrence launch
 # for both directions (agan_lstm_fwd).  Backward: agan_lstm_bwd (gate gradients) + agan_lstm_wgrad (W_hh, b_hh), the projections'
 # own backward (W_ih, b_ih, data) and agan_embedding_bwd.  Nothing is atomic.
 class _EmbeddingFn(Function):

@@ -15,42 +15,52 @@ from torch import Tensor, nn
 from .backend import functional as HF
 
 
-class FlatAdam:
-    def __init__(self, params: Iterable[nn.Parameter], lr: float = 2e-4, betas=(0.5, 0.999), eps: float = 1e-8):
-        self.params: List[nn.Parameter] = [p for p in params if p.requires_grad]
-        if not self.params:
-            raise ValueError("FlatAdam: no trainable parameters")
-        dev, dt = self.params[0].device, self.params[0].dtype
-        if dt != torch.float32:
-            raise ValueError("FlatAdam: float32 parameters only")
-        self.lr, self.betas, self.eps = lr, tuple(betas), eps
+class _FlatHome:
+    """Parameters re-homed as views of one flat fp32 buffer that packed-weight caches follow on its own (HF.register_flat)."""
+
+    def _rehome(self, params: List[nn.Parameter], device) -> None:
+        """-> self.params, self.offsets, self.numel, self.flat: the buffer holds the parameters' values and every p.data views it"""
+        self.params = params
         self.offsets, total = [], 0
         for p in self.params:
             self.offsets.append(total)
             total += (p.numel() + 3) // 4 * 4           # keep every parameter 16-byte aligned inside the buffer
         self.numel = total
-        self.flat = torch.zeros(total, dtype=dt, device=dev)
-        self.grad = torch.zeros(total, dtype=dt, device=dev)
-        self.exp_avg = torch.zeros(total, dtype=dt, device=dev)
-        self.exp_avg_sq = torch.zeros(total, dtype=dt, device=dev)
+        self.flat = torch.zeros(total, dtype=torch.float32, device=device)
         with torch.no_grad():
             for p, o in zip(self.params, self.offsets):
                 self.flat[o:o + p.numel()].copy_(p.detach().reshape(-1))
                 p.data = self.flat[o:o + p.numel()].view(p.shape)
-                p.grad = self.grad[o:o + p.numel()].view(p.shape)
-                p._agan_grad_dst = HF.GradDst(self.grad, o, p.numel())   # backward kernels write here directly
         if self.flat.is_cuda:
-            HF.register_flat(self.flat)        # packed-weight caches follow THIS buffer's Adam steps only
-        self.step_count = 0
-        # device-resident step counter + bias-correction coefficients (see agan_adam_step): advanced by the kernel itself, so a
-        # captured HIP graph keeps counting on replay; step_count mirrors it on the host for state_dict()
-        self.step_state = torch.zeros(4, dtype=torch.int32, device=dev)
+            HF.register_flat(self.flat)        # packed-weight caches follow THIS buffer's writes only
 
     def __del__(self):
         try:
             HF.unregister_flat(self.flat)
-        except Exception:      # interpreter shutdown
+        except Exception:      # interpreter shutdown, or a constructor that raised before the buffer existed
             pass
+
+
+class FlatAdam(_FlatHome):
+    def __init__(self, params: Iterable[nn.Parameter], lr: float = 2e-4, betas=(0.5, 0.999), eps: float = 1e-8):
+        params = [p for p in params if p.requires_grad]
+        if not params:
+            raise ValueError("FlatAdam: no trainable parameters")
+        dev, dt = params[0].device, params[0].dtype
+        if dt != torch.float32:
+            raise ValueError("FlatAdam: float32 parameters only")
+        self.lr, self.betas, self.eps = lr, tuple(betas), eps
+        self._rehome(params, dev)
+        self.grad = torch.zeros(self.numel, dtype=dt, device=dev)
+        self.exp_avg = torch.zeros(self.numel, dtype=dt, device=dev)
+        self.exp_avg_sq = torch.zeros(self.numel, dtype=dt, device=dev)
+        for p, o in zip(self.params, self.offsets):
+            p.grad = self.grad[o:o + p.numel()].view(p.shape)
+            p._agan_grad_dst = HF.GradDst(self.grad, o, p.numel())   # backward kernels write here directly
+        self.step_count = 0
+        # device-resident step counter + bias-correction coefficients (see agan_adam_step): advanced by the kernel itself, so a
+        # captured HIP graph keeps counting on replay; step_count mirrors it on the host for state_dict()
+        self.step_state = torch.zeros(4, dtype=torch.int32, device=dev)
 
     # -- torch.optim-like surface ---------------------------------------------------------------------------
     def zero_grad(self, set_to_none: bool = False) -> None:
@@ -161,7 +171,7 @@ class FlatAdam:
             self.step_state[0] = self.step_count
 
 
-class FlatEMA:
+class FlatEMA(_FlatHome):
     """Exponential moving average of a module's weights in a shadow module, as ONE fused HIP launch per update.
 
     The shadow's trainable parameters are re-homed into a flat buffer of its own with `live_opt`'s order, offsets and padding, so
@@ -190,26 +200,15 @@ class FlatEMA:
             odd = sorted(k for k in set(live_all) | set(shadow_all) if live_all.get(k) != shadow_all.get(k))
             raise ValueError(f"FlatEMA: the shadow's parameters differ from the live module's in name or shape: {odd[:4]}")
         shadow_params = dict(shadow_module.named_parameters())
-        self.params: List[nn.Parameter] = [shadow_params[k] for k, _ in live_named]
-        self.offsets, total = [], 0
+        self._rehome([shadow_params[k] for k, _ in live_named], live_opt.flat.device)
+        assert self.offsets == live_opt.offsets and self.numel == live_opt.numel, "FlatEMA: the shadow's layout must be the live optimiser's"
         for p in self.params:
-            self.offsets.append(total)
-            total += (p.numel() + 3) // 4 * 4
-        assert self.offsets == live_opt.offsets and total == live_opt.numel, "FlatEMA: the shadow's layout must be the live optimiser's"
-        self.numel = total
-        self.flat = torch.zeros(total, dtype=torch.float32, device=live_opt.flat.device)
-        with torch.no_grad():
-            for p, o in zip(self.params, self.offsets):
-                self.flat[o:o + p.numel()].copy_(p.detach().reshape(-1))
-                p.data = self.flat[o:o + p.numel()].view(p.shape)
-                p.grad = None
+            p.grad = None
         for p in shadow_module.parameters():
             p.requires_grad_(False)
         for m in shadow_module.modules():                  # packed copies the original had made of ITS weights
             if isinstance(m.__dict__.get("_packed"), dict):
                 m._packed = {}
-        if self.flat.is_cuda:
-            HF.register_flat(self.flat)
         cls = type(shadow_module)
         shadow_module.__class__ = type(cls.__name__, (cls,), {"train": lambda self, mode=True: nn.Module.train(self, False),
                                                               "__module__": cls.__module__})
@@ -219,12 +218,6 @@ class FlatEMA:
         self._table = None
         if self.flat.is_cuda:
             self._segments()
-
-    def __del__(self):
-        try:
-            HF.unregister_flat(self.flat)
-        except Exception:      # interpreter shutdown
-            pass
 
     def _buffer_pairs(self):
         """[(live module's buffer dict, shadow module's buffer dict, name)] of every floating-point buffer, checked"""
@@ -268,10 +261,6 @@ class FlatEMA:
         table, nseg, total = self._segments()
         self.updates += 1
         HF.ema_update_(table, nseg, total, self.state, self.decay, self.warmup, self.flat)
-
-    def mark_updated(self) -> None:
-        """A replayed HIP graph ran update(): the shadow's packed weights are stale (update() itself says so when it runs eagerly)."""
-        HF.mark_flat_written(self.flat)
 
     def sync_updates(self) -> int:
         """The device counter is the truth (a replayed HIP graph advances only it): mirror it on the host.  One host sync."""

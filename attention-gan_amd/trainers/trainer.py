@@ -439,7 +439,14 @@ class GanTrainStep(ModelTrainer):
             graph.register_generator_state(self.rng)       # noise / eps draws inside the graph advance this generator on replay
         with torch.cuda.graph(graph):
             out = self.step(word_embs, sent_embs, lengths, None, real_imgs, noise, eps, aug_u, aug_q)
-        return GraphedStep(graph, out, self.g_ema)
+        return GraphedStep(graph, out, self)
+
+    def _mark_replayed(self) -> None:
+        """A replayed graph ran every Adam step and the averaging update without their host code: say what adam_step_ and ema_update_
+        say, or the next EAGER use of a network (generate_images, step) runs on packs of the weights from before the replay."""
+        for holder in [self.g_opt, self.g_ema] + self.d_opts:
+            if holder is not None:
+                HF.mark_flat_written(holder.flat)
 
     # -- segment-wise HIP graphs for world > 1 --------------------------------------------------------------------------
     def capture_segments(self, word_embs: Tensor, sent_embs: Tensor, lengths: Tensor, real_imgs: Sequence[Tensor], warmup: int = 2,
@@ -687,13 +694,12 @@ def sample_fakes(G: Module, word_embs: Tensor, sent_embs: Tensor, mask: Tensor, 
 class GraphedStep:
     """A captured train step: `replay()` runs it; `out` holds the static result tensors (losses, fake images)."""
 
-    def __init__(self, graph, out: Dict[str, Tensor], ema: Optional[FlatEMA] = None):
-        self.graph, self.out, self.ema = graph, out, ema
+    def __init__(self, graph, out: Dict[str, Tensor], trainer: "GanTrainStep"):
+        self.graph, self.out, self.t = graph, out, trainer
 
     def replay(self) -> Dict[str, Tensor]:
         self.graph.replay()
-        if self.ema is not None:
-            self.ema.mark_updated()                        # the averaged generator re-packs its weights at its next use
+        self.t._mark_replayed()
         return self.out
 
 
@@ -723,8 +729,7 @@ class SegmentedStep:
         self.g_backward.replay()
         t.g_buckets.exchange_all()
         self.g_adam.replay()
-        if t.g_ema is not None:
-            t.g_ema.mark_updated()
+        t._mark_replayed()
         return self.out
 
 

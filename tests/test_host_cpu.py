@@ -482,7 +482,8 @@ def test_batch_wire_format(tmp_path):
 
 def test_flat_buffer_epochs_are_per_buffer_and_survive_recycling():
     """packed-weight caches follow the Adam steps of THEIR flat buffer (functional.register_flat): ranges are looked up by
-    address, an overlapping re-registration (recycled memory) drops the old range and starts above every epoch handed out."""
+    address, an overlapping re-registration (recycled memory) drops the old range and starts above every epoch handed out, and a
+    dropped range says that it is no longer registered."""
     HF = importlib.import_module("attention-gan_amd.backend.functional")
     saved = list(HF._FLAT_RANGES)
     try:
@@ -493,13 +494,16 @@ def test_flat_buffer_epochs_are_per_buffer_and_survive_recycling():
         ra, rb = HF._flat_range(a.data_ptr() + 40), HF._flat_range(b.data_ptr())
         assert ra is not None and rb is not None and ra is not rb
         assert HF._flat_range(a.data_ptr() + 400) is not ra            # one past the end
-        ra[2] += 5                                                    # five optimiser steps on a
-        assert rb[2] != ra[2]
+        for _ in range(5):                                            # five optimiser steps on a
+            HF.mark_flat_written(a)
+        assert rb.epoch != ra.epoch
+        assert ra.registered and rb.registered
         HF.register_flat(a[10:60])                                    # same memory handed out again under another base
         rn = HF._flat_range(a.data_ptr() + 44)
-        assert rn is not ra and rn[2] > ra[2] and ra not in HF._FLAT_RANGES
+        assert rn is not ra and rn.epoch > ra.epoch and ra not in HF._FLAT_RANGES
+        assert not ra.registered and rn.registered and rb.registered
         HF.unregister_flat(b)
-        assert HF._flat_range(b.data_ptr()) is None
+        assert HF._flat_range(b.data_ptr()) is None and not rb.registered
     finally:
         HF._FLAT_RANGES[:] = saved
 
