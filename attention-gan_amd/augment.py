@@ -6,9 +6,14 @@ device, differentiable by autograd.  The training step never calls it.
 
 Adaptive discriminator augmentation (Karras et al. 2020): with q and p every stage is applied per sample with probability p (the
 gated entries agan_diffaug_gated_*), `AdaController` keeps p in device memory and steers it by two small HIP launches
-(agan_ada_observe / agan_ada_update), and `ada_reference` restates the controller in Python integers and doubles, as its oracle."""
+(agan_ada_observe / agan_ada_update), and `ada_reference` restates the controller in Python integers and doubles, as its oracle.
+
+The geometric stages of that paper (x-flip, quarter turns, isotropic scale, rotation, anisotropic scale) are ONE bilinear affine warp
+in front of DiffAugment's stages (agan_geoaug_matrix / agan_affine_warp_*): `parse_geometry` names them, and
+`geometry_matrices_reference`, `affine_warp_reference` and `geoaug_reference` are the oracle of those kernels."""
 from __future__ import annotations
 
+import math
 import struct
 from typing import Dict, Optional, Tuple, Union
 
@@ -123,6 +128,126 @@ def diffaug_reference(x: Tensor, u: Tensor, policy: Union[str, int, None], q: Op
         cut = ((ys >= y0) & (ys < y0 + ch) & (xs >= x0) & (xs < x0 + cw)).view(N, 1, H, W)
         z = gated(2, torch.where(cut, torch.zeros((), dtype=z.dtype, device=z.device), z), z)
     return z
+
+
+# --------------------------------------------------------------------------------------------------------------
+# geometric stages (include/agan.h: agan_geoaug_matrix / agan_affine_warp_*): ONE bilinear affine warp per tensor
+# --------------------------------------------------------------------------------------------------------------
+XFLIP, ROT90, SCALE, ROTATE, ANISO = 1, 2, 4, 8, 16              # include/agan.h: AGAN_GEOAUG_*
+GEO_UNIFORMS = 16                                                # per sample: slots 0..4 stage values, 8..12 stage gates
+_GEO_BITS = {"xflip": XFLIP, "rot90": ROT90, "scale": SCALE, "rotate": ROTATE, "aniso": ANISO}
+
+
+def parse_geometry(geometry: Union[str, int, None]) -> int:
+    """"xflip,rot90,scale,rotate,aniso" (any subset, any order; "" or None = nothing) -> the bit mask; an int in 0..31 passes
+    through.  Separate from parse_policy: the geometric stages are one warp in front of DiffAugment's, with a mask of their own."""
+    if geometry is None:
+        return 0
+    if isinstance(geometry, int) and not isinstance(geometry, bool):
+        if not 0 <= geometry <= 31:
+            raise ValueError(f"geometry {geometry} outside 0..31")
+        return geometry
+    if not isinstance(geometry, str):
+        raise ValueError(f"geometry must be a string of names, an int or None, got {type(geometry).__name__}")
+    mask = 0
+    for name in (p.strip() for p in geometry.split(",")):
+        if not name:
+            continue
+        if name not in _GEO_BITS:
+            raise ValueError(f"unknown geometric augmentation {name!r}: expected a comma-separated subset of {', '.join(_GEO_BITS)}")
+        mask |= _GEO_BITS[name]
+    return mask
+
+
+def geometry_names(geometry: int) -> str:
+    """the inverse of parse_geometry, names in stage order"""
+    geometry = parse_geometry(geometry)
+    return ",".join(n for n, b in _GEO_BITS.items() if geometry & b)
+
+
+def geometry_gates(g: Tensor, p) -> Tensor:
+    """bool [N, 5]: stage k of sample n passes its gate iff g[n, 8 + k] < p, compared in fp32; a NaN p passes nothing"""
+    g32 = g.detach().to(torch.float32)
+    p32 = p.detach().to(device=g32.device, dtype=torch.float32).reshape(()) if isinstance(p, Tensor) else torch.tensor(float(p), dtype=torch.float32, device=g32.device)
+    return g32[:, 8:13] < p32
+
+
+def geometry_matrices_reference(g: Tensor, geometry: Union[str, int, None], p=None) -> Tensor:
+    """M [N, 6] = (a, b, tx, c, d, ty) of include/agan.h (agan_geoaug_matrix) from the uniforms g [N, 16], in g's dtype: the product,
+    left to right, of the applied stages' output -> source maps.  A stage applies iff its bit is set and -- with p -- g[n, 8 + k] < p
+    in fp32; one that does not apply is skipped (torch.where keeps the running product, it is not multiplied by an identity).  The
+    decisions (flip, quarter turn, gates) come from the fp32 values of g whatever its dtype is."""
+    geometry = parse_geometry(geometry)
+    if g.dim() != 2 or g.shape[1] != GEO_UNIFORMS:
+        raise ValueError(f"geometry_matrices_reference: expected g [N, {GEO_UNIFORMS}], got {tuple(g.shape)}")
+    N, dt, dev = g.shape[0], g.dtype, g.device
+    g32 = g.detach().to(torch.float32)
+    gates = None if p is None else geometry_gates(g, p)
+
+    def on(k: int) -> Tensor:
+        m = torch.full((N,), bool(geometry >> k & 1), device=dev)
+        return m if gates is None else m & gates[:, k]
+
+    def stage(rows) -> Tensor:
+        return torch.stack([torch.stack(list(r), dim=1) for r in rows], dim=1)      # [N, 2, 2]
+
+    def mul(L: Tensor, S: Tensor, m: Tensor) -> Tensor:
+        a, b, c, d = L[:, 0, 0], L[:, 0, 1], L[:, 1, 0], L[:, 1, 1]
+        P = stage(((a * S[:, 0, 0] + b * S[:, 1, 0], a * S[:, 0, 1] + b * S[:, 1, 1]),
+                   (c * S[:, 0, 0] + d * S[:, 1, 0], c * S[:, 0, 1] + d * S[:, 1, 1])))
+        return torch.where(m.view(N, 1, 1), P, L)
+
+    one, zero = torch.ones(N, dtype=dt, device=dev), torch.zeros(N, dtype=dt, device=dev)
+    L = stage(((one, zero), (zero, one)))
+    L = mul(L, stage(((-one, zero), (zero, one))), on(0) & (g32[:, 0] >= 0.5))
+    k = torch.clamp((4.0 * g32[:, 1]).to(torch.int64), max=3)
+    c = torch.tensor([1, 0, -1, 0], dtype=dt, device=dev)[k]
+    s = torch.tensor([0, 1, 0, -1], dtype=dt, device=dev)[k]
+    L = mul(L, stage(((c, -s), (s, c))), on(1))
+    sc = torch.exp2(0.7 * g[:, 2] - 0.35)
+    L = mul(L, stage(((sc, zero), (zero, sc))), on(2))
+    th = (2.0 * g[:, 3] - 1.0) * math.pi
+    c, s = torch.cos(th), torch.sin(th)
+    L = mul(L, stage(((c, -s), (s, c))), on(3))
+    r = torch.exp2(0.7 * g[:, 4] - 0.35)
+    L = mul(L, stage(((r, zero), (zero, 1.0 / r))), on(4))
+    return torch.stack([L[:, 0, 0], L[:, 0, 1], zero, L[:, 1, 0], L[:, 1, 1], zero], dim=1)
+
+
+def affine_warp_reference(x: Tensor, M: Tensor) -> Tensor:
+    """The warp of include/agan.h (agan_affine_warp_fwd) on x [N, C, H, W] with M [N, 6], every operation in x's dtype and in the
+    header's order: bilinear taps about the image centre, zero outside the image.  Differentiable in x by autograd (the transpose
+    agan_affine_warp_bwd computes); M gets no gradient."""
+    if x.dim() != 4 or M.dim() != 2 or tuple(M.shape) != (x.shape[0], 6):
+        raise ValueError(f"affine_warp_reference: expected x [N, C, H, W] and M [N, 6], got {tuple(x.shape)} and {tuple(M.shape)}")
+    N, C, H, W = x.shape
+    dt, dev = x.dtype, x.device
+    M = M.detach().to(device=dev, dtype=dt)
+    cy, cx = (H - 1) / 2, (W - 1) / 2
+    oy = (torch.arange(H, dtype=dt, device=dev) - cy).view(1, H, 1)
+    ox = (torch.arange(W, dtype=dt, device=dev) - cx).view(1, 1, W)
+    v = lambda i: M[:, i].view(N, 1, 1)
+    sx = (v(0) * ox + v(1) * oy) + (v(2) * W + cx)
+    sy = (v(3) * ox + v(4) * oy) + (v(5) * H + cy)
+    x0f, y0f = torch.floor(sx), torch.floor(sy)
+    fx, fy = sx - x0f, sy - y0f
+    x0 = x0f.clamp(-2, W).to(torch.int64)                                   # (anything outside [-1, W - 1] has no tap inside)
+    y0 = y0f.clamp(-2, H).to(torch.int64)
+    flat = x.reshape(N, C, H * W)
+    out = torch.zeros_like(x)
+    for j, wy in ((0, 1 - fy), (1, fy)):
+        for i, wx in ((0, 1 - fx), (1, fx)):
+            yy, xx = y0 + j, x0 + i
+            inside = (yy >= 0) & (yy < H) & (xx >= 0) & (xx < W)
+            idx = (yy.clamp(0, H - 1) * W + xx.clamp(0, W - 1)).view(N, 1, H * W).expand(N, C, H * W)
+            val = flat.gather(2, idx).view(N, C, H, W)
+            out = out + torch.where(inside.view(N, 1, H, W), val * (wy * wx).view(N, 1, H, W), torch.zeros((), dtype=dt, device=dev))
+    return out
+
+
+def geoaug_reference(x: Tensor, g: Tensor, geometry: Union[str, int, None], p=None) -> Tensor:
+    """matrices from the uniforms (in x's dtype), then the warp: what GanTrainStep(geometry=...) applies in front of DiffAugment"""
+    return affine_warp_reference(x, geometry_matrices_reference(g.to(x.dtype), geometry, p))
 
 
 # --------------------------------------------------------------------------------------------------------------

@@ -1880,6 +1880,80 @@ def diffaug(xs, u: Tensor, policy: int, q: Optional[Tensor] = None, p: Optional[
 
 
 # --------------------------------------------------------------------------------------------------------------
+# geometric augmentation (augment.py: geometry_matrices_reference, affine_warp_reference; include/agan.h: agan_geoaug_matrix,
+# agan_affine_warp_*)
+# --------------------------------------------------------------------------------------------------------------
+def geometry_matrices(g: Tensor, geometry: int, p: Optional[Tensor] = None) -> Tensor:
+    """M [N, 6] of include/agan.h (agan_geoaug_matrix) from the uniforms g [N, 16] and the stage mask of augment.parse_geometry: ONE
+    launch, one thread per sample.  With `p` (a ONE-element fp32 device tensor, read when the kernel runs) stage k of sample n applies
+    iff its bit is set and g[n, 8 + k] < p; without it every enabled stage applies."""
+    g = _dev(g.detach(), "geometry_matrices g")
+    if g.dim() != 2 or g.shape[1] != L.GEOAUG_UNIFORMS or g.shape[0] < 1:
+        raise ValueError(f"geometry_matrices: g must be [N, {L.GEOAUG_UNIFORMS}], got {tuple(g.shape)}")
+    if p is not None and (not p.is_cuda or p.device != g.device or p.dtype != torch.float32 or p.numel() != 1):
+        raise ValueError(f"geometry_matrices: p must be a one-element float32 tensor on {g.device}, got {p.dtype} {tuple(p.shape)} on {p.device}")
+    M = torch.empty((g.shape[0], 6), dtype=torch.float32, device=g.device)
+    _kmeans_call("agan_geoaug_matrix", _p(g), _p(p), int(geometry), _p(M), int(g.shape[0]), _stream())
+    return M
+
+
+def _affine_warp_bwd(dy: Tensor, M: Tensor) -> Tensor:
+    N, C, H, W = dy.shape
+    dx = torch.empty_like(dy)
+    _kmeans_call("agan_affine_warp_bwd", _p(dy), _p(M), _p(dx), N, C, H, W, _stream())
+    return dx
+
+
+class _AffineWarpFn(Function):
+    @staticmethod
+    def forward(ctx, M, *xs):
+        x0 = xs[0]
+        x1 = xs[1] if len(xs) > 1 else None
+        n0, C, H, W = x0.shape
+        n1 = 0 if x1 is None else int(x1.shape[0])
+        y = torch.empty((n0 + n1, C, H, W), dtype=torch.float32, device=x0.device)
+        _kmeans_call("agan_affine_warp_fwd", _p(x0), _p(x1), n0, n1, _p(M), _p(y), C, H, W, _stream())
+        ctx.save_for_backward(M)
+        ctx.sizes = (n0, n1)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        M, = ctx.saved_tensors
+        n0, n1 = ctx.sizes
+        need = list(ctx.needs_input_grad[1:])
+        dy = _dev(dy, "affine_warp dy")
+        if all(need):                                     # one call over the whole batch, split per source
+            dx = _affine_warp_bwd(dy, M)
+            grads = [dx] if n1 == 0 else [dx[:n0], dx[n0:]]
+        else:                                             # only the samples of the source that asks
+            bounds = [(0, n0), (n0, n0 + n1)]
+            grads = [_affine_warp_bwd(dy[lo:hi], M[lo:hi]) if want else None for want, (lo, hi) in zip(need, bounds)]
+        return (None, *grads)
+
+
+def affine_warp(xs, M: Tensor) -> Tensor:
+    """The bilinear affine warp of include/agan.h (agan_affine_warp_fwd; augment.affine_warp_reference states it in torch ops) on one
+    [N, C, H, W] tensor or a PAIR of equal-shaped ones, whose samples come out concatenated in ONE tensor, as for diffaug.  M: [N, 6]
+    = (a, b, tx, c, d, ty) per sample of the result, an output -> source map about the image centre; a tap outside the image reads
+    zero.  Differentiable in the images (never in M): the backward is a gather with one summation order and no atomics, run for the
+    sources that require grad.  The forward takes any finite matrix; the backward is specified for linear parts that shrink no axis
+    below 1/16 (its candidate walk is clamped at 32 outputs either way per axis)."""
+    xs = (xs,) if isinstance(xs, Tensor) else tuple(xs)
+    if not 1 <= len(xs) <= 2:
+        raise ValueError(f"affine_warp: expected one tensor or a pair, got {len(xs)}")
+    xs = tuple(_dev(x, "affine_warp x") for x in xs)
+    if xs[0].dim() != 4 or any(x.shape != xs[0].shape or x.device != xs[0].device for x in xs):
+        raise ValueError(f"affine_warp: expected [N, C, H, W] tensors of one shape on one device, got {[tuple(x.shape) for x in xs]}")
+    n = sum(int(x.shape[0]) for x in xs)
+    M = _dev(M.detach(), "affine_warp M")
+    if M.device != xs[0].device or tuple(M.shape) != (n, 6):
+        raise ValueError(f"affine_warp: M must be [{n}, 6] on {xs[0].device}, got {tuple(M.shape)} on {M.device}")
+    return _AffineWarpFn.apply(M, *xs)
+
+
+# --------------------------------------------------------------------------------------------------------------
 # the controller of the augmentation probability (augment.py: AdaController; include/agan.h: agan_ada_*)
 # --------------------------------------------------------------------------------------------------------------
 def _ada_words(t: Tensor, words: int, what: str) -> None:

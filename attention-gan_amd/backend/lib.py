@@ -23,6 +23,8 @@ AMAX_SLOT = 256        # floats per amax slot (include/agan.h: AGAN_AMAX_SLOT)
 EINVAL, EWORKSPACE = -1, -2                # include/agan.h: AGAN_EINVAL, AGAN_EWORKSPACE
 DIFFAUG_COLOR, DIFFAUG_TRANSLATION, DIFFAUG_CUTOUT = 1, 2, 4      # include/agan.h: AGAN_DIFFAUG_*
 ADA_STATE_WORDS, ADA_P_WORD, ADA_SLOT_WORD = 16, 4, 8           # include/agan.h: AGAN_ADA_*
+GEOAUG_XFLIP, GEOAUG_ROT90, GEOAUG_SCALE, GEOAUG_ROTATE, GEOAUG_ANISO = 1, 2, 4, 8, 16      # include/agan.h: AGAN_GEOAUG_*
+GEOAUG_ALL, GEOAUG_UNIFORMS = 31, 16
 ABI_VERSION = 101     # include/agan.h: AGAN_VERSION this binding was written against (argument lists changed between versions)
 
 
@@ -167,6 +169,9 @@ _SIGNATURES = {
     "agan_diffaug_gated_bwd": (c_int, [_P, _P, _P, _P, c_int, _P, c_int, c_int, c_int, c_int, _P, c_size_t, _P]),
     "agan_ada_observe": (c_int, [_P, c_int, c_float, _P, _P]),
     "agan_ada_update": (c_int, [_P, c_int, c_int, c_double, c_double, c_double, _P]),
+    "agan_geoaug_matrix": (c_int, [_P, _P, c_int, _P, c_int, _P]),
+    "agan_affine_warp_fwd": (c_int, [_P, _P, c_int, c_int, _P, _P, c_int, c_int, c_int, _P]),
+    "agan_affine_warp_bwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     "agan_ema_plan": (c_int, [_P, c_int]),
     "agan_ema_update": (c_int, [_P, c_int, c_int, _P, c_double, c_int, _P]),
     "agan_adam_step": (c_int, [_P, _P, _P, _P, c_size_t, _P, c_double, c_double, c_double, c_double, c_float, _P]),

@@ -14,7 +14,7 @@ import torch
 from torch import Tensor
 from torch.nn import Module
 
-from ..augment import AdaController, parse_policy
+from ..augment import GEO_UNIFORMS, AdaController, parse_geometry, parse_policy
 from ..backend import functional as HF
 from ..dataparallel import GradBuckets, any_rank, averaged_buffers, broadcast_module_, rank_of, world_size
 from ..losses.disc_loss import NonSaturatingDiscLoss
@@ -134,8 +134,9 @@ class ModelTrainer:
 
 # what the generator's forward leaves for the rest of the step
 # (aug_u: the augmentation's uniforms [3 * len(Ds), B, 8], None without a policy; aug_q: the per-stage gate uniforms
-# [3 * len(Ds), B, 4], None unless the augmentation has a probability)
-_Forward = collections.namedtuple("_Forward", "labels mask fakes attn mu logvar aug_u aug_q")
+# [3 * len(Ds), B, 4], None unless the augmentation has a probability; aug_m: the geometric stages' matrices [3 * len(Ds), B, 6],
+# None without `geometry`)
+_Forward = collections.namedtuple("_Forward", "labels mask fakes attn mu logvar aug_u aug_q aug_m", defaults=(None,))
 
 
 def _forked(streams, i: int, main):
@@ -168,7 +169,7 @@ class GanTrainStep(ModelTrainer):
     state_dict() carries it as "generator_ema" and "ema".  With None (default) there is no copy, no launch and no checkpoint key.
 
     `augment_p`, `ada_target`: apply every stage of `augment` to every sample with probability p instead of always (adaptive
-    discriminator augmentation, Karras et al. 2020; both need a non-empty `augment`).  `augment_p` alone is a fixed probability;
+    discriminator augmentation, Karras et al. 2020; both need a non-empty `augment` or `geometry`).  `augment_p` alone is a fixed probability;
     `ada_target` lets p adapt, starting from `augment_p or 0.0`: every discriminator's real scores are tallied on its own stream
     (r_t = E[sign(D(real) - 0.5)]), and ONE one-thread launch next to the averaging update -- after the generator's Adam step, in
     step(), capture() and capture_segments() alike -- moves p every `ada_interval` steps by (real scores seen) / (ada_kimg * 1000 *
@@ -178,6 +179,16 @@ class GanTrainStep(ModelTrainer):
     aug_u: aug_q [3 * len(Ds), B, 4], slots as for aug_u.  state_dict() carries the controller's words as "ada" with `ada_target`
     only; a checkpoint without the key loads with p at its initial value.  Under torch.distributed `augment_p` works and
     `ada_target` is refused: whether r_t is per rank or all-reduced is not decided yet.
+
+    `geometry`: the paper's geometric stages ("xflip,rot90,scale,rotate,aniso", any subset; augment.parse_geometry) as ONE bilinear
+    affine warp with zero fill (backend.functional.affine_warp) applied to the same tensors IN FRONT of `augment`'s stages --
+    geometry before colour, the paper's order -- and differentiated in the generator update by a gather with a fixed summation
+    order.  The uniforms are one more torch.rand draw from `self.rng`, the LAST of _gen_forward's draws: aug_g [3 * len(Ds), B, 16],
+    slots as for aug_u; one small launch right after it (backend.functional.geometry_matrices) turns all of them into matrices,
+    which do not depend on the resolution.  With `augment_p` / `ada_target` (which need a non-empty `augment` OR `geometry`) every
+    geometric stage is gated per sample by slots 8..12 of its uniforms against the same device-resident p.  The image encoder,
+    generate_images and evaluate never see the warp; the stages are configuration, not checkpoint content.  With None (default)
+    nothing is drawn and no kernel runs.
     """
 
     def __init__(self, generator: Module, discriminators: Sequence[Module], image_encoder: Optional[Callable] = None,
@@ -185,9 +196,9 @@ class GanTrainStep(ModelTrainer):
                  wlambda: float = 5.0, slambda: float = 5.0, bucket_bytes: int = 64 << 20, group=None, seed: int = 0,
                  g_bucket_bytes: Optional[int] = None, augment: Optional[str] = None, ema: Optional[float] = None,
                  ema_warmup: bool = True, augment_p: Optional[float] = None, ada_target: Optional[float] = None, ada_interval: int = 4,
-                 ada_kimg: float = 500.0, ada_p_max: float = 1.0):
+                 ada_kimg: float = 500.0, ada_p_max: float = 1.0, geometry: Optional[str] = None):
         super().__init__()
-        if (augment_p is not None or ada_target is not None) and not parse_policy(augment):
+        if (augment_p is not None or ada_target is not None) and not (parse_policy(augment) or parse_geometry(geometry)):
             raise ValueError("GanTrainStep: augment_p and ada_target need a non-empty augment policy")
         if ada_target is not None and world_size(group) > 1:
             raise ValueError("GanTrainStep: ada_target is single-process for now (how r_t is formed over ranks is not decided); "
@@ -199,6 +210,7 @@ class GanTrainStep(ModelTrainer):
         if ema is not None and not 0.0 < float(ema) < 1.0:
             raise ValueError(f"GanTrainStep: ema must be a decay inside (0, 1) or None, got {ema}")
         self.augment = parse_policy(augment)                # bit mask; 0 = no augmentation
+        self.geometry = parse_geometry(geometry)            # bit mask of the geometric stages; 0 = no warp
         self.G, self.Ds, self.image_encoder = generator, list(discriminators), image_encoder
         self.group = group
         for m in [self.G] + self.Ds:
@@ -251,7 +263,7 @@ class GanTrainStep(ModelTrainer):
 
     def step(self, word_embs: Tensor, sent_embs: Tensor, lengths, class_ids, real_imgs: Sequence[Tensor],
              noise: Optional[Tensor] = None, eps: Optional[Tensor] = None, aug_u: Optional[Tensor] = None,
-             aug_q: Optional[Tensor] = None) -> Dict[str, Tensor]:
+             aug_q: Optional[Tensor] = None, aug_g: Optional[Tensor] = None) -> Dict[str, Tensor]:
         if word_embs.is_cuda and not (isinstance(lengths, Tensor) and lengths.is_cuda):
             # host-side caption lengths (the reference's DataLoader hands over a list / CPU tensor): ONE pinned, non-blocking
             # copy up front -- a blocking H2D copy in the middle of the step drains the launch pipeline (~4 ms per step)
@@ -261,12 +273,13 @@ class GanTrainStep(ModelTrainer):
             HF.amax_begin_step(word_embs.device)        # zeroed amax slots of this step (fp16 split mode only; one fill launch)
         prev_side = HF.set_wgrad_side_stream(self.overlap_weight_gradients and word_embs.is_cuda)
         try:
-            return self._step(word_embs, sent_embs, lengths, class_ids, real_imgs, noise, eps, aug_u, aug_q)
+            return self._step(word_embs, sent_embs, lengths, class_ids, real_imgs, noise, eps, aug_u, aug_q, aug_g)
         finally:
             HF.set_wgrad_side_stream(prev_side)
 
-    def _step(self, word_embs, sent_embs, lengths, class_ids, real_imgs, noise, eps, aug_u=None, aug_q=None) -> Dict[str, Tensor]:
-        fw = self._gen_forward(word_embs, sent_embs, lengths, noise, eps, aug_u, aug_q)
+    def _step(self, word_embs, sent_embs, lengths, class_ids, real_imgs, noise, eps, aug_u=None, aug_q=None,
+              aug_g=None) -> Dict[str, Tensor]:
+        fw = self._gen_forward(word_embs, sent_embs, lengths, noise, eps, aug_u, aug_q, aug_g)
         out: Dict[str, Tensor] = {}
         # ---- discriminator updates (train.py:123-130) ----
         # The three updates are independent of each other (each D has its own weights, optimiser and images), so each runs on
@@ -299,7 +312,7 @@ class GanTrainStep(ModelTrainer):
         return self._results(fw, out)
 
     # -- the phases of the step: _step() runs them eagerly, capture_segments() records each into a graph of its own --------
-    def _gen_forward(self, word_embs, sent_embs, lengths, noise, eps, aug_u=None, aug_q=None) -> "_Forward":
+    def _gen_forward(self, word_embs, sent_embs, lengths, noise, eps, aug_u=None, aug_q=None, aug_g=None) -> "_Forward":
         b = word_embs.shape[0]
         labels = self._make_match_labels(b)
         mask = self._make_mask(lengths, word_embs.shape[2])
@@ -319,10 +332,29 @@ class GanTrainStep(ModelTrainer):
             aug_q = torch.rand(3 * len(self.Ds), b, 4, dtype=torch.float32, device=word_embs.device, generator=self.rng)
         elif tuple(aug_q.shape) != (3 * len(self.Ds), b, 4):
             raise ValueError(f"aug_q must be [{3 * len(self.Ds)}, {b}, 4], got {tuple(aug_q.shape)}")
-        return _Forward(labels, mask, *self.G(noise, sent_embs, word_embs, mask, eps), aug_u, aug_q)
+        if not self.geometry:
+            return _Forward(labels, mask, *self.G(noise, sent_embs, word_embs, mask, eps), aug_u, aug_q)
+        slots = 3 * len(self.Ds)
+        if aug_g is None:                                   # the geometric stages' uniforms: the last draw of the step
+            aug_g = torch.rand(slots, b, GEO_UNIFORMS, dtype=torch.float32, device=word_embs.device, generator=self.rng)
+        elif tuple(aug_g.shape) != (slots, b, GEO_UNIFORMS):
+            raise ValueError(f"aug_g must be [{slots}, {b}, {GEO_UNIFORMS}], got {tuple(aug_g.shape)}")
+        # every slot's matrices by ONE launch: they do not depend on the resolution, so the discriminators' sizes share them
+        aug_m = HF.geometry_matrices(aug_g.reshape(-1, GEO_UNIFORMS), self.geometry, None if self.ada is None else self.ada.p)
+        return _Forward(labels, mask, *self.G(noise, sent_embs, word_embs, mask, eps), aug_u, aug_q, aug_m.view(slots, b, 6))
 
     def _augmenter(self, fw: "_Forward", first: int, count: int) -> Optional[Callable]:
-        """What the losses apply to the images before D: slots first .. first + count - 1 of the step's uniforms, one per tensor."""
+        """What the losses apply to the images before D: slots first .. first + count - 1 of the step's uniforms, one per tensor;
+        the geometric warp first, then DiffAugment's stages."""
+        color = self._diffaugmenter(fw, first, count)
+        if fw.aug_m is None:
+            return color
+        m = fw.aug_m[first:first + count].reshape(-1, 6)    # (adjacent slots: a view, no launch)
+        if color is None:
+            return lambda xs: HF.affine_warp(xs, m)
+        return lambda xs: color(HF.affine_warp(xs, m))
+
+    def _diffaugmenter(self, fw: "_Forward", first: int, count: int) -> Optional[Callable]:
         if fw.aug_u is None:
             return None
         u = fw.aug_u[first:first + count].reshape(-1, 8)    # (adjacent slots: a view, no launch)
@@ -405,7 +437,8 @@ class GanTrainStep(ModelTrainer):
         out["mu"], out["logvar"] = fw.mu.detach(), fw.logvar.detach()
         return out
 
-    def _warm_up(self, who: str, word_embs, sent_embs, lengths, real_imgs, warmup: int, noise, eps, aug_u=None, aug_q=None) -> None:
+    def _warm_up(self, who: str, word_embs, sent_embs, lengths, real_imgs, warmup: int, noise, eps, aug_u=None, aug_q=None,
+                 aug_g=None) -> None:
         """What both captures do first: `warmup` real train steps off the default stream, then the host-side tables."""
         if not (isinstance(lengths, Tensor) and lengths.is_cuda and lengths.dtype == torch.int64):
             raise ValueError(f"{who}(): lengths must be an int64 device tensor")
@@ -413,7 +446,7 @@ class GanTrainStep(ModelTrainer):
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):                      # warm-up off the default stream: tables, caches, allocator pools
             for _ in range(max(1, warmup)):
-                self.step(word_embs, sent_embs, lengths, None, real_imgs, noise, eps, aug_u, aug_q)
+                self.step(word_embs, sent_embs, lengths, None, real_imgs, noise, eps, aug_u, aug_q, aug_g)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         HF.build_pack_tables()                             # the batched re-pack's job tables: host work, not capturable
@@ -421,24 +454,25 @@ class GanTrainStep(ModelTrainer):
     # -- whole-step HIP graph ----------------------------------------------------------------------------------------
     def capture(self, word_embs: Tensor, sent_embs: Tensor, lengths: Tensor, real_imgs: Sequence[Tensor], warmup: int = 2,
                 noise: Optional[Tensor] = None, eps: Optional[Tensor] = None, aug_u: Optional[Tensor] = None,
-                aug_q: Optional[Tensor] = None) -> "GraphedStep":
+                aug_q: Optional[Tensor] = None, aug_g: Optional[Tensor] = None) -> "GraphedStep":
         """Capture one full train step (all four optimiser updates, every stream) into a HIP graph.
 
         The arguments become the graph's STATIC input buffers: copy each new batch into them (`.copy_()`) and call `replay()`.
         `lengths` must be a device int64 tensor (no host reads inside the step); noise and the CA-net eps are drawn inside the
         graph (graph-safe Philox state) unless static `noise` / `eps` buffers are given, and so are the augmentation's uniforms
-        (`aug_u`, with an `augment` policy; `aug_q`, the gates' uniforms, with `augment_p` / `ada_target`); BatchNorm counters, the
+        (`aug_u`, with an `augment` policy; `aug_q`, the gates' uniforms, with `augment_p` / `ada_target`; `aug_g`, with `geometry`,
+        whose matrix launch is part of the graph and reads the live p); BatchNorm counters, the
         Adam step counters and the augmentation probability with its controller's window live in device memory, so replays keep
         advancing -- and adapting -- exactly like eager steps.  The warm-up steps are real
         training steps.  Single-process only: with world_size > 1 run the eager `step()`."""
         if self.g_buckets.active:
             raise RuntimeError("capture(): the all-reduce path is not captured; use step() under torch.distributed")
-        self._warm_up("capture", word_embs, sent_embs, lengths, real_imgs, warmup, noise, eps, aug_u, aug_q)
+        self._warm_up("capture", word_embs, sent_embs, lengths, real_imgs, warmup, noise, eps, aug_u, aug_q, aug_g)
         graph = torch.cuda.CUDAGraph()
         if self.rng.device.type == "cuda":
             graph.register_generator_state(self.rng)       # noise / eps draws inside the graph advance this generator on replay
         with torch.cuda.graph(graph):
-            out = self.step(word_embs, sent_embs, lengths, None, real_imgs, noise, eps, aug_u, aug_q)
+            out = self.step(word_embs, sent_embs, lengths, None, real_imgs, noise, eps, aug_u, aug_q, aug_g)
         return GraphedStep(graph, out, self)
 
     def _mark_replayed(self) -> None:
@@ -451,7 +485,7 @@ class GanTrainStep(ModelTrainer):
     # -- segment-wise HIP graphs for world > 1 --------------------------------------------------------------------------
     def capture_segments(self, word_embs: Tensor, sent_embs: Tensor, lengths: Tensor, real_imgs: Sequence[Tensor], warmup: int = 2,
                          noise: Optional[Tensor] = None, eps: Optional[Tensor] = None, aug_u: Optional[Tensor] = None,
-                         aug_q: Optional[Tensor] = None) -> "SegmentedStep":
+                         aug_q: Optional[Tensor] = None, aug_g: Optional[Tensor] = None) -> "SegmentedStep":
         """The train step as NINE HIP graphs with the gradient exchange launched between them -- the form for world_size > 1, where
         the whole-step graph of capture() cannot be used (the RCCL collectives are not captured) and an eager step costs every rank
         ~11 ms of Python per 27 ms step on host cores the 8 ranks share:
@@ -465,7 +499,7 @@ class GanTrainStep(ModelTrainer):
         first -- and nothing overlaps the generator's 28 MB.  The arguments become static input buffers exactly as for capture();
         the graphs share one memory pool and must be replayed in capture order (SegmentedStep.replay does).  Results are
         bit-identical to the eager step (tests/test_gpu_dataparallel.py, one-rank `nccl` rehearsal)."""
-        self._warm_up("capture_segments", word_embs, sent_embs, lengths, real_imgs, warmup, noise, eps, aug_u, aug_q)
+        self._warm_up("capture_segments", word_embs, sent_embs, lengths, real_imgs, warmup, noise, eps, aug_u, aug_q, aug_g)
         # memory pools: graphs that share a pool must never run concurrently (a later capture re-uses the temporaries an earlier one
         # freed).  The three discriminator updates replay CONCURRENTLY on their own streams, so each gets a private pool for its two
         # graphs; the generator's graphs, which run alone, share one.
@@ -488,7 +522,7 @@ class GanTrainStep(ModelTrainer):
                 g0.register_generator_state(self.rng)
             with torch.cuda.graph(g0, pool=pool, capture_error_mode=mode):
                 HF.amax_begin_step(word_embs.device)
-                fw = self._gen_forward(word_embs, sent_embs, lengths, noise, eps, aug_u, aug_q)
+                fw = self._gen_forward(word_embs, sent_embs, lengths, noise, eps, aug_u, aug_q, aug_g)
             seg.gen_forward = g0
             out: Dict[str, Tensor] = {}
             # ---- discriminator updates: backward graph, (exchange), Adam graph ----

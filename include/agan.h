@@ -722,6 +722,60 @@ int agan_ada_observe(const float* score /* [n] */, int n, float threshold, int32
 int agan_ada_update(int32_t* state /* 16 words */, int nslots, int interval, double target, double rate, double p_max, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Geometric augmentation of discriminator inputs (csrc/geoaug.hip; augment.py: geometry_matrices_reference, affine_warp_reference,
+ * geoaug_reference; backend/functional.py: geometry_matrices, affine_warp): the geometric stages of adaptive discriminator
+ * augmentation (Karras et al. 2020) as ONE bilinear affine warp per tensor.  THIS text defines the warp and the matrices.
+ *
+ * Warp.  x is [N, C, H, W] fp32, 1 <= C <= 4, finite; M is [N, 6] fp32 = (a, b, tx, c, d, ty) per sample, an OUTPUT -> SOURCE map about
+ * the image centre cx = (W - 1) / 2, cy = (H - 1) / 2.  For output pixel (oy, ox), every operation in fp32 and rounded on its own:
+ *     sx = (a (ox - cx) + b (oy - cy)) + (tx W + cx)        sy = (c (ox - cx) + d (oy - cy)) + (ty H + cy)
+ *     x0 = floor(sx), fx = sx - x0;  y0, fy likewise
+ *     y[oy][ox] = sum over the taps (y0 + j, x0 + i), j outer and i inner, of  x[tap] * (wy_j * wx_i),   (w_0, w_1) = (1 - f, f)
+ * A tap outside the image contributes zero (zero fill, like the translation stage of agan_diffaug_*; no reflection).  The map is
+ * linear in x; agan_affine_warp_bwd is its exact transpose and no gradient goes to M.
+ * agan_affine_warp_fwd takes its N = n0 + n1 samples from two sources and writes one tensor, as agan_diffaug_fwd does (x1 NULL:
+ * n1 = 0); y must not overlap a source.  A thread owns 4 adjacent output pixels in all channels and stores 16 bytes per lane and
+ * channel where W % 4 == 0 and y is 16-byte aligned, else one pixel; the taps are dword loads.  It works for ANY finite matrix.
+ * agan_affine_warp_bwd is a gather over dy: a thread owns one input pixel, walks the integer bounding box of the outputs that can
+ * reach it -- half-extents |inv00| + |inv01| and |inv10| + |inv11| of the inverse linear part, padded by one on every side, each
+ * clamped at 32 -- recomputes every candidate's source position with the forward's own arithmetic and adds dy * weight for the tap
+ * that lands on its pixel, in row-major candidate order.  It is SPECIFIED for linear parts that shrink no axis below 1/16 (beyond
+ * that the clamp drops contributions; a singular matrix gives meaningless numbers, never a fault); dx must not overlap dy.
+ * No atomics, no workspace, one fixed summation order: run-to-run identical, graph-capturable; the outputs' contents on entry do
+ * not matter.
+ *
+ * Matrices.  g is [n, 16] fp32 uniforms in [0, 1): slots 0..4 stage values, slots 8..12 stage gates, the rest reserved; geometry is a
+ * mask of AGAN_GEOAUG_* (stage order = bit order).  The linear part is the product, LEFT TO RIGHT, of the applied stages' own
+ * output -> source maps, 2 x 2 products in fp32:
+ *   XFLIP   diag(-1, 1) iff g0 >= 0.5, else nothing
+ *   ROT90   k = min(int(4 g1), 3); [[c, -s], [s, c]] with (c, s) from the table (1, 0), (0, 1), (-1, 0), (0, -1) -- no trig
+ *   SCALE   s I, s = exp2(0.7 g2 - 0.35)
+ *   ROTATE  [[cos t, -sin t], [sin t, cos t]], t = (2 g3 - 1) pi
+ *   ANISO   diag(r, 1 / r), r = exp2(0.7 g4 - 0.35)
+ * and tx = ty = 0.  With p NULL every stage whose bit is set applies.  With p -- ONE fp32 in DEVICE memory, read when the kernel runs,
+ * word AGAN_ADA_P_WORD of the controller's state -- stage k applies iff its bit is set and g[8 + k] < *p (fp32 compare; a NaN p passes
+ * nothing).  A stage that does not apply is skipped, not multiplied in: a sample with no stage gets exactly (1, 0, 0, 0, 1, 0), and
+ * XFLIP / ROT90 alone give entries exactly in {0, +-1} -- the warp is then the flip / quarter turn of the pixels, bit for bit, on
+ * square images.  The bounded uniform log-scales (same standard deviation as the paper's log-normal 0.2) bound the backward's box:
+ * at most 7 candidates per axis.  One thread per sample, one launch.
+ * AGAN_EINVAL with a message before any launch: a null pointer (p may be NULL), n < 1, geometry outside 0..31; for the warps C outside
+ * 1..4, a non-positive size, H or W above 2^24, N * C * H * W >= 2^31.
+ * ---------------------------------------------------------------------------------------------- */
+#define AGAN_GEOAUG_XFLIP 1
+#define AGAN_GEOAUG_ROT90 2
+#define AGAN_GEOAUG_SCALE 4
+#define AGAN_GEOAUG_ROTATE 8
+#define AGAN_GEOAUG_ANISO 16
+#define AGAN_GEOAUG_ALL 31
+#define AGAN_GEOAUG_UNIFORMS 16
+int agan_geoaug_matrix(const float* g /* [n, 16] */, const float* p /* DEVICE, one fp32, or NULL */, int geometry, float* M /* [n, 6] */,
+                       int n, void* stream);
+int agan_affine_warp_fwd(const float* x0 /* [n0, C, H, W] */, const float* x1 /* [n1, C, H, W] or NULL */, int n0, int n1,
+                         const float* M /* [n0 + n1, 6] */, float* y /* [n0 + n1, C, H, W] */, int C, int H, int W, void* stream);
+int agan_affine_warp_bwd(const float* dy /* [N, C, H, W] */, const float* M /* [N, 6] */, float* dx /* [N, C, H, W] */, int N, int C, int H,
+                         int W, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Exponential moving average of a module's weights (csrc/ema.hip; optim.py: FlatEMA; backend/functional.py: ema_update_, ema_reference).
  * One call updates every segment of a DEVICE-resident table:  dst[i] = fma(omb, src[i] - dst[i], dst[i])  in fp32, src only read.
  * Segment i owns workgroups [first_block, next segment's first_block); the last one runs to total_blocks.  A segment moves 16 bytes per
