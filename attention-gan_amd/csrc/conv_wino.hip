@@ -18,6 +18,7 @@
 #include "conv_common.h"
 
 #include <cstring>
+#include <type_traits>
 
 using namespace agan;
 using namespace agan::conv;
@@ -559,16 +560,24 @@ __global__ __launch_bounds__(256) void wino_s2_weight_transform_kernel(const flo
 // The contraction index of the 16 products is the TILE: both operands are transformed activations, staged [position][channel][8 tiles]
 // in LDS (a lane's 16 bytes = 4 k-steps of its channel), produced by the threads straight from global memory (a thread loads its tile's
 // 4x4 x patch / 2x2 dy tile, transforms it and writes 16 values; no raw copy in LDS).  A workgroup owns 64 output x 64 input channels
-// (wave = one 32 x 32 fragment pair, all 16 positions: 256 accumulator registers, output transform in registers) and a range of tile
-// octets; per octet 64 MFMAs per wave, ONE barrier.  Partial results [cout][cin][3][3] per pixel split, summed by sum_slabs_kernel.
-__global__ __launch_bounds__(256, 1) void conv_wino_wgrad_f32_kernel(const float* __restrict__ x, const float* __restrict__ dy, float* __restrict__ part,
+// and a range of tile octets.  It has 8 waves, TWO per SIMD: waves 0-3 hold one 32 x 32 fragment pair each for positions 0-7, waves 4-7
+// the same fragment pairs for positions 8-15 (128 accumulator registers per wave, 32 MFMAs per octet), and each of the 512 threads
+// produces ONE (tile, channel) pair of each operand.  A wave's own VALU work is not hidden by its own MFMAs, another wave's is (DESIGN
+// section 4), and two waves running the same program stay in phase -- so the two groups are offset by construction: the lower group
+// transforms / loads in the first four of its eight stages of an octet and only multiplies in the last four, the upper group the other
+// way round (measured: no faster than both groups on the same stages -- what pays is two waves per SIMD and few VALU instructions
+// per wave).  ONE barrier per octet.  The output transform needs all 16 positions: after the octet loop the groups swap halves of their
+// accumulators through LDS (the operand buffers are dead by then) -- the lower group finishes registers 0-7 of the fragment, the upper
+// group registers 8-15.  Partial results [tap][cout][cin] per pixel split, summed by wino_wgrad_sum_kernel.
+__global__ __launch_bounds__(512, 1) void conv_wino_wgrad_f32_kernel(const float* __restrict__ x, const float* __restrict__ dy, float* __restrict__ part,
                                                                      const Geom g, const WinoWgradPlan wp) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     constexpr int ZV = 16 * 64 * 8;                               // floats of one operand image [pos][64 channels][8 tiles]
     float* const L = reinterpret_cast<float*>(lds);               // [2 buffers][Z | V]
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int fj = w & 1, fi = w >> 1;                            // cout / cin fragment of this wave
+    const int up = w >> 2;                                        // position half of this wave: positions 8 * up ... + 7
+    const int fj = w & 1, fi = (w >> 1) & 1;                      // cout / cin fragment of this wave
     const int l31 = lane & 31, lh = lane >> 5;
     int jt, it, split;
     {
@@ -583,84 +592,87 @@ __global__ __launch_bounds__(256, 1) void conv_wino_wgrad_f32_kernel(const float
     const __amdgpu_buffer_rsrc_t rd = make_rsrc(dy, (size_t)g.B * g.Cout * ihw * sizeof(float));
     const int tw8 = g.OW >> 4, th = g.OH >> 1;                    // tile octets per row, tile rows per image
 
-    // this thread's two (tile, channel) pairs of each operand: tile = tid & 7, channel = (tid >> 3) + 32 k
+    // this thread's (tile, channel) pair of each operand: tile = tid & 7, channel = tid >> 3
     const int tj = tid & 7, tc = tid >> 3;
-    float xr[2][16];
-    float2 dr[2][2];
-    // loads of octet o in 4 pieces (pair k = lp >> 1; x rows 2 * (lp & 1), +1; the dy tile with the first half)
+    float xr[16];
+    float2 dr[2];
+    // A foreign VALU instruction gets an issue slot about every 21 cycles beside the other wave's MFMAs: the address
+    // arithmetic of the loads is kept to one add per row -- the thread's part of an offset (channel plane, tile column) is formed here
+    // once, the octet's part (image, tile row, octet column; row validity) is scalar -- and the two inner columns of a patch row, always
+    // inside the image and 8-byte aligned (IW and the plane size are even), come as one 8-byte load.
+    const int xthr = (i0 + tc) * ihw + 2 * tj - 1, dthr = (j0 + tc) * ihw + 2 * tj;
+    const bool cvx = i0 + tc < g.Cin, cvd = j0 + tc < g.Cout;
+    const bool tj_first = tj == 0, tj_last = tj == 7;
+    // loads of octet o in 3 pieces (x rows 0-1, x rows 2-3, the dy tile)
     auto load_piece = [&](int o, int lp) {
         const bool ov = o < o_end;
         const int txo = o % tw8, t1 = o / tw8;
         const int ty = t1 % th, b = t1 / th;
-        const int tx = txo * 8 + tj;
-        const int k = lp >> 1, half = lp & 1;
-        const int ci = i0 + tc + 32 * k, co = j0 + tc + 32 * k;
-        const bool cv = ov & (ci < g.Cin);
-        const int xbase = (b * g.Cin + ci) * ihw + 2 * tx - 1;
-        const bool c0ok = tx > 0, c3ok = 2 * tx + 2 < g.IW;
+        if (lp < 2) {
+            const int sx = b * g.Cin * ihw + 16 * txo;
+            const bool c0ok = !(tj_first & (txo == 0)), c3ok = !(tj_last & (txo == tw8 - 1));      // patch columns -1 / IW of the edge tiles
 #pragma unroll
-        for (int ii = 0; ii < 2; ++ii) {
-            const int i = 2 * half + ii;
-            const int iy = 2 * ty - 1 + i;
-            const bool rv = cv & ((unsigned)iy < (unsigned)g.IH);
-            const unsigned ro = (unsigned)(xbase + iy * g.IW) * 4u;
-            xr[k][i * 4 + 0] = buf_load(rx, (rv & c0ok) ? ro : kOOB);
-            xr[k][i * 4 + 1] = buf_load(rx, rv ? ro + 4u : kOOB);
-            xr[k][i * 4 + 2] = buf_load(rx, rv ? ro + 8u : kOOB);
-            xr[k][i * 4 + 3] = buf_load(rx, (rv & c3ok) ? ro + 12u : kOOB);
-        }
-        if (half == 0) {
-            const bool dv = ov & (co < g.Cout);
-            const int dbase = (b * g.Cout + co) * ihw + 2 * ty * g.OW + 2 * tx;
+            for (int ii = 0; ii < 2; ++ii) {
+                const int i = 2 * lp + ii;
+                const int iy = 2 * ty - 1 + i;
+                const bool rv = cvx & (ov & ((unsigned)iy < (unsigned)g.IH));
+                const unsigned ro = (unsigned)(xthr + (sx + iy * g.IW)) * 4u;
+                xr[i * 4 + 0] = buf_load(rx, (rv & c0ok) ? ro : kOOB);
+                const float2 mid = __builtin_bit_cast(float2, __builtin_amdgcn_raw_buffer_load_b64(rx, rv ? ro + 4u : kOOB, 0, 0));
+                xr[i * 4 + 1] = mid.x;
+                xr[i * 4 + 2] = mid.y;
+                xr[i * 4 + 3] = buf_load(rx, (rv & c3ok) ? ro + 12u : kOOB);
+            }
+        } else {
+            const bool dv = cvd & ov;
+            const int sd = b * g.Cout * ihw + 2 * ty * g.OW + 16 * txo;
 #pragma unroll
             for (int a = 0; a < 2; ++a)
-                dr[k][a] = __builtin_bit_cast(float2, __builtin_amdgcn_raw_buffer_load_b64(rd, dv ? (unsigned)(dbase + a * g.OW) * 4u : kOOB, 0, 0));
+                dr[a] = __builtin_bit_cast(float2, __builtin_amdgcn_raw_buffer_load_b64(rd, dv ? (unsigned)(dthr + (sd + a * g.OW)) * 4u : kOOB, 0, 0));
         }
     };
     auto load_oct = [&](int o) {
 #pragma unroll
-        for (int lp = 0; lp < 4; ++lp) load_piece(o, lp);
+        for (int lp = 0; lp < 3; ++lp) load_piece(o, lp);
     };
-    // transform + LDS stores of the loaded octet in 8 pieces (pair k = tp >> 2; V rows 0-1, V rows 2-3, Z rows 0-1, Z rows 2-3)
-    float tt_[2][4][4];                                          // t = B^T d of pair k, kept between its two V pieces
-    auto transform_piece = [&](float* buf, int tp) {             // buf: Z at 0, V at ZV
-        const int k = tp >> 2, sub = tp & 3;
-        const int ch = tc + 32 * k;
+    // transform + LDS stores of the loaded octet in 4 pieces (V rows 0-1, V rows 2-3, Z rows 0-1, Z rows 2-3)
+    float tt_[4][4];                                             // t = B^T d, kept between the two V pieces
+    auto transform_piece = [&](float* buf, int sub) {            // buf: Z at 0, V at ZV
         if (sub == 0) {
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
-                const float d0 = xr[k][c], d1 = xr[k][4 + c], d2 = xr[k][8 + c], d3 = xr[k][12 + c];
-                tt_[k][0][c] = d0 - d2; tt_[k][1][c] = d1 + d2; tt_[k][2][c] = d2 - d1; tt_[k][3][c] = d3 - d1;
+                const float d0 = xr[c], d1 = xr[4 + c], d2 = xr[8 + c], d3 = xr[12 + c];
+                tt_[0][c] = d0 - d2; tt_[1][c] = d1 + d2; tt_[2][c] = d2 - d1; tt_[3][c] = d3 - d1;
             }
         }
         if (sub < 2) {                                           // V = (B^T d) B, rows 2 * sub, + 1
 #pragma unroll
             for (int x2 = 0; x2 < 2; ++x2) {
                 const int xi = 2 * sub + x2;
-                const float* t = tt_[k][xi];
-                float* o = buf + ZV + ((xi * 4) * 64 + ch) * 8 + tj;
+                const float* t = tt_[xi];
+                float* o = buf + ZV + ((xi * 4) * 64 + tc) * 8 + tj;
                 o[0] = t[0] - t[2]; o[64 * 8] = t[1] + t[2]; o[2 * 64 * 8] = t[2] - t[1]; o[3 * 64 * 8] = t[3] - t[1];
             }
         } else {                                                 // Z = G e G^T, rows 2 * (sub - 2), + 1
-            const float e00 = dr[k][0].x, e01 = dr[k][0].y, e10 = dr[k][1].x, e11 = dr[k][1].y;
+            const float e00 = dr[0].x, e01 = dr[0].y, e10 = dr[1].x, e11 = dr[1].y;
 #pragma unroll
             for (int x2 = 0; x2 < 2; ++x2) {
                 const int xi = 2 * (sub - 2) + x2;
                 const float u0 = xi == 0 ? e00 : (xi == 1 ? 0.5f * (e00 + e10) : (xi == 2 ? 0.5f * (e00 - e10) : e10));
                 const float u1 = xi == 0 ? e01 : (xi == 1 ? 0.5f * (e01 + e11) : (xi == 2 ? 0.5f * (e01 - e11) : e11));
-                float* o = buf + ((xi * 4) * 64 + ch) * 8 + tj;
+                float* o = buf + ((xi * 4) * 64 + tc) * 8 + tj;
                 o[0] = u0; o[64 * 8] = 0.5f * (u0 + u1); o[2 * 64 * 8] = 0.5f * (u0 - u1); o[3 * 64 * 8] = u1;
             }
         }
     };
     auto transform_store = [&](float* buf) {
 #pragma unroll
-        for (int tp = 0; tp < 8; ++tp) transform_piece(buf, tp);
+        for (int tp = 0; tp < 4; ++tp) transform_piece(buf, tp);
     };
 
-    f32x16 acc[16];
+    f32x16 acc[8];                                               // positions 8 * up + q
 #pragma unroll
-    for (int q = 0; q < 16; ++q)
+    for (int q = 0; q < 8; ++q)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[q][r] = 0.f;
 
@@ -669,47 +681,76 @@ __global__ __launch_bounds__(256, 1) void conv_wino_wgrad_f32_kernel(const float
         transform_store(L);
         load_oct(o_beg + 1);
         lds_barrier_w();
-        const unsigned zl = (unsigned)((fj * 32 + l31) * 8 + lh * 4), vl = (unsigned)(ZV + (fi * 32 + l31) * 8 + lh * 4);
-        for (int o = o_beg; o < o_end; ++o) {
+        const unsigned zl = (unsigned)(up * 8 * 64 * 8 + (fj * 32 + l31) * 8 + lh * 4), vl = (unsigned)(ZV + up * 8 * 64 * 8 + (fi * 32 + l31) * 8 + lh * 4);
+        // one octet of a wave: 8 stages of [next stage's fragments][a piece of the other work][4 MFMAs].  The other work -- the next
+        // octet's transform (its patches were loaded one octet ago) and the loads of the octet after that -- stands in the four stages
+        // from S0 on; the other four are MFMAs and their fragment reads only.  S0 = 0 for the lower group and 4 for the upper one: while
+        // one wave of a SIMD issues VALU / memory instructions between its MFMAs, the other one keeps the matrix pipe fed.
+        auto octet = [&](auto s0, int o) {
+            constexpr int S0 = decltype(s0)::value;
             const float* cur = L + ((o - o_beg) & 1) * (2 * ZV);
             float* nxt = L + (((o - o_beg) & 1) ^ 1) * (2 * ZV);
-            // the next octet's operands (its patches were loaded one octet ago) are transformed and written, the octet after that is loaded,
-            // all in the shadow of this octet's 64 MFMAs -- pinned stage by stage as in the gather kernel
             u32x4 zf[2], vf[2];
             zf[0] = *reinterpret_cast<const u32x4*>(cur + zl);
             vf[0] = *reinterpret_cast<const u32x4*>(cur + vl);
 #pragma unroll
-            for (int pos = 0; pos < 16; ++pos) {
-                if (pos + 1 < 16) {
-                    zf[(pos + 1) & 1] = *reinterpret_cast<const u32x4*>(cur + (pos + 1) * 64 * 8 + zl);
-                    vf[(pos + 1) & 1] = *reinterpret_cast<const u32x4*>(cur + (pos + 1) * 64 * 8 + vl);
+            for (int q = 0; q < 8; ++q) {
+                if (q + 1 < 8) {
+                    zf[(q + 1) & 1] = *reinterpret_cast<const u32x4*>(cur + (q + 1) * 64 * 8 + zl);
+                    vf[(q + 1) & 1] = *reinterpret_cast<const u32x4*>(cur + (q + 1) * 64 * 8 + vl);
                 }
                 // no branch around the pieces (after the last octet they transform zeros into the buffer nobody reads): one basic block per
-                // position, so that the pieces can be issued BETWEEN the four MFMAs of the position (below)
-                if (pos >= 1 && pos <= 8) transform_piece(nxt, pos - 1);
-                if (pos >= 9 && pos <= 12) load_piece(o + 2, pos - 9);          // (past the range: zero range, nothing is fetched)
+                // stage, so that the pieces can be issued BETWEEN the four MFMAs of the stage (below).  xr is dead once piece 0 has formed
+                // B^T d, dr after piece 3: the loads of octet o + 2 follow them (past the range: zero range, nothing is fetched)
+                if (q >= S0 && q < S0 + 4) transform_piece(nxt, q - S0);
+                if (q >= S0 + 1 && q < S0 + 4) load_piece(o + 2, q - S0 - 1);
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
-                    acc[pos] = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(zf[pos & 1][j]), __uint_as_float(vf[pos & 1][j]), acc[pos], 0, 0, 0);
-                // a wave is alone on its SIMD and issues in order: whatever FOLLOWS four back-to-back MFMAs in program order waits for all
-                // of them to issue, i.e. overlaps only the last one.  The scalar / LDS / global-load instructions of the piece are spread
-                // over the four 64-cycle shadows instead (the VALU ones cost their ~6 cycles wherever they stand: on gfx950 the fp32 MFMA
-                // and the vector ALU do not overlap -- profiles/micro/mfma_issue.hip).
+                    acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(zf[q & 1][j]), __uint_as_float(vf[q & 1][j]), acc[q], 0, 0, 0);
+                // a wave issues in order: whatever FOLLOWS four back-to-back MFMAs in program order waits for all of them to issue.  The
+                // scalar / LDS / global-load instructions of the piece are spread over the four 64-cycle shadows instead; the VALU ones
+                // cost this wave ~6 cycles each wherever they stand (profiles/micro/mfma_issue.hip) -- cycles in which the SIMD's other
+                // wave, in its MFMA-only half, has the matrix pipe
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);          // MFMA
-                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);          // DS read (the next position's fragments)
+                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);          // DS read (the next stage's fragments)
                     __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);          // VALU
-                    __builtin_amdgcn_sched_group_barrier(0x020, 3, 0);          // VMEM read
-                    __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);          // DS write
+                    __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);          // VMEM read
+                    __builtin_amdgcn_sched_group_barrier(0x200, 2, 0);          // DS write
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
             lds_barrier_w();
+        };
+        if (up == 0) {
+            for (int o = o_beg; o < o_end; ++o) octet(std::integral_constant<int, 0>{}, o);
+        } else {
+            for (int o = o_beg; o < o_end; ++o) octet(std::integral_constant<int, 4>{}, o);
         }
     }
 
-    // ---- dw = A^T M A in registers; D[cout][cin]: lane l31 = input channel, register -> output channel.  The slab is [tap][cout][cin]:
+    // ---- dw = A^T M A needs the 16 positions of a (cout, cin) pair in one lane.  The two waves of a fragment pair swap halves: wave w
+    //      leaves the accumulator registers its partner finishes -- 8 positions x 8 registers, as 16 float4 per lane -- in its 16 KB of
+    //      the (now dead) operand buffers: the lower group finishes registers 0-7, the upper group registers 8-15.  Once per workgroup. ----
+    auto hand_over = [&](auto upc) {
+        constexpr int R0 = decltype(upc)::value ? 0 : 8;         // the registers the partner finishes
+        f32x4* const mine = reinterpret_cast<f32x4*>(L) + w * (16 * 64) + lane;
+#pragma unroll
+        for (int q = 0; q < 8; ++q)
+#pragma unroll
+            for (int rq = 0; rq < 2; ++rq) {
+                f32x4 v;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = acc[q][R0 + 4 * rq + e];
+                mine[(q * 2 + rq) * 64] = v;
+            }
+    };
+    if (up == 0) hand_over(std::integral_constant<int, 0>{});
+    else hand_over(std::integral_constant<int, 1>{});
+    lds_barrier_w();
+
+    // ---- D[cout][cin]: lane l31 = input channel, register -> output channel.  The slab is [tap][cout][cin]:
     //      a store instruction writes 128 contiguous bytes per half wave (OIHW would scatter its lanes 36 bytes apart: the 38 MB of slabs
     //      of a 128-way pixel split took 30 us that way); wino_wgrad_sum_kernel transposes while it sums.  Addresses: lane part in the
     //      vector offset once, (register, tap) part in the scalar offset. ----
@@ -719,25 +760,40 @@ __global__ __launch_bounds__(256, 1) void conv_wino_wgrad_f32_kernel(const float
     const int cob = j0 + fj * 32;                                // + (r & 3) + 8 (r >> 2) + 4 lh
     const unsigned vo = ci < g.Cin ? (unsigned)(4 * lh * g.Cin + ci) * 4u : kOOB;
     const unsigned tapb = (unsigned)(g.Cout * g.Cin) * 4u;
+    const f32x4* const theirs = reinterpret_cast<const f32x4*>(L) + (w ^ 4) * (16 * 64) + lane;
+    auto finish = [&](auto upc) {
+        constexpr int UP = decltype(upc)::value;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        if (cob + 8 * (r >> 2) >= g.Cout) continue;             // (a group of 8 channels is valid as a whole: Cout is a multiple of 8)
-        float c[3][4];                                           // rows of A^T M
+        for (int rq = 0; rq < 2; ++rq) {
+            const int rg = 2 * UP + rq;                          // r >> 2 of the four registers of this round
+            if (cob + 8 * rg >= g.Cout) continue;                // (a group of 8 channels is valid as a whole: Cout is a multiple of 8)
+            f32x4 oth[8];                                        // the partner's positions 8 * (1 - UP) + q of registers 4 * rg ... + 3
 #pragma unroll
-        for (int nu = 0; nu < 4; ++nu) {
-            const float m0 = acc[nu][r], m1 = acc[4 + nu][r], m2 = acc[8 + nu][r], m3 = acc[12 + nu][r];
-            c[0][nu] = m0 + m1 + m2;
-            c[1][nu] = m1 - m2;
-            c[2][nu] = m1 + m2 + m3;
+            for (int q = 0; q < 8; ++q) oth[q] = theirs[(q * 2 + rq) * 64];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int r = 4 * rg + e;
+                float c[3][4];                                   // rows of A^T M
+#pragma unroll
+                for (int nu = 0; nu < 4; ++nu) {
+                    const float m0 = UP ? oth[nu][e] : acc[nu][r], m1 = UP ? oth[4 + nu][e] : acc[4 + nu][r];
+                    const float m2 = UP ? acc[nu][r] : oth[nu][e], m3 = UP ? acc[4 + nu][r] : oth[4 + nu][e];
+                    c[0][nu] = m0 + m1 + m2;
+                    c[1][nu] = m1 - m2;
+                    c[2][nu] = m1 + m2 + m3;
+                }
+                const unsigned so = (unsigned)((cob + e + 8 * rg) * g.Cin) * 4u;
+#pragma unroll
+                for (int rr = 0; rr < 3; ++rr) {
+                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, c[rr][0] + c[rr][1] + c[rr][2]), ro, vo, so + (unsigned)(rr * 3 + 0) * tapb, 0);
+                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, c[rr][1] - c[rr][2]), ro, vo, so + (unsigned)(rr * 3 + 1) * tapb, 0);
+                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, c[rr][1] + c[rr][2] + c[rr][3]), ro, vo, so + (unsigned)(rr * 3 + 2) * tapb, 0);
+                }
+            }
         }
-        const unsigned so = (unsigned)((cob + (r & 3) + 8 * (r >> 2)) * g.Cin) * 4u;
-#pragma unroll
-        for (int rr = 0; rr < 3; ++rr) {
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, c[rr][0] + c[rr][1] + c[rr][2]), ro, vo, so + (unsigned)(rr * 3 + 0) * tapb, 0);
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, c[rr][1] - c[rr][2]), ro, vo, so + (unsigned)(rr * 3 + 1) * tapb, 0);
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, c[rr][1] + c[rr][2] + c[rr][3]), ro, vo, so + (unsigned)(rr * 3 + 2) * tapb, 0);
-        }
-    }
+    };
+    if (up == 0) finish(std::integral_constant<int, 0>{});
+    else finish(std::integral_constant<int, 1>{});
 }
 
 // dw[cout][cin][tap] (+)= sum over the pixel-split slabs [tap][cout][cin].  As conv.hip's sum_slabs_kernel: a workgroup covers 32 float4
@@ -899,7 +955,7 @@ WinoWgradPlan plan_wino_wgrad(const Geom& g) {
 
 void launch_wino_wgrad(const float* x, const float* dy, float* part, const Geom& g, const WinoWgradPlan& p, hipStream_t st) {
     allow_dynamic_lds<conv_wino_wgrad_f32_kernel>(160 * 1024);
-    AGAN_LAUNCH(conv_wino_wgrad_f32_kernel, dim3(p.jtiles * p.itiles * p.psplit), dim3(256), (size_t)p.smem_bytes, st, x, dy, part, g, p);
+    AGAN_LAUNCH(conv_wino_wgrad_f32_kernel, dim3(p.jtiles * p.itiles * p.psplit), dim3(512), (size_t)p.smem_bytes, st, x, dy, part, g, p);
 }
 
 void launch_wino_wgrad_sum(const float* part, const Geom& g, const WinoWgradPlan& p, float* dw, int accumulate, hipStream_t st) {
