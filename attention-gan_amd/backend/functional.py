@@ -1121,6 +1121,154 @@ def ns_gen_loss(p_fake):
     return _GenLossFn.apply(p_fake)
 
 
+# --------------------------------------------------------------------------------------------------------------
+# the text-conditional discriminator head (networks/discriminators.py: COND_DNET; include/agan.h: agan_cond_join_*, agan_cond_disc_loss)
+# --------------------------------------------------------------------------------------------------------------
+# AttnGAN's jointConv is conv3x3 over cat(h, rep(s)) on the 4x4 code.  The sentence channels are constant over the map, so
+#     conv3x3(cat(h, rep(s)), W)[n, c, i, j] = conv3x3(h, W[:, :8df])[n, c, i, j] + sum_{t valid at (i, j)} P[n, c, t]
+#     P[n, c, t] = sum_e s[n, e] * W[c, 8df + e, t]
+# with t = 3 (di + 1) + (dj + 1) the tap that reads input (i + di, j + dj), valid iff that position lies inside the map.  `cond_join`
+# adds the two terms: yi from the library's conv (computed ONCE for [real; fake]), p from its linear (once per caption).
+def _tap_mask(dtype, device) -> Tensor:
+    """[9, 4, 4]: 1 where tap t is valid at (i, j)"""
+    m = torch.zeros(9, 4, 4, dtype=dtype, device=device)
+    for t in range(9):
+        di, dj = t // 3 - 1, t % 3 - 1
+        m[t, max(0, -di):4 - max(0, di), max(0, -dj):4 - max(0, dj)] = 1
+    return m
+
+
+def _cond_join_dims(yi: Tensor, p: Tensor, wrong: bool, what: str) -> Tuple[int, int, int]:
+    """-> (B, k, C) of yi [k * B, C, 4, 4] and p [B, C, 9], or ValueError"""
+    if yi.dim() != 4 or tuple(yi.shape[2:]) != (4, 4):
+        raise ValueError(f"{what}: the image term must be [k * B, C, 4, 4], got {tuple(yi.shape)}")
+    if p.dim() != 3 or p.shape[2] != 9 or p.shape[1] != yi.shape[1]:
+        raise ValueError(f"{what}: the sentence term must be [B, {yi.shape[1]}, 9], got {tuple(p.shape)}")
+    B, C = int(p.shape[0]), int(p.shape[1])
+    if B < 1 or C < 1 or yi.shape[0] < B or yi.shape[0] % B:
+        raise ValueError(f"{what}: {yi.shape[0]} image rows are not whole groups of the {B} captions")
+    if yi.device != p.device:
+        raise ValueError(f"{what}: the image term is on {yi.device}, the sentence term on {p.device}")
+    if wrong and B < 2:
+        raise ValueError(f"{what}: the mismatched pairs (wrong=True) need at least 2 captions")
+    return B, int(yi.shape[0]) // B, C
+
+
+def cond_join_reference(yi: Tensor, p: Tensor, wrong: bool = False) -> Tensor:
+    """What cond_join computes, in torch ops, in the operands' dtype, on any device, differentiable by autograd:
+    y[n] = yi[n] + S(p[n mod B]) for the k * B rows of yi, and with `wrong` B more rows yi[b] + S(p[(b + 1) mod B]), where
+    S(p)[c, i, j] = sum of p[c, t] over the taps valid at (i, j), added in ascending t starting from yi (an invalid tap adds 0)."""
+    B, k, C = _cond_join_dims(yi, p, wrong, "cond_join_reference")
+    if yi.dtype != p.dtype:
+        raise ValueError(f"cond_join_reference: the image term is {yi.dtype}, the sentence term {p.dtype}")
+    m = _tap_mask(yi.dtype, yi.device)
+    caps, y = p.repeat(k, 1, 1), yi
+    if wrong:
+        caps, y = torch.cat([caps, p.roll(-1, 0)], dim=0), torch.cat([yi, yi[:B]], dim=0)
+    for t in range(9):
+        y = y + caps[:, :, t, None, None] * m[t]
+    return y
+
+
+class _CondJoinFn(Function):
+    @staticmethod
+    def forward(ctx, yi, p, wrong):
+        B, C = p.shape[0], p.shape[1]
+        k = yi.shape[0] // B
+        yi, p = _dev(yi, "cond_join image term"), _dev(p, "cond_join sentence term")
+        y = torch.empty(((k + wrong) * B, C, 4, 4), dtype=torch.float32, device=yi.device)
+        L.call("agan_cond_join_fwd", _p(yi), _p(p), _p(y), B, k, C, wrong, _stream())
+        ctx.dims = (B, k, C, wrong)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        B, k, C, wrong = ctx.dims
+        want_yi, want_p = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        dy = _dev(dy, "cond_join grad")
+        dyi = dp = None
+        if want_yi and not wrong:
+            dyi = dy                     # without wrong rows the image term's gradient IS dy: no launch (the generator update)
+        elif want_yi:
+            dyi = torch.empty((k * B, C, 4, 4), dtype=torch.float32, device=dy.device)
+        if want_p:
+            dp = torch.empty((B, C, 9), dtype=torch.float32, device=dy.device)
+        if dp is not None or wrong and dyi is not None:
+            L.call("agan_cond_join_bwd", _p(dy), _p(dyi if wrong else None), _p(dp), B, k, C, wrong, _stream())
+        return dyi, dp, None
+
+
+def cond_join(yi: Tensor, p: Tensor, wrong: bool = False) -> Tensor:
+    """The join of the conditional discriminator head on the HIP kernels (csrc/cond_join.hip), fp32, with autograd.
+
+    yi [k * B, C, 4, 4]: the image term, k consecutive groups of B rows, row n carrying caption n mod B.  p [B, C, 9]: the sentence
+    term per caption, channel and tap.  -> y [(k + wrong) * B, C, 4, 4]: rows n < k * B are yi[n] + S(p[n mod B]); with `wrong`, B more
+    rows yi[b] + S(p[(b + 1) mod B]) pair the FIRST group's images with the next sample's caption, cyclically (cond_join_reference
+    states it in torch ops).  The backward has one summation order and no atomics; only the gradients autograd asks for are
+    produced, and the image term's gradient without wrong rows is dy itself.  Works in fp32: 16-bit operands (activation storage)
+    are widened on the way in and their gradients cast back.  ValueError on mismatched shapes, devices or dtypes, and for
+    wrong=True with fewer than 2 captions."""
+    B, k, C = _cond_join_dims(yi, p, wrong, "cond_join")
+    for t, name in ((yi, "image"), (p, "sentence")):
+        if not t.is_cuda:
+            raise ValueError(f"cond_join: the {name} term is on {t.device}; the kernels run on the GPU (cond_join_reference runs anywhere)")
+        if t.dtype != torch.float32 and t.dtype not in _DT_OF:
+            raise ValueError(f"cond_join: the {name} term is {t.dtype}; expected float32 (or 16-bit activation storage)")
+    if yi.dtype != torch.float32:       # autograd casts the gradients back
+        yi = yi.float()
+    if p.dtype != torch.float32:
+        p = p.float()
+    return _CondJoinFn.apply(yi, p, bool(wrong))
+
+
+def _cond_scores(pu: Tensor, pc: Tensor, what: str) -> int:
+    if pu.dim() != 1 or pc.dim() != 1 or pu.numel() < 2 or pu.numel() % 2 or pc.numel() * 2 != pu.numel() * 3:
+        raise ValueError(f"{what}: expected unconditional scores [2B] of [real; fake] and conditional scores [3B] of [real; fake; wrong], "
+                         f"got {tuple(pu.shape)} and {tuple(pc.shape)}")
+    if pu.device != pc.device or pu.dtype != pc.dtype:
+        raise ValueError(f"{what}: the score vectors differ in device or dtype ({pu.device} {pu.dtype}, {pc.device} {pc.dtype})")
+    return pu.numel() // 2
+
+
+def cond_disc_loss_reference(pu: Tensor, pc: Tensor) -> Tensor:
+    """cond_disc_loss in torch ops, in the operands' dtype, on any device."""
+    B = _cond_scores(pu, pc, "cond_disc_loss_reference")
+    real = (-torch.log(pu[:B] + 1e-8)).mean() + (-torch.log(pc[:B] + 1e-8)).mean()
+    fake = ((-torch.log(1 - pu[B:] + 1e-8)).mean() + (-torch.log(1 - pc[B:2 * B] + 1e-8)).mean()
+            + (-torch.log(1 - pc[2 * B:] + 1e-8)).mean())
+    return real / 2 + fake / 3
+
+
+class _CondDiscLossFn(Function):
+    @staticmethod
+    def forward(ctx, pu, pc):
+        pu, pc = _dev(pu, "unconditional scores"), _dev(pc, "conditional scores")
+        loss = torch.empty((), dtype=torch.float32, device=pu.device)
+        dpu, dpc = torch.empty_like(pu), torch.empty_like(pc)
+        L.call("agan_cond_disc_loss", _p(pu), _p(pc), _p(loss), _p(dpu), _p(dpc), pu.numel() // 2, _stream())
+        ctx.save_for_backward(dpu, dpc)
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        dpu, dpc = ctx.saved_tensors
+        return dpu * g, dpc * g
+
+
+def cond_disc_loss(pu: Tensor, pc: Tensor) -> Tensor:
+    """The discriminator loss of a text-conditional discriminator in ONE launch (loss and both gradients): pu [2B] are the unconditional
+    scores of [real; fake], pc [3B] the conditional scores of [real; fake; wrong], all probabilities;
+        (m(-log pu_r) + m(-log pc_r)) / 2 + (m(-log(1 - pu_f)) + m(-log(1 - pc_f)) + m(-log(1 - pc_w))) / 3,   m = mean over B
+    -- AttnGAN's weights (errD_real: two terms halved; errD_fake + errD_wrong: three terms over 3) on this project's non-saturating
+    log terms with their 1e-8 guards, not BCELoss."""
+    _cond_scores(pu, pc, "cond_disc_loss")
+    if not pu.is_cuda:
+        raise ValueError(f"cond_disc_loss: the scores are on {pu.device}; the kernel runs on the GPU (cond_disc_loss_reference runs anywhere)")
+    return _CondDiscLossFn.apply(pu, pc)
+
+
 class _KLFn(Function):
     @staticmethod
     def forward(ctx, mu, logvar):

@@ -122,6 +122,9 @@ _SIGNATURES = {
     "agan_kl_loss": (c_int, [_P, _P, _P, _P, _P, c_int, _P]),
     "agan_reparam_fwd": (c_int, [_P, _P, _P, _P, c_int, _P]),
     "agan_reparam_bwd": (c_int, [_P, _P, _P, _P, _P, c_int, _P]),
+    "agan_cond_join_fwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P]),
+    "agan_cond_join_bwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P]),
+    "agan_cond_disc_loss": (c_int, [_P, _P, _P, _P, _P, c_int, _P]),
     "agan_conv2d_pack_mode": (c_int, [POINTER(Conv2dDesc), c_int]),
     "agan_conv2d_effective_prec": (c_int, [POINTER(Conv2dDesc), c_int]),
     "agan_conv2d_ws_bytes": (c_size_t, [POINTER(Conv2dDesc), c_int]),

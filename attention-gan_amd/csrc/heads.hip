@@ -35,6 +35,27 @@ __global__ __launch_bounds__(256) void disc_loss_kernel(const float* __restrict_
     if (threadIdx.x == 0) loss[0] = -s * inv;
 }
 
+// The text-conditional discriminator loss (include/agan.h: agan_cond_disc_loss): AttnGAN's weights on the non-saturating terms,
+//   (m(-log pu_r) + m(-log pc_r)) / 2 + (m(-log(1 - pu_f)) + m(-log(1 - pc_f)) + m(-log(1 - pc_w))) / 3,   m = mean over B,
+// on pu = [real; fake] and pc = [real; fake; wrong], every log guarded by 1e-8 like disc_loss_kernel's
+__global__ __launch_bounds__(256) void cond_disc_loss_kernel(const float* __restrict__ pu, const float* __restrict__ pc,
+                                                             float* __restrict__ loss, float* __restrict__ dpu, float* __restrict__ dpc, int B) {
+    __shared__ float red[4];
+    float sr = 0.f, sf = 0.f;
+    const float wr = 0.5f / B, wf = 1.f / (3.f * B);
+    for (int i = threadIdx.x; i < B; i += 256) {
+        const float ur = pu[i] + 1e-8f, cr = pc[i] + 1e-8f;
+        const float uf = 1.f - pu[B + i] + 1e-8f, cf = 1.f - pc[B + i] + 1e-8f, cw = 1.f - pc[2 * B + i] + 1e-8f;
+        sr += logf(ur) + logf(cr);
+        sf += logf(uf) + logf(cf) + logf(cw);
+        if (dpu) dpu[i] = -wr / ur, dpu[B + i] = wf / uf;
+        if (dpc) dpc[i] = -wr / cr, dpc[B + i] = wf / cf, dpc[2 * B + i] = wf / cw;
+    }
+    sr = block_sum<256>(sr, red);
+    sf = block_sum<256>(sf, red);
+    if (threadIdx.x == 0) loss[0] = -(sr * wr) - sf * wf;
+}
+
 // -mean(log(pf + 1e-8))      losses/gen_loss.py:45-46
 __global__ __launch_bounds__(256) void gen_loss_kernel(const float* __restrict__ pf, float* __restrict__ loss, float* __restrict__ dpf, int B) {
     __shared__ float red[4];
@@ -137,6 +158,12 @@ int agan_disc_loss(const float* p_real, const float* p_fake, float* loss, float*
     AGAN_REQUIRE(p_real && p_fake && loss && B > 0, "disc_loss: bad argument");
     hipLaunchKernelGGL(disc_loss_kernel, dim3(1), dim3(256), 0, as_stream(stream), p_real, p_fake, loss, dp_real, dp_fake, B);
     return check_launch("disc_loss");
+}
+
+int agan_cond_disc_loss(const float* pu, const float* pc, float* loss, float* dpu, float* dpc, int B, void* stream) {
+    AGAN_REQUIRE(pu && pc && loss && B > 0, "cond_disc_loss: bad argument");
+    hipLaunchKernelGGL(cond_disc_loss_kernel, dim3(1), dim3(256), 0, as_stream(stream), pu, pc, loss, dpu, dpc, B);
+    return check_launch("cond_disc_loss");
 }
 
 int agan_gen_loss(const float* p_fake, float* loss, float* dp_fake, int B, void* stream) {

@@ -54,6 +54,56 @@ class NonSaturatingDiscLoss(DiscLoss):
         return HF.ns_disc_loss(dx_score, dg_score)
 
 
+def _conditional(discriminator: Module, who: str) -> None:
+    if getattr(discriminator, "COND_DNET", None) is None:
+        raise ValueError(f"{who}: {type(discriminator).__name__} has no COND_DNET; build it with cond_dim=<sentence-embedding width>")
+
+
+class ConditionalDiscLoss(DiscLoss):
+    """The discriminator loss of AttnGAN's text-conditional discriminators (discriminator_loss in its miscc/losses.py): every image is
+    scored twice, alone and jointly with a sentence embedding (COND_DNET), and the joint head also sees the mismatched pairs -- a real
+    image with another sample's caption, the only adversarial signal for "this image does not show this sentence":
+
+        (m(-log Du(x)) + m(-log Dc(x, s))) / 2 + (m(-log(1 - Du(G))) + m(-log(1 - Dc(G, s))) + m(-log(1 - Dc(x, s')))) / 3
+
+    Departures from AttnGAN: the mismatched pairs are the B cyclic pairs (x_b, s_{(b+1) mod B}) where AttnGAN takes B - 1 and drops
+    the last -- equal groups are what functional.bn_groups takes; and the terms are this project's non-saturating log form with its
+    1e-8 guards (functional.cond_disc_loss), not BCELoss.
+
+    Paired path (the default, as NonSaturatingDiscLoss): ONE trunk pass over [real; fake] -- or over the augmenter's output -- under
+    bn_groups(2), then uncond(h), cond(h, sent, wrong=True) and ONE loss launch.  The wrong pairs reuse the real rows' (augmented)
+    code, as AttnGAN reuses real_features.  `batch_pairs = False`, or a discriminator without `supports_batch_groups`, runs the
+    trunk and each head separately per batch -- real, fake, then the wrong pairs through the joint head -- with the same results.
+    `observe` is handed the UNCONDITIONAL real scores, so the overfitting signal of adaptive augmentation keeps its meaning."""
+
+    batch_pairs = True
+
+    def get_loss(self, discriminator: Module, fake_images: Tensor, real_images: Tensor, sent: Tensor, augment=None, observe=None) -> Tensor:
+        _conditional(discriminator, "ConditionalDiscLoss")
+        b = real_images.shape[0]
+        if (self.batch_pairs and getattr(discriminator, "supports_batch_groups", False) and discriminator.training
+                and fake_images.is_cuda and fake_images.shape == real_images.shape):
+            both = torch.cat([real_images, fake_images], dim=0) if augment is None else augment((real_images, fake_images))
+            with HF.bn_groups(2):
+                h = discriminator.features(both)
+            pu = discriminator.uncond(h)
+            if observe is not None:
+                observe(pu.detach()[:b])
+            return HF.cond_disc_loss(pu, discriminator.cond(h, sent, wrong=True))
+        if augment is not None:
+            both = augment((real_images, fake_images))
+            real_images, fake_images = both[:b], both[b:]
+        # separate passes in the paired path's BatchNorm call order: trunk real, fake; joint head real, fake, wrong
+        h_real = discriminator.features(real_images)
+        pu_real = discriminator.uncond(h_real)
+        if observe is not None:
+            observe(pu_real.detach())
+        h_fake = discriminator.features(fake_images)
+        pu_fake = discriminator.uncond(h_fake)
+        pc = [discriminator.cond(h_real, sent), discriminator.cond(h_fake, sent), discriminator.cond(h_real, sent.roll(-1, 0))]
+        return HF.cond_disc_loss(torch.cat([pu_real, pu_fake]), torch.cat(pc))
+
+
 class StandardDiscLoss(DiscLoss):
     """BCE variant (disc_loss.py:26-47); not used by train.py:74-75.  The discriminator passes run on the HIP kernels, the
     cross-entropy over [B] probabilities is a stock ATen elementwise op."""

@@ -26,6 +26,21 @@ class NonSaturatingGenLoss(GenLoss):
         return HF.ns_gen_loss(discriminator(fake_images))
 
 
+class ConditionalGenLoss(GenLoss):
+    """-mean(log(Du(G(z)) + 1e-8)) - mean(log(Dc(G(z), s) + 1e-8)): the generator's adversarial term against a text-conditional
+    discriminator (AttnGAN's generator_loss: errG = cond_errG + uncond_errG, here in the non-saturating log form).  One trunk pass;
+    both heads read its 4x4 code."""
+
+    def get_loss(self, discriminator: Module, fake_images: Tensor, sent: Tensor, augment=None) -> Tensor:
+        if getattr(discriminator, "COND_DNET", None) is None:
+            raise ValueError(f"ConditionalGenLoss: {type(discriminator).__name__} has no COND_DNET; build it with "
+                             f"cond_dim=<sentence-embedding width>")
+        if augment is not None:
+            fake_images = augment(fake_images)
+        h = discriminator.features(fake_images)
+        return HF.ns_gen_loss(discriminator.uncond(h)) + HF.ns_gen_loss(discriminator.cond(h, sent))
+
+
 class StandardGenLoss(GenLoss):
     """BCE(D(G(z)), 1)  (gen_loss.py:21-35).  Not used by train.py:74; the discriminator runs on the HIP kernels, the
     cross-entropy over its [B] probabilities is a stock ATen elementwise op."""

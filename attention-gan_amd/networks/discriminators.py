@@ -1,11 +1,15 @@
-"""Unconditional sigmoid discriminators with the reference's interface (networks/discriminators.py:10-70)."""
+"""Sigmoid discriminators with the reference's interface (networks/discriminators.py:10-70): unconditional as the reference's, and
+with `cond_dim` AttnGAN's joint sentence-image head (COND_DNET) next to the unconditional one."""
 from __future__ import annotations
 
+from typing import Optional
+
+import torch
 from torch import Tensor, nn
 
 from ..backend import functional as HF
 from ..backend import lib as L
-from ..utilities.layers import HipConv2d, Layers
+from ..utilities.layers import HipBatchNorm2d, HipConv2d, HipLinear, Layers
 
 
 class _LogitHead(nn.Module):
@@ -26,39 +30,164 @@ class _LogitHead(nn.Module):
         return HF.activation(logit, L.ACT_SIGMOID)
 
 
+class _Held:
+    """mixin of a parameter holder whose owner writes and reads its state_dict entry (_JointConv): no entry of its own"""
+
+    def _save_to_state_dict(self, destination, prefix, keep_vars):
+        pass
+
+    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
+        pass
+
+
+class _HeldConv2d(_Held, HipConv2d):
+    pass
+
+
+class _HeldLinear(_Held, HipLinear):
+    pass
+
+
+class _JointConv(nn.Module):
+    """AttnGAN's jointConv = Block3x3_leakRelu(8df + nef, 8df) on cat(h, rep(s)), stored split: the sentence channels are constant over
+    the 4x4 map, so conv3x3(cat(h, rep(s)), W) = conv3x3(h, W[:, :8df]) + the border-aware tap sums of P = s . W[:, 8df:]
+    (backend/functional.py: cond_join).  `image` holds W[:, :8df]; `sentence` holds W[:, 8df:] arranged [c][t][e], so that
+    sentence(s).view(B, 8df, 9) is P.  Both are ordinary parameters (flat optimiser, packed weight forms).  state_dict shows
+    AttnGAN's keys: '0.weight' [8df, 8df + nef, 3, 3] -- the concatenation, assembled on save and split on load -- and '1.*', the
+    BatchNorm."""
+
+    def __init__(self, c: int, nef: int):
+        super().__init__()
+        self.c, self.nef = c, nef
+        self.image = _HeldConv2d(c, c, 3, 1, 1, False)
+        self.sentence = _HeldLinear(nef, 9 * c, bias=False)
+        self.add_module("1", HipBatchNorm2d(c))
+        # ONE default init of the joint conv (the fan-in of AttnGAN's layer: (8df + nef) * 9), then split; the two holders' own draws above
+        # are overwritten.  (COND_DNET is built after every other child, so the draws shift nothing that existed before.)
+        joint = nn.Conv2d(c + nef, c, kernel_size=3, stride=1, padding=1, bias=False)
+        self._split_(joint.weight.detach())
+
+    @torch.no_grad()
+    def _split_(self, w: Tensor) -> None:
+        c, nef = self.c, self.nef
+        self.image.weight.copy_(w[:, :c])
+        self.sentence.weight.copy_(w[:, c:].reshape(c, nef, 9).permute(0, 2, 1).reshape(9 * c, nef))
+
+    def joint_weight(self) -> Tensor:
+        """W [8df, 8df + nef, 3, 3] of AttnGAN's layout from the two stored parts (differentiable: the test oracles use it)"""
+        c, nef = self.c, self.nef
+        ws = self.sentence.weight.view(c, 9, nef).permute(0, 2, 1).reshape(c, nef, 3, 3)
+        return torch.cat([self.image.weight, ws], dim=1)
+
+    # the two stored parts appear as the single concatenated key (they write and read no entries of their own: _Held); the BatchNorm
+    # child keeps its entries
+    def _save_to_state_dict(self, destination, prefix, keep_vars):
+        w = self.joint_weight()
+        destination[prefix + "0.weight"] = w if keep_vars else w.detach()
+
+    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
+        key = prefix + "0.weight"
+        if key not in state_dict:
+            if strict:
+                missing_keys.append(key)
+            return
+        w = state_dict[key]
+        want = (self.c, self.c + self.nef, 3, 3)
+        if tuple(w.shape) != want:
+            error_msgs.append(f"size mismatch for {key}: copying a param with shape {tuple(w.shape)} from checkpoint, the shape in "
+                              f"current model is {want}.")
+            return
+        self._split_(w.to(self.image.weight.dtype))
+
+
+class _CondDNet(nn.Module):
+    """AttnGAN's D_GET_LOGITS(bcondition=True): jointConv on the code and the sentence, then the logit head (keys jointConv.{0,1}.*,
+    outlogits.0.*)."""
+
+    def __init__(self, c: int, nef: int):
+        super().__init__()
+        self.jointConv = _JointConv(c, nef)
+        self.outlogits = _LogitHead(c)
+
+
 class _Disc(nn.Module):
     # every BatchNorm inside is a HipBatchNorm2d and nothing else couples samples of a batch, so a [real; fake] batch may go
     # through in one pass under functional.bn_groups(2) (losses/disc_loss.py)
     supports_batch_groups = True
 
+    def _add_cond(self, df_dim: int, cond_dim: Optional[int]) -> None:
+        """called LAST by the constructors: the existing children keep their initial values under a given seed"""
+        self.cond_dim = cond_dim
+        if cond_dim is None:
+            self.COND_DNET = None          # (a plain attribute: no module, no state_dict key, no random draw)
+            return
+        if int(cond_dim) < 1:
+            raise ValueError(f"cond_dim must be a positive sentence-embedding width or None, got {cond_dim}")
+        self.COND_DNET = _CondDNet(df_dim * 8, int(cond_dim))
+
     def _tail(self, x: Tensor) -> Tensor:
         return self.outlogits(x).view(-1)
 
+    def forward(self, X: Tensor) -> Tensor:
+        return self._tail(self.features(X))
+
+    def uncond(self, h: Tensor) -> Tensor:
+        """the unconditional scores from a 4x4 code (forward(X) = uncond(features(X)))"""
+        return self._tail(h)
+
+    def cond(self, h: Tensor, sent: Tensor, wrong: bool = False) -> Tensor:
+        """The conditional scores [(k + wrong) * B] from a code h [k * B, 8df, 4, 4] -- k consecutive groups of B rows, row n showing
+        caption n mod B -- and the sentence embeddings sent [B, nef]: AttnGAN's COND_DNET(h, c_code).  With `wrong`, B more scores pair
+        the FIRST group's codes (the real images' in a discriminator update) with the next sample's caption, cyclically: AttnGAN's
+        mismatched pairs, here B of them (AttnGAN has B - 1 and drops the last) so that the groups are equal, which bn_groups takes.
+
+        Image conv once over all k * B rows, linear once over the B captions, cond_join, then jointConv.1 as fused BatchNorm +
+        LeakyReLU under bn_groups(k + wrong): in train mode the BatchNorm behaves as k + wrong consecutive calls in the order of the
+        groups (real, fake, wrong), each with its own statistics and its own running-statistic update."""
+        net = self.COND_DNET
+        if net is None:
+            raise ValueError(f"{type(self).__name__} was built without cond_dim: it has no COND_DNET")
+        jc = net.jointConv
+        if sent.dim() != 2 or sent.shape[1] != jc.nef:
+            raise ValueError(f"cond: sentence embeddings must be [B, {jc.nef}], got {tuple(sent.shape)}")
+        B = sent.shape[0]
+        if h.dim() != 4 or tuple(h.shape[1:]) != (jc.c, 4, 4) or h.shape[0] < B or h.shape[0] % B:
+            raise ValueError(f"cond: the code must be [k * {B}, {jc.c}, 4, 4], got {tuple(h.shape)}")
+        if wrong and B < 2:
+            raise ValueError("cond: the mismatched pairs (wrong=True) need at least 2 captions")
+        k = h.shape[0] // B
+        y = HF.cond_join(jc.image(h), jc.sentence(sent).view(B, jc.c, 9), wrong)
+        with HF.bn_groups(k + int(bool(wrong))):
+            y = getattr(jc, "1").fused(y, L.ACT_LRELU)
+        return net.outlogits(y).view(-1)
+
 
 class Disc64(_Disc):
-    def __init__(self, df_dim: int):
+    def __init__(self, df_dim: int, cond_dim: Optional[int] = None):
         super().__init__()
         self.img_code_s16 = Layers.encode_image_by_16times(df_dim)
         self.outlogits = _LogitHead(df_dim * 8)
+        self._add_cond(df_dim, cond_dim)
 
-    def forward(self, X: Tensor) -> Tensor:
-        return self._tail(self.img_code_s16(X))
+    def features(self, X: Tensor) -> Tensor:
+        return self.img_code_s16(X)
 
 
 class Disc128(_Disc):
-    def __init__(self, df_dim: int):
+    def __init__(self, df_dim: int, cond_dim: Optional[int] = None):
         super().__init__()
         self.img_code_s16 = Layers.encode_image_by_16times(df_dim)
         self.img_code_s32 = Layers.downBlock(df_dim * 8, df_dim * 16)
         self.img_code_s32_1 = Layers.Block3x3_leakRelu(df_dim * 16, df_dim * 8)
         self.outlogits = _LogitHead(df_dim * 8)
+        self._add_cond(df_dim, cond_dim)
 
-    def forward(self, X: Tensor) -> Tensor:
-        return self._tail(self.img_code_s32_1(self.img_code_s32(self.img_code_s16(X))))
+    def features(self, X: Tensor) -> Tensor:
+        return self.img_code_s32_1(self.img_code_s32(self.img_code_s16(X)))
 
 
 class Disc256(_Disc):
-    def __init__(self, df_dim: int):
+    def __init__(self, df_dim: int, cond_dim: Optional[int] = None):
         super().__init__()
         self.img_code_s16 = Layers.encode_image_by_16times(df_dim)
         self.img_code_s32 = Layers.downBlock(df_dim * 8, df_dim * 16)
@@ -66,7 +195,8 @@ class Disc256(_Disc):
         self.img_code_s64_1 = Layers.Block3x3_leakRelu(df_dim * 32, df_dim * 16)
         self.img_code_s64_2 = Layers.Block3x3_leakRelu(df_dim * 16, df_dim * 8)
         self.outlogits = _LogitHead(df_dim * 8)
+        self._add_cond(df_dim, cond_dim)
 
-    def forward(self, X: Tensor) -> Tensor:
+    def features(self, X: Tensor) -> Tensor:
         x = self.img_code_s64(self.img_code_s32(self.img_code_s16(X)))
-        return self._tail(self.img_code_s64_2(self.img_code_s64_1(x)))
+        return self.img_code_s64_2(self.img_code_s64_1(x))

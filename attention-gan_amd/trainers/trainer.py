@@ -17,8 +17,8 @@ from torch.nn import Module
 from ..augment import GEO_UNIFORMS, AdaController, parse_geometry, parse_policy
 from ..backend import functional as HF
 from ..dataparallel import GradBuckets, any_rank, averaged_buffers, broadcast_module_, rank_of, world_size
-from ..losses.disc_loss import NonSaturatingDiscLoss
-from ..losses.gen_loss import NonSaturatingGenLoss
+from ..losses.disc_loss import ConditionalDiscLoss, NonSaturatingDiscLoss
+from ..losses.gen_loss import ConditionalGenLoss, NonSaturatingGenLoss
 from ..losses.KL_loss import KL_loss
 from ..losses.sentence_loss import SentenceLoss
 from ..losses.words_loss import WordsLoss
@@ -135,8 +135,8 @@ class ModelTrainer:
 # what the generator's forward leaves for the rest of the step
 # (aug_u: the augmentation's uniforms [3 * len(Ds), B, 8], None without a policy; aug_q: the per-stage gate uniforms
 # [3 * len(Ds), B, 4], None unless the augmentation has a probability; aug_m: the geometric stages' matrices [3 * len(Ds), B, 6],
-# None without `geometry`)
-_Forward = collections.namedtuple("_Forward", "labels mask fakes attn mu logvar aug_u aug_q aug_m", defaults=(None,))
+# None without `geometry`; sent: the sentence embeddings, detached, for the conditional discriminator heads, None unless `conditional`)
+_Forward = collections.namedtuple("_Forward", "labels mask fakes attn mu logvar aug_u aug_q aug_m sent", defaults=(None, None))
 
 
 def _forked(streams, i: int, main):
@@ -189,6 +189,15 @@ class GanTrainStep(ModelTrainer):
     geometric stage is gated per sample by slots 8..12 of its uniforms against the same device-resident p.  The image encoder,
     generate_images and evaluate never see the warp; the stages are configuration, not checkpoint content.  With None (default)
     nothing is drawn and no kernel runs.
+
+    `conditional`: text-conditional discriminators, AttnGAN's own: every discriminator must carry COND_DNET (built with cond_dim =
+    the sentence embedding's width; ValueError otherwise).  The discriminator updates use losses.disc_loss.ConditionalDiscLoss --
+    unconditional and joint sentence-image scores of the real and the fake batch plus the joint scores of the B mismatched pairs
+    (real image b, caption (b + 1) mod B; AttnGAN takes B - 1), which reuse the real batch's augmented code -- and the generator update
+    losses.gen_loss.ConditionalGenLoss, both on the step's `sent_embs`, detached (the text encoder is frozen).  Eager step, capture()
+    and capture_segments() alike; `augment`, `geometry`, `augment_p` / `ada_target` (fed the UNCONDITIONAL real scores), `ema` and
+    torch.distributed work unchanged, and checkpoints need nothing new: the head's parameters live in the discriminators' state_dict
+    (AttnGAN's keys) and flat optimisers.  With False (default) no module, launch, random draw or result key is added.
     """
 
     def __init__(self, generator: Module, discriminators: Sequence[Module], image_encoder: Optional[Callable] = None,
@@ -196,8 +205,12 @@ class GanTrainStep(ModelTrainer):
                  wlambda: float = 5.0, slambda: float = 5.0, bucket_bytes: int = 64 << 20, group=None, seed: int = 0,
                  g_bucket_bytes: Optional[int] = None, augment: Optional[str] = None, ema: Optional[float] = None,
                  ema_warmup: bool = True, augment_p: Optional[float] = None, ada_target: Optional[float] = None, ada_interval: int = 4,
-                 ada_kimg: float = 500.0, ada_p_max: float = 1.0, geometry: Optional[str] = None):
+                 ada_kimg: float = 500.0, ada_p_max: float = 1.0, geometry: Optional[str] = None, conditional: bool = False):
         super().__init__()
+        if conditional and any(getattr(d, "COND_DNET", None) is None for d in discriminators):
+            raise ValueError("GanTrainStep: conditional=True needs every discriminator built with cond_dim=<sentence-embedding width> "
+                             "(networks.discriminators: COND_DNET)")
+        self.conditional = bool(conditional)
         if (augment_p is not None or ada_target is not None) and not (parse_policy(augment) or parse_geometry(geometry)):
             raise ValueError("GanTrainStep: augment_p and ada_target need a non-empty augment policy")
         if ada_target is not None and world_size(group) > 1:
@@ -240,7 +253,8 @@ class GanTrainStep(ModelTrainer):
         dev = next(self.G.parameters()).device
         self.words_loss = WordsLoss(dev, gamma1, gamma2, gamma3, wlambda)
         self.sent_loss = SentenceLoss(dev, gamma3, slambda)
-        self.disc_loss, self.gen_loss = NonSaturatingDiscLoss(), NonSaturatingGenLoss()
+        self.disc_loss, self.gen_loss = ((ConditionalDiscLoss(), ConditionalGenLoss()) if self.conditional else
+                                         (NonSaturatingDiscLoss(), NonSaturatingGenLoss()))
         self.g_losses: List = []
         self.d_losses: List = []
         self.damsm_losses: List = []
@@ -332,8 +346,9 @@ class GanTrainStep(ModelTrainer):
             aug_q = torch.rand(3 * len(self.Ds), b, 4, dtype=torch.float32, device=word_embs.device, generator=self.rng)
         elif tuple(aug_q.shape) != (3 * len(self.Ds), b, 4):
             raise ValueError(f"aug_q must be [{3 * len(self.Ds)}, {b}, 4], got {tuple(aug_q.shape)}")
+        sent = sent_embs.detach() if self.conditional else None      # (the text encoder is frozen: no gradient leaves the heads)
         if not self.geometry:
-            return _Forward(labels, mask, *self.G(noise, sent_embs, word_embs, mask, eps), aug_u, aug_q)
+            return _Forward(labels, mask, *self.G(noise, sent_embs, word_embs, mask, eps), aug_u, aug_q, None, sent)
         slots = 3 * len(self.Ds)
         if aug_g is None:                                   # the geometric stages' uniforms: the last draw of the step
             aug_g = torch.rand(slots, b, GEO_UNIFORMS, dtype=torch.float32, device=word_embs.device, generator=self.rng)
@@ -341,7 +356,7 @@ class GanTrainStep(ModelTrainer):
             raise ValueError(f"aug_g must be [{slots}, {b}, {GEO_UNIFORMS}], got {tuple(aug_g.shape)}")
         # every slot's matrices by ONE launch: they do not depend on the resolution, so the discriminators' sizes share them
         aug_m = HF.geometry_matrices(aug_g.reshape(-1, GEO_UNIFORMS), self.geometry, None if self.ada is None else self.ada.p)
-        return _Forward(labels, mask, *self.G(noise, sent_embs, word_embs, mask, eps), aug_u, aug_q, aug_m.view(slots, b, 6))
+        return _Forward(labels, mask, *self.G(noise, sent_embs, word_embs, mask, eps), aug_u, aug_q, aug_m.view(slots, b, 6), sent)
 
     def _augmenter(self, fw: "_Forward", first: int, count: int) -> Optional[Callable]:
         """What the losses apply to the images before D: slots first .. first + count - 1 of the step's uniforms, one per tensor;
@@ -369,7 +384,10 @@ class GanTrainStep(ModelTrainer):
         if arm:
             self.d_buckets[i].arm()
         aug = self._augmenter(fw, 3 * i, 2)                 # (None without a policy: the call is then the one it always was)
-        if self.ada is not None and self.ada.adaptive:      # the real scores' signs go to discriminator i's slot, on this stream
+        if self.conditional:                                # (the unconditional real scores are what the controller is handed)
+            observe = (lambda score: self._observe(i, score)) if self.ada is not None and self.ada.adaptive else None
+            loss = self.disc_loss.get_loss(self.Ds[i], fw.fakes[i].detach(), real_imgs[i], fw.sent, augment=aug, observe=observe)
+        elif self.ada is not None and self.ada.adaptive:    # the real scores' signs go to discriminator i's slot, on this stream
             loss = self.disc_loss.get_loss(self.Ds[i], fw.fakes[i].detach(), real_imgs[i], augment=aug,
                                            observe=lambda score: self._observe(i, score))
         else:
@@ -400,7 +418,10 @@ class GanTrainStep(ModelTrainer):
             for i, d in enumerate(self.Ds):
                 with _forked(streams, i, main):
                     aug = self._augmenter(fw, 3 * i + 2, 1)
-                    gl = self.gen_loss.get_loss(d, fw.fakes[i]) if aug is None else self.gen_loss.get_loss(d, fw.fakes[i], augment=aug)
+                    if self.conditional:
+                        gl = self.gen_loss.get_loss(d, fw.fakes[i], fw.sent, augment=aug)
+                    else:
+                        gl = self.gen_loss.get_loss(d, fw.fakes[i]) if aug is None else self.gen_loss.get_loss(d, fw.fakes[i], augment=aug)
                     terms.append(gl)
                     out[f"g_loss{i}"] = gl.detach()
                     if i == len(self.Ds) - 1 and self.image_encoder is not None:

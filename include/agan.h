@@ -348,6 +348,32 @@ int agan_reparam_fwd(const float* mu, const float* logvar, const float* eps, flo
 int agan_reparam_bwd(const float* logvar, const float* eps, const float* dc, float* dmu, float* dlogvar, int n, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The text-conditional discriminator head (csrc/cond_join.hip, csrc/heads.hip; backend/functional.py: cond_join, cond_disc_loss;
+ * networks/discriminators.py: COND_DNET).  AttnGAN's jointConv is conv3x3 over cat(h, rep(s)) on the 4x4 code; the sentence channels
+ * are constant over the map, so
+ *     conv3x3(cat(h, rep(s)), W)[n, c, i, j] = conv3x3(h, W[:, :8df])[n, c, i, j] + sum_{t valid at (i, j)} P[n, c, t]
+ *     P[n, c, t] = sum_e s[n, e] * W[c, 8df + e, t]
+ * with t = 3 (di + 1) + (dj + 1) the tap that reads input (i + di, j + dj), valid iff 0 <= i + di < 4 and 0 <= j + dj < 4.
+ * Write S(p)[c, i, j] = sum_{t valid at (i, j)} p[c, t].
+ *   agan_cond_join_fwd: yi [k * B, C, 4, 4] is the image term, k consecutive groups of B rows, row n carrying caption n mod B;
+ *     p [B, C, 9]; y [(k + wrong) * B, C, 4, 4].  Rows n < k * B: y[n] = yi[n] + S(p[n mod B]), the taps added in ascending t starting
+ *     from yi.  With `wrong`, rows k * B + b (b < B): y = yi[b] + S(p[(b + 1) mod B]) -- the FIRST group's images with the next
+ *     sample's caption, cyclically.
+ *   agan_cond_join_bwd: dyi[n] = dy[n], plus dy[k * B + n] when `wrong` and n < B.  dp[b, c, t] = the sum over the rows that used
+ *     caption b -- row b of group 0, then of group 1, ..., then wrong row (b - 1 + B) mod B -- and inside each row over the positions
+ *     (i, j) where t is valid, in ascending (i, j): one running sum per tap.  Either output may be NULL (both: nothing is launched).
+ * One lane owns one (row, channel); no atomics, one summation order: two runs give the same bits.  Null pointers, B < 1, k < 1,
+ * C < 1, (k + 1) * B * C > 2^30, `wrong` with B < 2 and yi / y / dy / dyi off a 16-byte boundary are AGAN_EINVAL before any launch.
+ *   agan_cond_disc_loss: pu [2B] = the unconditional scores of [real; fake], pc [3B] = the conditional scores of [real; fake; wrong]:
+ *     loss = (m(-log(pu_r+1e-8)) + m(-log(pc_r+1e-8))) / 2 + (m(-log(1-pu_f+1e-8)) + m(-log(1-pc_f+1e-8)) + m(-log(1-pc_w+1e-8))) / 3
+ *     with m the mean over B: AttnGAN's weights on the non-saturating terms above.  ONE launch writes the loss and both gradients
+ *     (dpu [2B], dpc [3B]; either may be NULL).
+ * ---------------------------------------------------------------------------------------------- */
+int agan_cond_join_fwd(const float* yi, const float* p, float* y, int B, int k, int C, int wrong, void* stream);
+int agan_cond_join_bwd(const float* dy, float* dyi, float* dp, int B, int k, int C, int wrong, void* stream);
+int agan_cond_disc_loss(const float* pu, const float* pc, float* loss, float* dpu, float* dpc, int B, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Fused Adam over one flat parameter buffer (torch.optim.Adam as configured at train.py:78-80:
  * no weight decay, no amsgrad).  grad_scale multiplies the gradient first (1/world_size after a sum all-reduce).
  * step_state: 16 bytes of device memory owned by the optimiser ([0] = int32 step count, advanced by the call; [2],[3] = the
