@@ -2445,3 +2445,42 @@ def poly_kernel_sum(x: Tensor, y: Tensor, exclude_diagonal: bool = False) -> Ten
     ws, wsp = _ws(nbytes, x)
     _kmeans_call("agan_poly_kernel_sum", _p(x), _p(y), n, m, D, 1 if exclude_diagonal else 0, _p(out), wsp, nbytes, _stream())
     return out
+
+
+# --------------------------------------------------------------------------------------------------------------
+# the Inception Score's reduction (evaluation.py: inception_score; include/agan.h: agan_inception_score)
+# --------------------------------------------------------------------------------------------------------------
+def inception_split_scores(logits: Tensor, splits: int = 10) -> Tensor:
+    """-> float64 [splits, 3] on the device of logits [N, C] float32: per split s of the rows [s N // splits, (s + 1) N // splits) the
+    Inception Score exp(Hm - Hc), the label entropy Hm of the split's mean class distribution and the mean conditional entropy Hc of
+    its rows (include/agan.h states the arithmetic).  1 <= C <= 4096, N * C < 2^31, 1 <= splits <= min(N, 1024).  A row that holds
+    +inf or a NaN, or nothing but -inf, makes its own split's three numbers NaN.  Device tensors run on the library; a CPU tensor takes
+    the float64 restatement below.  No autograd: a measurement."""
+    if logits.dim() != 2:
+        raise ValueError(f"inception_split_scores: expected logits [N, C], got {tuple(logits.shape)}")
+    if logits.dtype != torch.float32:
+        raise ValueError(f"inception_split_scores: logits must be float32, got {logits.dtype}")
+    logits = logits.detach().contiguous()
+    N, C = logits.shape
+    splits = int(splits)
+    if not _rows_in_domain(N, C) or not 1 <= splits <= min(N, 1024):
+        raise ValueError(f"inception_split_scores: N {N}, C {C}, splits {splits} outside N >= 1, 1 <= C <= 4096, N * C < 2^31, "
+                         f"1 <= splits <= min(N, 1024)")
+    if not logits.is_cuda:
+        out = torch.empty(splits, 3, dtype=torch.float64)
+        zero = torch.zeros((), dtype=torch.float64)
+        for s in range(splits):
+            x = logits[s * N // splits:(s + 1) * N // splits].double()
+            m = x.max(1, keepdim=True)[0]
+            logp = x - (m + (x - m).exp().sum(1, keepdim=True).log())
+            p = logp.exp()
+            hc = -torch.where(p == 0, zero, p * logp).sum(1).mean()
+            q = p.mean(0)
+            hm = -torch.where(q == 0, zero, q * q.log()).sum()
+            out[s, 0], out[s, 1], out[s, 2] = (hm - hc).exp(), hm, hc
+        return out
+    out = torch.empty(splits, 3, dtype=torch.float64, device=logits.device)
+    nbytes = L.load().agan_inception_score_ws_bytes(N, C, splits)
+    ws, wsp = _ws(nbytes, logits)
+    _kmeans_call("agan_inception_score", _p(logits), N, C, splits, _p(out), wsp, nbytes, _stream())
+    return out

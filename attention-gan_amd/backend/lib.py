@@ -184,6 +184,8 @@ _SIGNATURES = {
     "agan_manifold_scan": (c_int, [_P, _P, _P] + [c_int] * 3 + [_P, _P, _P, _P, c_size_t, _P]),
     "agan_poly_kernel_sum_ws_bytes": (c_size_t, [c_int] * 3),
     "agan_poly_kernel_sum": (c_int, [_P, _P] + [c_int] * 4 + [_P, _P, c_size_t, _P]),
+    "agan_inception_score_ws_bytes": (c_size_t, [c_int] * 3),
+    "agan_inception_score": (c_int, [_P, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

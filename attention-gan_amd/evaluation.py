@@ -1,5 +1,5 @@
-"""Evaluation of a generator: R-precision and the Frechet distance, the two numbers AttnGAN-style work is judged by, and three
-companions that look at the image distribution where the Frechet distance is blind or biased.
+"""Evaluation of a generator: R-precision, the Frechet distance and the Inception Score, the numbers AttnGAN-style work is judged by,
+and three companions that look at the image distribution where the Frechet distance is blind or biased.
 
   * R-precision: does the DAMSM image code of a generated image retrieve its own caption's sentence embedding among R - 1 mismatched
     ones (cosine similarity, losses/sentence_loss.py without gamma3)?  `r_precision` draws the mismatched captions from OTHER class ids
@@ -15,12 +15,17 @@ companions that look at the image distribution where the Frechet distance is bli
   * The Kernel Inception Distance (Binkowski et al. 2018), `kernel_distance`: an unbiased estimate at any sample count, for the
     "folder of images" case with fewer samples than feature dimensions, where most of the Frechet distance's spectrum is noise
     (functional.poly_kernel_sum).
+  * The Inception Score (Salimans et al. 2016), `inception_score`: exp of the mean KL divergence between an image's class distribution
+    under a classifier head on the trunk (CNNEncoder(num_classes=...).logits) and the mean distribution of its split, over 10
+    contiguous splits of the images, reported as mean and standard deviation with the label entropy (diversity) and the conditional
+    entropy (sharpness) it is made of.  functional.inception_split_scores reads the fp32 logits twice and reduces in float64;
+    `inception_score_reference` states the protocol in plain torch.
 
 The trunk's weights are whatever the user loaded (CNNEncoder.load_trunk_state_dict); nothing is downloaded.  A Frechet distance over a
 randomly initialised or self-trained trunk orders the checkpoints of one run; it is NOT comparable with published FID values, which
-presuppose the ImageNet-trained Inception-v3.  The same holds for precision, recall, density, coverage and the kernel distance.
-The Inception Score is out of scope (the trunk has no classifier head), and so is data-parallel evaluation beyond
-`FeatureMoments.merge`.
+presuppose the ImageNet-trained Inception-v3.  The same holds for precision, recall, density, coverage and the kernel distance, and
+for the Inception Score, which in addition presupposes a head trained on the image domain (ImageNet's 1000 classes, or the 200-class
+CUB fine-tune of AttnGAN evaluations).  Data-parallel evaluation beyond `FeatureMoments.merge` is out of scope.
 """
 from __future__ import annotations
 
@@ -182,6 +187,59 @@ def kernel_distance(real, fake, subsets: int = 100, subset_size: int = 1000, see
     return {"kid": float(est.mean()), "kid_std": float(est.std(unbiased=False))}
 
 
+def _splits_arg(splits, rows: Optional[int], what: str) -> int:
+    """an integer number of splits in 1..min(rows, 1024) (1..1024 while the row count is not known yet), or ValueError"""
+    most = 1024 if rows is None else min(rows, 1024)
+    if isinstance(splits, bool) or not isinstance(splits, (int, np.integer)) or not 1 <= int(splits) <= most:
+        raise ValueError(f"{what}: {splits!r} splits" + ("" if rows is None else f" of {rows} rows") +
+                         " (an integer, 1 <= splits <= min(rows, 1024): no split may be empty)")
+    return int(splits)
+
+
+def _logit_rows(logits: Tensor, splits, what: str) -> int:
+    if not isinstance(logits, Tensor) or logits.dim() != 2 or logits.shape[1] < 1:
+        raise ValueError(f"{what}: expected logits [N, C], got {tuple(logits.shape) if isinstance(logits, Tensor) else type(logits).__name__}")
+    return _splits_arg(splits, logits.shape[0], what)
+
+
+def inception_score_reference(logits: Tensor, splits: int = 10) -> Tensor:
+    """-> float64 [splits, 3] on the device of logits [N, C]: (IS_s, Hm_s, Hc_s) of split s = rows [s N // splits, (s + 1) N // splits),
+    the contiguous chunks of the published protocol, in plain float64 torch:
+        lse_k = m_k + log sum_y exp(l[k][y] - m_k) with m_k the row's maximum;  logp = l[k][y] - lse_k;  p = exp(logp)
+        Hc_s = -mean_k sum_y p logp;  q_s = mean_k p[k];  Hm_s = -sum_y q log q        (a term with p == 0 or q == 0 counts as 0)
+        IS_s = exp(Hm_s - Hc_s) = exp(mean_k KL(p(.|x_k) || q_s)).
+    logp comes from l - lse and never from log(p), so an underflowed or masked (-inf) class gives 0 and not NaN; a row that holds +inf
+    or a NaN, or nothing but -inf, makes its own split NaN.  The yardstick of functional.inception_split_scores."""
+    splits = _logit_rows(logits, splits, "inception_score_reference")
+    l = logits.detach().double()
+    N = l.shape[0]
+    zero = torch.zeros((), dtype=torch.float64, device=l.device)
+    rows = []
+    for s in range(splits):
+        x = l[s * N // splits:(s + 1) * N // splits]
+        m = x.max(1, keepdim=True)[0]
+        lse = m + (x - m).exp().sum(1, keepdim=True).log()
+        logp = x - lse
+        p = logp.exp()
+        hc = -torch.where(p == 0, zero, p * logp).sum(1).mean()
+        q = p.mean(0)
+        hm = -torch.where(q == 0, zero, q * q.log()).sum()
+        rows.append(torch.stack([(hm - hc).exp(), hm, hc]))
+    return torch.stack(rows)
+
+
+def inception_score(logits: Tensor, splits: int = 10) -> Dict:
+    """-> {"inception_score": mean of the splits' scores, "inception_score_std": their standard deviation (ddof = 0, the published
+    np.std), "inception_score_splits": the scores, "label_entropy", "conditional_entropy": the means of Hm and Hc over the splits}
+    of classifier logits [N, C] (any float dtype; reduced from float32), by functional.inception_split_scores and one read-back of
+    [splits, 3] doubles.  IS = exp(label entropy - conditional entropy) per split: a sharp classifier on diverse images scores high."""
+    splits = _logit_rows(logits, splits, "inception_score")
+    t = AF.inception_split_scores(logits.detach().float(), splits).cpu()      # the one synchronisation
+    return {"inception_score": float(t[:, 0].mean()), "inception_score_std": float(t[:, 0].std(unbiased=False)),
+            "inception_score_splits": [float(v) for v in t[:, 0]], "label_entropy": float(t[:, 1].mean()),
+            "conditional_entropy": float(t[:, 2].mean())}
+
+
 def frechet_distance(mu1: Tensor, cov1: Tensor, mu2: Tensor, cov2: Tensor) -> float:
     """|mu1 - mu2|^2 + tr S1 + tr S2 - 2 tr (S1 S2)^(1/2), in float64 on the host.  With S1 = V L V^T the last trace is the sum of the
     square roots of the eigenvalues of the symmetric matrix L^(1/2) V^T S2 V L^(1/2) (similar to S1 S2), each clamped at 0: two
@@ -327,7 +385,7 @@ class Evaluator:
     @torch.no_grad()
     def evaluate(self, batches: Iterable, real: FeatureMoments, n_samples: int, R: int = 100, seed: int = 0,
                  batch_size: Optional[int] = None, folds: int = 10, source: str = "fake", real_features: Optional[FeatureBank] = None,
-                 k: int = 3, kid_subsets: int = 100, kid_subset_size: int = 1000) -> Dict:
+                 k: int = 3, kid_subsets: int = 100, kid_subset_size: int = 1000, inception_splits: Optional[int] = None) -> Dict:
         """Generates up to n_samples images from the batches' captions (noise from a device generator seeded with `seed`), and returns
         {"r_precision", "r_precision_folds", "rank", "fid", "n"}.  A batch whose shortest caption has fewer than 2 words, or with fewer
         rows than batch_size (default: the first batch's), is skipped -- the reference's batch guard (train.py:112).
@@ -335,11 +393,20 @@ class Evaluator:
         pair.  Deterministic for a seed.
         With real_features (a FeatureBank of real images, e.g. from real_statistics) the generated pooled vectors are kept too and the
         result gains "precision", "recall", "density", "coverage" (manifold_metrics with k) and "kid", "kid_std" (kernel_distance
-        with kid_subsets, kid_subset_size and seed).  Without it nothing more is stored or launched."""
+        with kid_subsets, kid_subset_size and seed).  Without it nothing more is stored or launched.
+        With inception_splits (an integer; the published protocol uses 10) the image encoder must offer `logits(pooled)`
+        (CNNEncoder(num_classes=...)): the kept rows' class logits are collected too and the result gains "inception_score",
+        "inception_score_std", "inception_score_splits", "label_entropy" and "conditional_entropy" (inception_score); source="real"
+        gives the real images' score.  More splits than kept rows is a ValueError.  With None nothing more is stored or launched."""
         if source not in ("fake", "real"):
             raise ValueError(f"Evaluator.evaluate: source must be 'fake' or 'real', got {source!r}")
         if real_features is not None and not isinstance(real_features, FeatureBank):
             raise ValueError(f"Evaluator.evaluate: real_features must be a FeatureBank, got {type(real_features).__name__}")
+        if inception_splits is not None:
+            _splits_arg(inception_splits, None, "Evaluator.evaluate: inception_splits")
+            if not hasattr(self.image_encoder, "logits"):
+                raise ValueError("Evaluator.evaluate: inception_splits needs an image encoder with logits(pooled) -> class logits "
+                                 "(networks.CNNEncoder(num_classes=...))")
         dev = self.device
         rng = torch.Generator(device=dev)
         rng.manual_seed(int(seed))
@@ -348,6 +415,7 @@ class Evaluator:
         sents: List[Tensor] = []
         cids: List[np.ndarray] = []
         feats: List[Tensor] = []
+        class_logits: List[Tensor] = []
         fm, n = None, 0
         with _eval_mode(self.G, self.text_encoder, self.image_encoder):
             for batch in batches:
@@ -372,12 +440,16 @@ class Evaluator:
                 fm.update(pooled[:keep])
                 if real_features is not None:
                     feats.append(pooled[:keep].detach().float())
+                if inception_splits is not None:
+                    class_logits.append(self.image_encoder.logits(pooled[:keep]).detach().float())
                 codes.append(code[:keep])
                 sents.append(sent_embs[:keep])
                 cids.append(np.asarray(class_ids.detach().cpu() if isinstance(class_ids, Tensor) else class_ids).reshape(-1)[:keep])
                 n += keep
         if n == 0:
             raise ValueError("Evaluator.evaluate: no batch passed the guard")
+        if inception_splits is not None:
+            _splits_arg(inception_splits, n, "Evaluator.evaluate: inception_splits")
         out = r_precision(torch.cat(codes), torch.cat(sents), np.concatenate(cids), R=R, seed=seed, folds=folds)
         out["fid"] = frechet_distance(real.mean(), real.cov(), fm.mean(), fm.cov())
         out["n"] = n
@@ -385,4 +457,6 @@ class Evaluator:
             fake_rows = torch.cat(feats)
             out.update(manifold_metrics(real_features, fake_rows, k=k))
             out.update(kernel_distance(real_features, fake_rows, subsets=kid_subsets, subset_size=kid_subset_size, seed=seed))
+        if inception_splits is not None:
+            out.update(inception_score(torch.cat(class_logits), int(inception_splits)))
         return out

@@ -23,14 +23,16 @@ PyTorch-ROCm ops (MIOpen convolutions) on the same device/stream as the HIP path
   channel slice, the running statistics updated as torch does; agan_bn_relu_slice_fwd / agan_bn_slice_bwd).  It needs a frozen trunk
   (no weight gradients) and BatchNorms with a momentum and running statistics, and raises ValueError otherwise -- nothing falls back.
   `hip_train` has no effect with backend="torch" or in eval mode.  `backend` is an attribute and can be switched; the state_dict
-  keys are the same for every setting.
+  keys are the same for every setting.  `CNNEncoder(..., num_classes=1000)` (default None: nothing is added) appends the classifier
+  head `fc` = Linear(2048 -> num_classes) under torchvision's keys, frozen like the trunk, and `logits(pooled)` applies it in eval
+  mode (on functional.linear with backend="hip"): what the Inception Score needs (evaluation.inception_score).
 * `StandInImageEncoder(out_dim)` -- a deliberately tiny frozen map honouring only the contract (adaptive 17x17 average pool
   -> 1x1 projection; region mean -> linear).  bench.py's default: its FLOPs are negligible, i.e. the timed step is the hot
   path of SURVEY.md §8d (which prices the trunk separately); `bench.py --image-encoder inception` times the full trunk too.
 """
 from __future__ import annotations
 
-from typing import Dict, Tuple
+from typing import Dict, Optional, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -173,8 +175,10 @@ class CNNEncoder(nn.Module):
 
     BACKENDS = ("torch", "hip")
 
-    def __init__(self, out_dim: int = 256, backend: str = "torch", hip_train: bool = False):
+    def __init__(self, out_dim: int = 256, backend: str = "torch", hip_train: bool = False, num_classes: Optional[int] = None):
         super().__init__()
+        if num_classes is not None and int(num_classes) < 1:
+            raise ValueError(f"CNNEncoder num_classes must be None or a positive integer, got {num_classes!r}")
         self.out_dim = out_dim
         self.backend = backend
         self.hip_train = hip_train
@@ -194,14 +198,24 @@ class CNNEncoder(nn.Module):
         self.emb_cnn_code = nn.Linear(2048, out_dim)
         self.emb_features.weight.data.uniform_(-0.1, 0.1)
         self.emb_cnn_code.weight.data.uniform_(-0.1, 0.1)
+        if num_classes is not None:                      # the classifier head, torchvision's `fc`: created last, so that every
+            self.fc = nn.Linear(2048, int(num_classes))  # parameter above keeps its initial value under a seed; frozen like the trunk
+            for p in self.fc.parameters():
+                p.requires_grad = False
 
     def freeze_all_weights(self):
         for p in self.parameters():
             p.requires_grad = False
 
     def load_trunk_state_dict(self, state: Dict[str, Tensor]) -> None:
-        """Load a torchvision inception_v3 state_dict supplied by the user (weights_only file); AuxLogits / fc are ignored."""
+        """Load a torchvision inception_v3 state_dict supplied by the user (weights_only file).  AuxLogits is ignored; `fc.weight` /
+        `fc.bias` are loaded into a classifier head built with num_classes (ValueError if their shapes differ from the head's) and
+        ignored without one."""
         own = self.state_dict()
+        for k in ("fc.weight", "fc.bias"):
+            if k in own and k in state and tuple(state[k].shape) != tuple(own[k].shape):
+                raise ValueError(f"CNNEncoder.load_trunk_state_dict: {k} is {tuple(state[k].shape)} in the state_dict, the head built with "
+                                 f"num_classes={self.fc.out_features} holds {tuple(own[k].shape)}")
         self.load_state_dict({k: v for k, v in state.items() if k in own and not k.startswith("emb_")}, strict=False)
 
     @property
@@ -295,3 +309,17 @@ class CNNEncoder(nn.Module):
             return AF.linear(pooled, self.emb_cnn_code.weight, self.emb_cnn_code.bias, cache[1]), pooled
         pooled = self._trunk_torch(x)[1]
         return self.emb_cnn_code(pooled), pooled
+
+    def logits(self, pooled: Tensor) -> Tensor:
+        """-> class logits [B, num_classes] of pooled vectors [B, 2048] (from `pooled` / `code_and_pooled`) under the classifier head
+        `fc`: torchvision's eval forward after the pooling, where dropout is the identity -- what the Inception Score is computed from
+        (evaluation.inception_score).  Eval mode only, as `pooled`; needs a head (num_classes at construction)."""
+        if not hasattr(self, "fc"):
+            raise ValueError("CNNEncoder.logits needs the classifier head: construct with num_classes=...")
+        if self.training:
+            raise RuntimeError("CNNEncoder.logits is an eval-mode call: call .eval() first")
+        if self._backend == "hip":
+            from ..backend import functional as AF
+            cache = self.__dict__.setdefault("_agan_fc_cache", {})
+            return AF.linear(pooled, self.fc.weight, self.fc.bias, cache)
+        return self.fc(pooled)

@@ -689,8 +689,9 @@ class GanTrainStep(ModelTrainer):
     def evaluate(self, batches, text_encoder: Callable, real, n_samples: int, use_ema: bool = False, **kwargs) -> Dict:
         """R-precision and Frechet distance of this step's generator under its own image encoder (evaluation.Evaluator.evaluate:
         `real` is a FeatureMoments of real images, e.g. from Evaluator.real_moments; kwargs: R, seed, batch_size, folds, and
-        real_features, k, kid_subsets, kid_subset_size for precision / recall, density / coverage and the kernel distance); of the
-        averaged generator with use_ema=True."""
+        real_features, k, kid_subsets, kid_subset_size for precision / recall, density / coverage and the kernel distance;
+        inception_splits for the Inception Score, which needs an image encoder with a classifier head: CNNEncoder(num_classes=...));
+        of the averaged generator with use_ema=True."""
         from ..evaluation import Evaluator
         dev = next(self.G.parameters()).device
         return Evaluator(self._sampled_generator(use_ema), text_encoder, self.image_encoder, dev).evaluate(batches, real, n_samples, **kwargs)

@@ -38,7 +38,8 @@ extern "C" {
  * (agan_conv2d_train_*: forward, data gradient and weight gradient of any small geometry); the batch preparation from device-resident
  * uint8 shards (agan_image_prep); the two halves of a Lloyd iteration behind the pseudo-caption clustering (agan_kmeans_*); the
  * reductions of a generator's evaluation (agan_moments_*, agan_retrieval_rank; agan_knn_radius, agan_manifold_scan and
- * agan_poly_kernel_sum for precision / recall, density / coverage and the kernel distance). */
+ * agan_poly_kernel_sum for precision / recall, density / coverage and the kernel distance; agan_inception_score for the Inception
+ * Score's per-split reduction over classifier logits). */
 
 enum {
     AGAN_OK = 0,
@@ -863,6 +864,31 @@ int agan_manifold_scan(const float* q /* [m, D] */, const float* ref /* [n, D] *
 size_t agan_poly_kernel_sum_ws_bytes(int n, int m, int D);
 int agan_poly_kernel_sum(const float* x /* [n, D] */, const float* y /* [m, D] */, int n, int m, int D, int exclude_diagonal,
                          double* out /* [1] */, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The Inception Score's reduction over classifier logits (csrc/iscore.hip; evaluation.py: inception_score -- Salimans et al. 2016).
+ * logits [N, C] are fp32, row-major.  Split s of `splits` covers rows [s N / splits, (s + 1) N / splits) (integer division: the
+ * contiguous chunks of the published protocol), n_s of them.  In fp64 throughout (fp32 -> fp64 on load is exact; every exp, log,
+ * product and addition after it is fp64):
+ *   m_k = max_y l[k][y];  lse_k = m_k + log sum_y exp(l[k][y] - m_k);  logp = l[k][y] - lse_k;  p = exp(logp)
+ *   Hc_s = -(1 / n_s) sum_k sum_y p logp            (a term with p == 0 counts as 0; logp is never log(p))
+ *   q_s[y] = (1 / n_s) sum_k p[k][y];  Hm_s = -sum_y q log q            (a term with q == 0 counts as 0)
+ *   IS_s = exp(Hm_s - Hc_s) = exp(mean_k KL(p(.|x_k) || q_s))
+ *   scores[s] = { IS_s, Hm_s (label entropy: diversity), Hc_s (conditional entropy: sharpness) }.
+ * The logits are read twice and nothing of size N x C is stored: a row pass (one wave per row, the row in registers) leaves lse_k and
+ * sum_y p logp per row in the workspace; a column pass recomputes p and leaves one fp64 partial of q per (split, piece of 64 rows
+ * counted from the split's first row, class); a pass per class adds the pieces in order and a one-workgroup pass per split adds the
+ * class terms and the row terms through a fixed tree.  No atomics; every sum has one fixed order that does not depend on the launch
+ * geometry: two runs give the same bits, a split's numbers depend on its own rows only, and the same rows passed alone with
+ * splits = 1 give the same bits.  A class whose logit is -inf contributes 0.  A row that holds +inf or a NaN, or nothing but -inf,
+ * makes the three numbers of its own split NaN and leaves every other split alone; no address depends on the data.
+ * Domain: N >= 1, 1 <= C <= 4096, N * C < 2^31, 1 <= splits <= min(N, 1024) (no split is empty).  Anything else, or a missing
+ * pointer, is AGAN_EINVAL with a message before any launch (agan_inception_score_ws_bytes then returns 0); a workspace that is too
+ * small is AGAN_EWORKSPACE.  Only enqueues on `stream`: no allocation, no synchronisation.
+ * ---------------------------------------------------------------------------------------------- */
+size_t agan_inception_score_ws_bytes(int N, int C, int splits);
+int agan_inception_score(const float* logits /* [N, C] */, int N, int C, int splits, double* scores /* [splits, 3] */,
+                         void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }
