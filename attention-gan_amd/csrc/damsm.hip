@@ -874,6 +874,8 @@ __global__ __launch_bounds__(kNT) void func_attn_bwd_kernel(const float* __restr
 template <int TMAX, int DR = kNT>
 constexpr size_t pair_smem_bytes() { return sizeof(PairSmem<TMAX, DR>); }
 
+// shapes the words-loss entry points take
+inline bool words_shape_ok(int B, int D, int T, int S) { return B >= 1 && B <= kMaxB && D >= 1 && D <= kNT && S >= 1 && S <= kNT && T >= 1 && T <= 32; }
 // shapes the MFMA pair kernels take (everything else runs the thread-per-row kernels)
 inline bool pair_mfma_ok(int D, int T, int S) { return T <= kMW && D <= kMD && (D & 63) == 0 && S <= kMS - 3 && S >= 16; }
 // the form of the thread-per-row pair kernels for a shape: f(Int<TMAX>, Int<DR>)
@@ -890,6 +892,10 @@ inline void allow_ce_smem() { allow_dynamic_lds<contrastive_ce_kernel>((int)((kM
 extern "C" {
 
 size_t agan_words_loss_save_elems(int B, int D, int T, int S) {      // dS, transposed features, zero-padded features
+    if (!words_shape_ok(B, D, T, S)) {                                // (a size has no error code: 0 elements and the message)
+        set_error("words_loss_save_elems: shape B=%d D=%d T=%d S=%d out of range (B in [1,%d], D and S in [1,%d], T in [1,32])", B, D, T, S, kMaxB, kNT);
+        return 0;
+    }
     return (size_t)B * B + (size_t)B * D * S + (pair_mfma_ok(D, T, S) ? (size_t)B * D * kMS : 0);
 }
 
@@ -931,7 +937,9 @@ int agan_words_loss_bwd(const float* feat, const float* wemb, const int64_t* len
                         float gamma2, float gamma3, float lambda, float* dfeat, float* dwemb, int B, int D, int T, int S, void* ws,
                         size_t ws_bytes, void* stream) {
     AGAN_REQUIRE(feat && wemb && lens && save && dloss && dfeat && dwemb && ws, "words_loss_bwd: null pointer");
-    AGAN_REQUIRE(B >= 1 && B <= kMaxB && D <= kNT && S <= kNT && T <= 32, "words_loss_bwd: shape out of range");
+    AGAN_REQUIRE(B >= 1 && B <= kMaxB, "words_loss_bwd: batch %d out of range [1,%d]", B, kMaxB);
+    AGAN_REQUIRE(D >= 1 && D <= kNT && S >= 1 && S <= kNT, "words_loss_bwd: nef %d / regions %d out of range [1,%d]", D, S, kNT);
+    AGAN_REQUIRE(T >= 1 && T <= 32, "words_loss_bwd: seq_len %d out of range [1,32]", T);
     if (ws_bytes < agan_words_loss_bwd_ws_bytes(B, D, T, S)) {
         set_error("words_loss_bwd: workspace %zu < %zu", ws_bytes, agan_words_loss_bwd_ws_bytes(B, D, T, S));
         return AGAN_EWORKSPACE;
@@ -975,6 +983,7 @@ int agan_sent_loss_fwd(const float* cnn_code, const float* rnn_code, const int64
 int agan_sent_loss_bwd(const float* cnn_code, const float* rnn_code, const float* save, const float* dloss, float gamma3, float lambda,
                        float eps, float* dcnn, float* drnn, int B, int D, void* stream) {
     AGAN_REQUIRE(cnn_code && rnn_code && save && dloss && dcnn && drnn, "sent_loss_bwd: null pointer");
+    AGAN_REQUIRE(B >= 1 && B <= kMaxB && D >= 1, "sent_loss_bwd: batch %d out of range [1,%d] or nef %d < 1", B, kMaxB, D);
     const float* dS = save;
     const float* dots = save + B * B;
     const float* norms = dots + B * B;

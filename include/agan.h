@@ -309,6 +309,13 @@ int agan_attn_bwd_dt(const void* images, const float* words, const float* w, con
  * Outputs: loss[1]; sim[B*B] (gamma3-scaled, masked similarity matrix: [image][caption]); attn maps
  * [B(caption)][T][S] of each caption against ITS OWN image (what the reference returns in att_maps).
  * fwd also leaves everything the backward needs in `save` (agan_words_loss_save_elems floats).
+ * Rows w >= lens[i] of caption i's attention maps are NOT written (every kernel form leaves them as the
+ * caller allocated them; backend/functional.py passes a zero-filled buffer).  dwemb[i][:][w >= lens[i]] is
+ * written as 0.
+ * Shapes: B in [1,128], D and S in [1,320], T (L) in [1,32]; every entry point, forward and backward,
+ * answers AGAN_EINVAL outside them before touching the device (the two size queries answer 0; the
+ * save_elems one also sets agan_last_error).  sent loss: B in [1,128], D >= 1;
+ * its `save` is dS [B*B], dots [B*B] (<cnn_j, rnn_i> at [j][i]), norms [2B] (|cnn_j|, then |rnn_i|).
  * ---------------------------------------------------------------------------------------------- */
 /* standalone func_attention forward (attention.py:82-120): query [B,D,L], context [B,D,S] -> wctx [B,D,L], attn [B,L,S] */
 int agan_func_attention_fwd(const float* query, const float* context, float gamma1, float scale, float* wctx, float* attn,
