@@ -916,6 +916,124 @@ def bn_act(x, gamma, beta, running_mean, running_var, nbt, training: bool, act: 
                           grad_dst(gamma), grad_dst(beta), _BN_GROUPS[0])
 
 
+# --------------------------------------------------------------------------------------------------------------
+# sentence-conditioned BatchNorm (utilities/layers.py: HipCondBatchNorm2d; include/agan.h: agan_cbn_*)
+# --------------------------------------------------------------------------------------------------------------
+def _cond_bn_dims(x: Tensor, gamma: Tensor, delta: Tensor, act: int, what: str) -> Tuple[int, int, int]:
+    """-> (B, C, HW) of x [B, C, ...] with gamma [C] and delta [B, 2C], or ValueError"""
+    if x.dim() < 2 or x.numel() == 0:
+        raise ValueError(f"{what}: the input must be [B, C, ...] and not empty, got {tuple(x.shape)}")
+    B, C = int(x.shape[0]), int(x.shape[1])
+    if act not in (L.ACT_NONE, L.ACT_GLU):
+        raise ValueError(f"{what}: activation {act}; the conditional BatchNorm takes ACT_NONE or ACT_GLU")
+    if act == L.ACT_GLU and C % 2:
+        raise ValueError(f"{what}: GLU needs an even channel count, got {C}")
+    if tuple(gamma.shape) != (C,):
+        raise ValueError(f"{what}: the weight must be [{C}], got {tuple(gamma.shape)}")
+    if tuple(delta.shape) != (B, 2 * C):
+        raise ValueError(f"{what}: delta must be [B, 2C] = [{B}, {2 * C}], got {tuple(delta.shape)}")
+    return B, C, x.numel() // (B * C)
+
+
+def cond_bn_act_reference(x: Tensor, gamma: Tensor, beta: Tensor, delta: Tensor, running_mean: Optional[Tensor],
+                          running_var: Optional[Tensor], training: bool, act: int, eps: float = 1e-5, momentum: float = 0.1):
+    """What cond_bn_act computes, in torch ops, in x's dtype, on any device, differentiable by autograd:
+
+        xhat = (x - mean[c]) / sqrt(var[c] + eps)       batch statistics over (b, p) with the biased variance when `training`,
+                                                        else the running statistics
+        z = (gamma[c] + delta[b, c]) * xhat + (beta[c] + delta[b, C + c])        out = z (ACT_NONE) or GLU over channel halves
+
+    -> (out, running_mean, running_var): the running statistics after the momentum update with the unbiased variance (the inputs
+    themselves, untouched, in eval mode or when they are None)."""
+    B, C, HW = _cond_bn_dims(x, gamma, delta, act, "cond_bn_act_reference")
+    xs = x.reshape(B, C, HW)
+    if training:
+        mean = xs.mean(dim=(0, 2))
+        var = ((xs - mean.view(1, C, 1)) ** 2).mean(dim=(0, 2))
+        if running_mean is not None:
+            n = B * HW
+            unbiased = var.detach() * (n / (n - 1)) if n > 1 else var.detach()
+            running_mean = (1 - momentum) * running_mean + momentum * mean.detach()
+            running_var = (1 - momentum) * running_var + momentum * unbiased
+    else:
+        mean, var = running_mean, running_var
+    xhat = (xs - mean.view(1, C, 1)) * torch.rsqrt(var.view(1, C, 1) + eps)
+    z = (gamma.view(1, C) + delta[:, :C]).unsqueeze(2) * xhat + (beta.view(1, C) + delta[:, C:]).unsqueeze(2)
+    if act == L.ACT_GLU:
+        z = z[:, :C // 2] * torch.sigmoid(z[:, C // 2:])
+    return z.reshape((B, z.shape[1]) + tuple(x.shape[2:])), running_mean, running_var
+
+
+class _CondBnActFn(Function):
+    @staticmethod
+    def forward(ctx, x, gamma, beta, delta, running_mean, running_var, nbt, training, act, eps, momentum, gdst, bdst):
+        shape = x.shape
+        B, C = shape[0], shape[1]
+        HW = x.numel() // (B * C)
+        g, b = _dev(gamma.detach(), "cond bn weight"), _dev(beta.detach(), "cond bn bias")
+        lib = L.load()
+        co = C // 2 if act == L.ACT_GLU else C
+        out = torch.empty((B, co) + tuple(shape[2:]), dtype=torch.float32, device=x.device)
+        if training:
+            mean = torch.empty(C, dtype=torch.float32, device=x.device)
+            invstd = torch.empty_like(mean)
+            nbytes = lib.agan_cbn_train_fwd_ws_bytes(B, C, HW)
+            ws, wsp = _ws(nbytes, x)
+            L.call("agan_cbn_train_fwd", _p(x), _p(g), _p(b), _p(delta), _p(out), _p(mean), _p(invstd), _p(running_mean),
+                   _p(running_var), _p(nbt), B, C, HW, float(eps), float(momentum), act, wsp, nbytes, _stream(), _p(_amax_out(out)))
+        else:
+            mean = running_mean
+            invstd = torch.rsqrt(running_var + eps)
+            L.call("agan_cbn_act_fwd", _p(x), _p(mean), _p(invstd), _p(g), _p(b), _p(delta), _p(out), B, C, HW, act, _stream(),
+                   _p(_amax_out(out)))
+        ctx.save_for_backward(x, g, b, delta, mean, invstd)
+        ctx.act, ctx.training, ctx.gdst, ctx.bdst = act, training, gdst, bdst
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        if not ctx.training:
+            raise L.AganError("BatchNorm backward in eval mode is not on the training path")
+        x, g, b, delta, mean, invstd = ctx.saved_tensors
+        dout = _dev(dout, "cond bn grad")
+        B, C = x.shape[0], x.shape[1]
+        HW = x.numel() // (B * C)
+        dx = torch.empty_like(x)
+        ddelta = torch.empty_like(delta)
+        # (frozen affine parameters: the sums go to scratch, as in _BnActFn)
+        dgbuf, gacc, dg = _grad_out(ctx.gdst if ctx.needs_input_grad[1] else None, g.shape, x)
+        dbbuf, bacc, db = _grad_out(ctx.bdst if ctx.needs_input_grad[2] else None, b.shape, x)
+        if gacc != bacc:
+            raise L.AganError("BatchNorm weight/bias gradient destinations out of step")
+        nbytes = L.load().agan_cbn_act_bwd_ws_bytes(B, C, HW)
+        ws, wsp = _ws(nbytes, x)
+        L.call("agan_cbn_act_bwd", _p(x), _p(dout), _p(mean), _p(invstd), _p(g), _p(b), _p(delta), _p(dx), _p(ddelta), _p(dgbuf),
+               _p(dbbuf), B, C, HW, ctx.act, gacc, wsp, nbytes, _stream(), _p(_amax_out(dx)))
+        return dx, dg, db, ddelta, None, None, None, None, None, None, None, None, None
+
+
+def cond_bn_act(x, gamma, beta, delta, running_mean, running_var, nbt, training: bool, act: int, eps: float = 1e-5,
+                momentum: float = 0.1) -> Tensor:
+    """Sentence-conditioned BatchNorm + activation on the HIP kernels (csrc/cond_bn.hip), fp32, with autograd: train-mode BatchNorm
+    of x [B, C, ...] whose affine terms are gamma[c] + delta[b, c] and beta[c] + delta[b, C + c], then ACT_NONE or ACT_GLU
+    (cond_bn_act_reference states it in torch ops).  delta is a contiguous fp32 [B, 2C] device tensor and receives its gradient
+    from autograd; the gamma / beta gradients go to the parameters' flat-gradient slices like bn_act's.  In eval mode the forward
+    uses the running statistics and a backward raises.  Not built: `bn_groups` other than 1 and 16-bit activation storage."""
+    B, C, HW = _cond_bn_dims(x, gamma, delta, act, "cond_bn_act")
+    if _BN_GROUPS[0] != 1:
+        raise L.AganError(f"cond_bn_act: bn_groups({_BN_GROUPS[0]}) is in force; the conditional BatchNorm normalises the batch as one group")
+    if get_activation_storage() != L.DT_F32 or x.dtype in _DT_OF:
+        raise L.AganError("cond_bn_act: the conditional BatchNorm kernels store fp32 only; 16-bit activation storage "
+                          "(set_activation_storage) is not built for them")
+    if not delta.is_cuda or delta.dtype != torch.float32 or not delta.is_contiguous():
+        raise L.AganError(f"cond_bn_act: delta must be a contiguous float32 [B, 2C] device tensor, got {delta.dtype} on {delta.device}"
+                          f"{'' if delta.is_contiguous() else ', not contiguous'}")
+    x = _dev(x, "cond bn input")
+    return _CondBnActFn.apply(x, gamma, beta, delta, running_mean, running_var, nbt, training, act, eps, momentum,
+                              grad_dst(gamma), grad_dst(beta))
+
+
 class _ActFn(Function):
     @staticmethod
     def forward(ctx, x, act):

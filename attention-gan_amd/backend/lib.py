@@ -104,6 +104,12 @@ _SIGNATURES = {
     "agan_glu_fwd": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
     "agan_glu_bwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),
     "agan_bn_last_launch": (c_int, [_P, c_int]),
+    "agan_cbn_train_fwd_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "agan_cbn_train_fwd": (c_int, [_P] * 10 + [c_int, c_int, c_int, c_float, c_float, c_int, _P, c_size_t, _P, _P]),
+    "agan_cbn_act_fwd": (c_int, [_P] * 7 + [c_int, c_int, c_int, c_int, _P, _P]),
+    "agan_cbn_act_bwd_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "agan_cbn_act_bwd": (c_int, [_P] * 11 + [c_int, c_int, c_int, c_int, c_int, _P, c_size_t, _P, _P]),
+    "agan_cbn_last_launch": (c_int, [_P, c_int]),
     "agan_attn_fwd": (c_int, [_P, _P, _P, _P, c_float, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     "agan_attn_bwd_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "agan_attn_bwd": (c_int, [_P] * 7 + [c_float, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_size_t, _P]),

@@ -8,14 +8,6 @@ using namespace agan;
 
 namespace {
 
-constexpr float kSlope = 0.2f;   // LeakyReLU slope, utilities/layers.py:124
-
-__device__ __forceinline__ float sigmoidf_(float v) { return 1.f / (1.f + __expf(-v)); }
-
-// Values per thread and loop step of the streaming sweeps: 8 where a 16-bit tensor is involved and rows are whole 8-groups (16-byte
-// accesses on it), else 4, else 1.  The host's choice of template width and the in-kernel loop choice both call this.
-__host__ __device__ __forceinline__ int vec_width(bool any16, int HW) { return (any16 && (HW & 7) == 0) ? 8 : ((HW & 3) == 0 ? 4 : 1); }
-
 // ---- launch log: one integer per kernel launch of the last agan_bn_* / agan_act_* / agan_glu_* call (agan_bn_last_launch) --------
 constexpr int kLogCap = 64;
 thread_local int g_log[kLogCap];
@@ -27,18 +19,6 @@ inline void log_reset() { g_log_n = 0; }
 inline void log_launch(int kind, int act, int xdt, int odt, int width) {
     if (g_log_n < kLogCap) g_log[g_log_n] = kind * 100000 + act * 10000 + xdt * 1000 + odt * 100 + width;
     ++g_log_n;
-}
-
-// ---- chunked per-channel reduction driver -----------------------------------------------------------------
-// Calls f(x_index, flat_pixel_index, vec) for every element of channel c inside [beg, end) of the (b, p) space.
-struct Chunk { int beg, end; };
-
-__device__ __forceinline__ Chunk chunk_of(int n, int nchunk, int chunk) {
-    int len = (cdiv(n, nchunk) + 7) & ~7;          // (whole 8-element groups: the widest vector access of the kernels below)
-    Chunk c;
-    c.beg = min(n, chunk * len);
-    c.end = min(n, c.beg + len);
-    return c;
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -125,26 +105,11 @@ __global__ __launch_bounds__(256) void bn_stats_rows_kernel(const float* __restr
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// forward apply
+// forward apply (Affine / make_affine / norm_of: bn_common.h)
 // ---------------------------------------------------------------------------------------------------------
-// z = (x - m) * s + b with s = gamma * invstd.  Most channels take the folded form m = 0, b = beta - mean * s (one FMA per value).
-// Where the mean is more than kCentreAt standard deviations from 0 the fold cancels two values of magnitude |mean * s| >> |z| and
-// loses z's own scale: such a channel is centred first, m = mean, b = beta ((x - mean) is exact there).  x - 0 = x exactly, so the
-// folded channels compute exactly what the plain x * s + (beta - mean * s) computes.
-constexpr float kCentreAt = 16.f;
-struct Affine { float s, m, b; };
-__device__ __forceinline__ Affine make_affine(float mean, float invstd, float gamma, float beta) {
-    Affine a;
-    a.s = gamma * invstd;
-    const bool centre = fabsf(mean * invstd) > kCentreAt;
-    a.m = centre ? mean : 0.f;
-    a.b = centre ? beta : beta - mean * a.s;
-    return a;
-}
 __device__ __forceinline__ Affine affine_of(const float* mean, const float* invstd, const float* gamma, const float* beta, int c) {
     return make_affine(mean[c], invstd[c], gamma[c], beta[c]);
 }
-__device__ __forceinline__ float norm_of(const Affine& a, float x) { return (x - a.m) * a.s + a.b; }
 
 // XDT: storage type of x; ODT: of out and the residual
 // V: elements per thread and iteration (1, 4, or 8 where a 16-bit tensor is involved: 16-byte accesses on it)
@@ -195,24 +160,6 @@ __global__ __launch_bounds__(256) void bn_act_fwd_kernel(const void* __restrict_
 // ---------------------------------------------------------------------------------------------------------
 // backward: pass 1 = per-channel sums of dz and dz*xhat, pass 2 = dx
 // ---------------------------------------------------------------------------------------------------------
-// dz for one element.  GLU: returns dz of the value half in dza and of the gate half in dzg.
-template <int ACT>
-__device__ __forceinline__ void dz_of(float xa, float xg, float d, const Affine& a, const Affine& g, float& dza, float& dzg) {
-    if (ACT == AGAN_ACT_GLU) {
-        const float za = norm_of(a, xa);
-        const float sg = sigmoidf_(norm_of(g, xg));
-        dza = d * sg;
-        dzg = d * za * sg * (1.f - sg);
-    } else if (ACT == AGAN_ACT_LRELU) {
-        const float z = norm_of(a, xa);
-        dza = z > 0.f ? d : d * kSlope;         // torch's leaky_relu_backward: slope 1 only where the input is > 0
-        dzg = 0.f;
-    } else {
-        dza = d;
-        dzg = 0.f;
-    }
-}
-
 template <int ACT, int XDT, int ODT>
 __global__ __launch_bounds__(256) void bn_bwd_partial_kernel(const void* __restrict__ x, const void* __restrict__ dout,
                                                              const float* __restrict__ mean, const float* __restrict__ invstd,
@@ -532,6 +479,30 @@ __global__ __launch_bounds__(256) void bn_small_bwd_kernel(const void* __restric
     if (amax) amax_commit(mx, amax);
 }
 
+// The statistics phase of bn_small_fwd_kernel alone, for a caller that applies them itself (bn_train_stats): the same values per
+// thread, added in the same order, through the same block_sum2 and bn_finish_channel -- one workgroup per channel of fp32 x.
+template <int PER>
+__global__ __launch_bounds__(256) void bn_small_stats_kernel(const float* __restrict__ x, float* __restrict__ mean, float* __restrict__ invstd,
+                                                             float* __restrict__ rmean, float* __restrict__ rvar, int64_t* __restrict__ nbt,
+                                                             int B, int C, int HW, float eps, float momentum) {
+    __shared__ double red[2][4];
+    const int c = blockIdx.x, n = B * HW;
+    if (c == 0 && threadIdx.x == 0 && nbt) *nbt += 1;
+    double s = 0.0, q = 0.0;
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+        const int i = threadIdx.x + j * 256;
+        if (i < n) {
+            const int b = i / HW, p = i - b * HW;
+            const float v = x[((size_t)b * C + c) * HW + p];
+            s += v;
+            q += (double)v * v;
+        }
+    }
+    block_sum2(s, q, red);
+    bn_finish_channel(s, q, n, eps, momentum, c, threadIdx.x == 0, mean, invstd, rmean, rvar);
+}
+
 int ew_blocks(size_t work) { return (int)std::max<size_t>(1, std::min<size_t>(cdivz(work, 256), 256 * 8)); }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -650,6 +621,22 @@ int bn_act_fwd_impl(const void* x, const float* mean, const float* invstd, const
 }
 
 }  // namespace
+
+int agan::bn_train_stats(const float* x, int B, int C, int HW, float eps, float* mean, float* invstd, float* running_mean,
+                         float* running_var, int64_t* nbt, float momentum, void* ws, size_t ws_bytes, void* stream, int* form, int* width) {
+    log_reset();
+    if (HW > 1 && (long long)B * HW <= kSmallN) {
+        AGAN_REQUIRE(x && mean && invstd && B > 0 && C > 0, "bn_train_stats: bad argument");
+        with_per(B * HW, [&](auto P) {
+            *form = 2, *width = P();
+            hipLaunchKernelGGL(bn_small_stats_kernel<P()>, dim3(C), dim3(256), 0, as_stream(stream), x, mean, invstd, running_mean,
+                               running_var, nbt, B, C, HW, eps, momentum);
+        });
+        return check_launch("bn_train_stats/small");
+    }
+    *form = HW == 1 ? 1 : 3, *width = vec_width(false, HW);
+    return bn_stats_impl(x, B, C, HW, eps, mean, invstd, running_mean, running_var, nbt, momentum, ws, ws_bytes, stream, AGAN_DT_F32);
+}
 
 extern "C" {
 

@@ -9,17 +9,32 @@ from .generator_submodules import GenInitialStage, GenMakeImage, GenNextStage, V
 
 
 class Generator(nn.Module):
-    def __init__(self, gf_dim: int, emb_dim: int, z_dim: int, cond_dim: int):
+    """`cond_bn` (not in the reference): the BatchNorm of every upBlock is conditional on the CA-net code `condition`
+    (utilities/layers.py: HipCondBatchNorm2d), which then reaches every scale and trains the CA-net through it.  Its extra weights
+    ('...2.cond.weight', one per upBlock) start at zero without a random draw: under one seed every other parameter equals the
+    unconditional generator's, and so does the function until they are trained.  Warm start: load an unconditional checkpoint with
+    strict=False -- only those keys are reported missing and they stay zero."""
+
+    def __init__(self, gf_dim: int, emb_dim: int, z_dim: int, cond_dim: int, cond_bn: bool = False):
         super().__init__()
-        self.gf_dim, self.emb_dim, self.z_dim, self.cond_dim = gf_dim, emb_dim, z_dim, cond_dim
+        self.gf_dim, self.emb_dim, self.z_dim, self.cond_dim, self.cond_bn = gf_dim, emb_dim, z_dim, cond_dim, bool(cond_bn)
         # creation order = the reference's, so the same torch seed yields the same initial weights
         self.vae = VarAutoEncoder(emb_dim=emb_dim, cond_dim=cond_dim)
-        self.gen1 = GenInitialStage(gf_dim=gf_dim * 16, z_dim=z_dim, cond_dim=cond_dim)
+        self.gen1 = GenInitialStage(gf_dim=gf_dim * 16, z_dim=z_dim, cond_dim=cond_dim, cond_bn=cond_bn)
         self.img_out1 = GenMakeImage(gf_dim=gf_dim)
-        self.gen2 = GenNextStage(gf_dim=gf_dim, emb_dim=emb_dim, num_residual_blocks=2)
+        self.gen2 = self._next_stage()
         self.img_out2 = GenMakeImage(gf_dim=gf_dim)
-        self.gen3 = GenNextStage(gf_dim=gf_dim, emb_dim=emb_dim, num_residual_blocks=2)
+        self.gen3 = self._next_stage()
         self.img_out3 = GenMakeImage(gf_dim=gf_dim)
+
+    def _next_stage(self) -> GenNextStage:
+        return GenNextStage(gf_dim=self.gf_dim, emb_dim=self.emb_dim, num_residual_blocks=2,
+                            cond_bn_dim=self.cond_dim if self.cond_bn else None)
+
+    def _run_stage(self, stage: GenNextStage, images: Tensor, word_embs: Tensor, mask: Tensor, condition: Tensor):
+        if self.cond_bn:
+            return stage(images, word_embs, mask, condition)
+        return stage(images, word_embs, mask)
 
     def forward(self, noise: Tensor, sent_emb: Tensor, word_embs: Tensor, mask: Tensor, eps: Optional[Tensor] = None):
         """(noise [B,z], sent_emb [B,emb], word_embs [B,emb,T], mask [B,T]) ->
@@ -31,7 +46,7 @@ class Generator(nn.Module):
         images = self.gen1(noise, condition)
         fake_imgs.append(self.img_out1(images))
         for stage, head in ((self.gen2, self.img_out2), (self.gen3, self.img_out3)):
-            images, attn = stage(images, word_embs, mask)
+            images, attn = self._run_stage(stage, images, word_embs, mask, condition)
             fake_imgs.append(head(images))
             attn_maps.append(attn)
         return (fake_imgs, attn_maps, mu, logvar)
@@ -43,11 +58,11 @@ class Generator1(nn.Module):
     `vae.*`, `gen1.*`, `img_out1.*` entries load into it.  forward() keeps the Generator's signature and return shape
     (one image, no attention maps), so trainers.GanTrainStep drives it with a single discriminator."""
 
-    def __init__(self, gf_dim: int, emb_dim: int, z_dim: int, cond_dim: int):
+    def __init__(self, gf_dim: int, emb_dim: int, z_dim: int, cond_dim: int, cond_bn: bool = False):
         super().__init__()
-        self.gf_dim, self.emb_dim, self.z_dim, self.cond_dim = gf_dim, emb_dim, z_dim, cond_dim
+        self.gf_dim, self.emb_dim, self.z_dim, self.cond_dim, self.cond_bn = gf_dim, emb_dim, z_dim, cond_dim, bool(cond_bn)
         self.vae = VarAutoEncoder(emb_dim=emb_dim, cond_dim=cond_dim)
-        self.gen1 = GenInitialStage(gf_dim=gf_dim * 16, z_dim=z_dim, cond_dim=cond_dim)
+        self.gen1 = GenInitialStage(gf_dim=gf_dim * 16, z_dim=z_dim, cond_dim=cond_dim, cond_bn=cond_bn)
         self.img_out1 = GenMakeImage(gf_dim=gf_dim)
 
     def forward(self, noise: Tensor, sent_emb: Tensor, word_embs: Optional[Tensor] = None, mask: Optional[Tensor] = None,

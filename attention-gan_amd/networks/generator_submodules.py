@@ -26,49 +26,57 @@ class _FcBnGlu(nn.Module):
 
 
 class GenInitialStage(nn.Module):
-    """(noise, condition) -> [B, gf_dim/16, 64, 64]: fc+BN1d+GLU, view [B,gf_dim,4,4], four upBlocks (:13-66)."""
+    """(noise, condition) -> [B, gf_dim/16, 64, 64]: fc+BN1d+GLU, view [B,gf_dim,4,4], four upBlocks (:13-66).  `cond_bn`: the
+    upBlocks' BatchNorms are conditional on `condition` as well (not in the reference)."""
 
-    def __init__(self, gf_dim: int, z_dim: int, cond_dim: int):
+    def __init__(self, gf_dim: int, z_dim: int, cond_dim: int, cond_bn: bool = False):
         super().__init__()
-        self.gf_dim, self.z_dim, self.cond_dim = gf_dim, z_dim, cond_dim
+        self.gf_dim, self.z_dim, self.cond_dim, self.cond_bn = gf_dim, z_dim, cond_dim, bool(cond_bn)
         self.define_module()
 
     def define_module(self):
         ng = self.gf_dim
         self.fc = _FcBnGlu(self.z_dim + self.cond_dim, ng * 4 * 4 * 2)
-        self.upsample1 = Layers.upBlock(ng, ng // 2)
-        self.upsample2 = Layers.upBlock(ng // 2, ng // 4)
-        self.upsample3 = Layers.upBlock(ng // 4, ng // 8)
-        self.upsample4 = Layers.upBlock(ng // 8, ng // 16)
+        cd = self.cond_dim if self.cond_bn else None
+        self.upsample1 = Layers.upBlock(ng, ng // 2, cd)
+        self.upsample2 = Layers.upBlock(ng // 2, ng // 4, cd)
+        self.upsample3 = Layers.upBlock(ng // 4, ng // 8, cd)
+        self.upsample4 = Layers.upBlock(ng // 8, ng // 16, cd)
 
     def forward(self, noise: Tensor, condition: Tensor) -> Tensor:
         x = self.fc(torch.cat((noise, condition), 1)).view(-1, self.gf_dim, 4, 4)
         for up in (self.upsample1, self.upsample2, self.upsample3, self.upsample4):
-            x = up(x)
+            x = up(x, condition) if self.cond_bn else up(x)
         return x
 
 
 class GenNextStage(nn.Module):
-    """attention -> concat -> residual blocks -> upBlock (:69-120).  Returns (images [B,gf,2h,2w], attn [B,T,h,w])."""
+    """attention -> concat -> residual blocks -> upBlock (:69-120).  Returns (images [B,gf,2h,2w], attn [B,T,h,w]).
+    `cond_bn_dim`: the upBlock's BatchNorm is conditional on a [B, cond_bn_dim] code that forward() then takes (not in the
+    reference); the residual blocks' BatchNorms stay as they are."""
 
-    def __init__(self, gf_dim: int, emb_dim: int, num_residual_blocks: int):
+    def __init__(self, gf_dim: int, emb_dim: int, num_residual_blocks: int, cond_bn_dim: Optional[int] = None):
         super().__init__()
-        self.gf_dim, self.emb_dim, self.num_residual_blocks = gf_dim, emb_dim, num_residual_blocks
+        self.gf_dim, self.emb_dim, self.num_residual_blocks, self.cond_bn_dim = gf_dim, emb_dim, num_residual_blocks, cond_bn_dim
         self.define_module()
 
     def define_module(self):
         self.attention = AttentionModule(nc_in=self.gf_dim, emb_dim=self.emb_dim)
         self.residual = self._make_layer(Layers.ResBlock, self.gf_dim * 2)
-        self.upsample = Layers.upBlock(self.gf_dim * 2, self.gf_dim)
+        self.upsample = Layers.upBlock(self.gf_dim * 2, self.gf_dim, self.cond_bn_dim)
 
     def _make_layer(self, block, channel_num: int):
         return nn.Sequential(*[block(channel_num) for _ in range(self.num_residual_blocks)])
 
-    def forward(self, images: Tensor, word_embs: Tensor, mask: Tensor) -> Tuple[Tensor, Tensor]:
+    def forward(self, images: Tensor, word_embs: Tensor, mask: Tensor, condition: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+        if self.cond_bn_dim is not None and condition is None:
+            raise ValueError("GenNextStage was built with cond_bn_dim: forward() needs the [B, cond_bn_dim] condition")
         self.attention.apply_mask(mask=mask)
         context, attn = self.attention(images, word_embs)
         x = self.residual(torch.cat((images, context), 1))
-        return self.upsample(x), attn
+        if self.cond_bn_dim is None:
+            return self.upsample(x), attn
+        return self.upsample(x, condition), attn
 
 
 class _ConvTanh(nn.Module):

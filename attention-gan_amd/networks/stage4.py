@@ -12,15 +12,15 @@ from torch import Tensor, nn
 from ..utilities.layers import Layers
 from .discriminators import _Disc, _LogitHead
 from .generator import Generator
-from .generator_submodules import GenMakeImage, GenNextStage
+from .generator_submodules import GenMakeImage
 
 
 class Generator4(Generator):
     """Generator with a 4th stage: returns 4 images (64, 128, 256, 512) and 3 attention maps."""
 
-    def __init__(self, gf_dim: int, emb_dim: int, z_dim: int, cond_dim: int):
-        super().__init__(gf_dim, emb_dim, z_dim, cond_dim)
-        self.gen4 = GenNextStage(gf_dim=gf_dim, emb_dim=emb_dim, num_residual_blocks=2)
+    def __init__(self, gf_dim: int, emb_dim: int, z_dim: int, cond_dim: int, cond_bn: bool = False):
+        super().__init__(gf_dim, emb_dim, z_dim, cond_dim, cond_bn)
+        self.gen4 = self._next_stage()
         self.img_out4 = GenMakeImage(gf_dim=gf_dim)
 
     def forward(self, noise: Tensor, sent_emb: Tensor, word_embs: Tensor, mask: Tensor, eps: Optional[Tensor] = None):
@@ -30,7 +30,7 @@ class Generator4(Generator):
         images = self.gen1(noise, condition)
         fake_imgs.append(self.img_out1(images))
         for stage, head in ((self.gen2, self.img_out2), (self.gen3, self.img_out3), (self.gen4, self.img_out4)):
-            images, attn = stage(images, word_embs, mask)
+            images, attn = self._run_stage(stage, images, word_embs, mask, condition)
             fake_imgs.append(head(images))
             attn_maps.append(attn)
         return (fake_imgs, attn_maps, mu, logvar)

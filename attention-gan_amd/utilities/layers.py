@@ -73,6 +73,27 @@ class HipBatchNorm2d(nn.BatchNorm2d, _BNState):
         return self.fused(x, L.ACT_NONE)
 
 
+class HipCondBatchNorm2d(HipBatchNorm2d):
+    """BatchNorm2d whose affine terms depend on a per-sample code: gamma[c] + dgamma[b, c], beta[c] + dbeta[b, c] with
+    (dgamma, dbeta) = cond(code), one bias-free linear layer (HF.cond_bn_act).  `cond.weight` starts at ZERO and is allocated
+    without a draw from the torch RNG, so the module starts as the plain BatchNorm2d it extends, and a network built with it under a
+    seed has every other parameter equal to the unconditional network's under that seed."""
+
+    def __init__(self, num_features: int, cond_dim: int):
+        super().__init__(num_features)
+        self.cond = HipLinear(cond_dim, 2 * num_features, bias=False, device="meta")      # (no storage, no draw)
+        self.cond.weight = nn.Parameter(torch.zeros(2 * num_features, cond_dim))
+
+    def forward(self, x: Tensor, condition: Tensor) -> Tensor:
+        return self.fused_cond(x, condition, L.ACT_NONE)
+
+    def fused_cond(self, x: Tensor, condition: Tensor, act: int) -> Tensor:
+        if self.momentum is None or not self.track_running_stats or not self.affine:
+            raise NotImplementedError("only the default BatchNorm configuration is on the hot path")
+        return HF.cond_bn_act(x, self.weight, self.bias, self.cond(condition), self.running_mean, self.running_var,
+                              self.num_batches_tracked, self.training, act, self.eps, self.momentum)
+
+
 class HipBatchNorm1d(nn.BatchNorm1d, _BNState):
     def forward(self, x: Tensor) -> Tensor:
         return self.fused(x, L.ACT_NONE)
@@ -104,14 +125,16 @@ class FusedChain(nn.Module):
         super().__init__()
         self._stages: List[_Stage] = []
 
-    def add_stage(self, conv_idx: int, conv: HipConv2d, bn_idx: Optional[int], act: int) -> "FusedChain":
+    def add_stage(self, conv_idx: int, conv: HipConv2d, bn_idx: Optional[int], act: int, cond_dim: Optional[int] = None) -> "FusedChain":
+        """`cond_dim`: the stage's BatchNorm is a HipCondBatchNorm2d on a code of that width, which run() then needs"""
         self.add_module(str(conv_idx), conv)
         if bn_idx is not None:
-            self.add_module(str(bn_idx), HipBatchNorm2d(conv.out_channels))
+            self.add_module(str(bn_idx), HipBatchNorm2d(conv.out_channels) if cond_dim is None
+                            else HipCondBatchNorm2d(conv.out_channels, cond_dim))
         self._stages.append(_Stage(str(conv_idx), None if bn_idx is None else str(bn_idx), act))
         return self
 
-    def run(self, x: Tensor, residual: Optional[Tensor] = None) -> Tensor:
+    def run(self, x: Tensor, residual: Optional[Tensor] = None, condition: Optional[Tensor] = None) -> Tensor:
         last = len(self._stages) - 1
         handoff = None
         for i, st in enumerate(self._stages):
@@ -125,15 +148,23 @@ class FusedChain(nn.Module):
             y = conv(x, L.ACT_NONE, None, handoff)
             handoff = None
             if st.bn is not None:
-                x = getattr(self, st.bn).fused(y, st.act, residual if i == last else None)
+                bn = getattr(self, st.bn)
+                if isinstance(bn, HipCondBatchNorm2d):
+                    if condition is None:
+                        raise ValueError("this block's BatchNorm is conditional: forward(x, condition) needs the code")
+                    if residual is not None:
+                        raise NotImplementedError("the conditional BatchNorm takes no residual")
+                    x = bn.fused_cond(y, condition, st.act)
+                else:
+                    x = bn.fused(y, st.act, residual if i == last else None)
             elif st.act != L.ACT_NONE:
                 x = HF.activation(y, st.act)
             else:
                 x = y
         return x
 
-    def forward(self, x: Tensor) -> Tensor:
-        return self.run(x)
+    def forward(self, x: Tensor, condition: Optional[Tensor] = None) -> Tensor:
+        return self.run(x, condition=condition)
 
 
 class _ReluChain(FusedChain):
@@ -188,9 +219,11 @@ class Layers:
         return HipConv2d(in_planes, out_planes, 4, 2, 1, bias)
 
     @staticmethod
-    def upBlock(in_planes: int, out_planes: int) -> FusedChain:
-        """Upsample(x2) -> conv3x3(in, 2*out) -> BN -> GLU; keys '1.weight', '2.*' (index 0/3 hold no state)."""
-        return FusedChain().add_stage(1, HipConv2d(in_planes, out_planes * 2, 3, 1, 1, False, kind="up"), 2, L.ACT_GLU)
+    def upBlock(in_planes: int, out_planes: int, cond_dim: Optional[int] = None) -> FusedChain:
+        """Upsample(x2) -> conv3x3(in, 2*out) -> BN -> GLU; keys '1.weight', '2.*' (index 0/3 hold no state).  With `cond_dim` the
+        BatchNorm is conditional on a [B, cond_dim] code (HipCondBatchNorm2d: one more key, '2.cond.weight') and the block is called
+        as forward(x, condition)."""
+        return FusedChain().add_stage(1, HipConv2d(in_planes, out_planes * 2, 3, 1, 1, False, kind="up"), 2, L.ACT_GLU, cond_dim)
 
     @staticmethod
     def upBlockReLU(in_planes: int, out_planes: int) -> FusedChain:

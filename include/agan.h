@@ -39,7 +39,7 @@ extern "C" {
  * uint8 shards (agan_image_prep); the two halves of a Lloyd iteration behind the pseudo-caption clustering (agan_kmeans_*); the
  * reductions of a generator's evaluation (agan_moments_*, agan_retrieval_rank; agan_knn_radius, agan_manifold_scan and
  * agan_poly_kernel_sum for precision / recall, density / coverage and the kernel distance; agan_inception_score for the Inception
- * Score's per-split reduction over classifier logits). */
+ * Score's per-split reduction over classifier logits); the sentence-conditioned BatchNorm of the generator's up blocks (agan_cbn_*). */
 
 enum {
     AGAN_OK = 0,
@@ -278,6 +278,44 @@ int agan_glu_bwd(const float* x, const float* dout, float* dx, int B, int C, int
  * (4 for the bare activations).  For the statistics kernels out_dtype repeats x_dtype.  Copies up to `capacity` codes into
  * codes[] and returns how many launches the call made. */
 int agan_bn_last_launch(int* codes, int capacity);
+
+/* ------------------------------------------------------------------------------------------------
+ * Sentence-conditioned BatchNorm + activation (csrc/cond_bn.hip; backend/functional.py: cond_bn_act; utilities/layers.py:
+ * HipCondBatchNorm2d).  Train-mode BatchNorm over (B, HW) per channel as above, with the affine terms per (sample, channel):
+ *     xhat[b,c,p] = (x[b,c,p] - mean[c]) * invstd[c]
+ *     g[b,c] = gamma[c] + delta[b, c]      t[b,c] = beta[c] + delta[b, C + c]      (delta [B, 2C] fp32, row-major)
+ *     z = g * xhat + t        out = z (AGAN_ACT_NONE)  or  z[:, :C/2] * sigmoid(z[:, C/2:]) (AGAN_ACT_GLU, C even)
+ * fp32 storage only; any other activation is AGAN_EINVAL.
+ *   agan_cbn_train_fwd: the statistics are agan_bn_train_fwd's -- mean, invstd, the running statistics and num_batches_tracked
+ *     come out bit for bit as that call writes them for the same x -- followed by ONE apply pass.  With delta = 0 that pass does
+ *     the arithmetic of agan_bn_act_fwd.
+ *   agan_cbn_act_fwd: the apply pass alone, mean / invstd from the caller (eval mode: the running statistics).
+ *   agan_cbn_act_bwd: with dz the gradient at z, S[b,c] = sum_p dz, Q[b,c] = sum_p dz * xhat and n = B * HW,
+ *       ddelta[b, c] = Q[b,c]    ddelta[b, C + c] = S[b,c]    dgamma[c] = sum_b Q[b,c]    dbeta[c] = sum_b S[b,c]
+ *       c0[c] = sum_b g[b,c] S[b,c] / n    c1[c] = sum_b g[b,c] Q[b,c] / n    dx = invstd[c] * (g[b,c] * dz - c0[c] - xhat * c1[c])
+ *     in three passes: the sums per plane (b, c) -- one wave per plane where HW <= 1024, else one workgroup per chunk of a plane --
+ *     then one wave per channel adds chunks and samples in index order (ddelta is overwritten; dgamma / dbeta are overwritten, or
+ *     added to where `accumulate`), then dx.  Every sum is fp64 in a fixed order, no atomics: two runs give the same bits.
+ * Null pointers (out_amax / dx_amax, the running statistics and num_batches_tracked may be NULL), an activation other than NONE /
+ * GLU, odd C under GLU, B, C or HW < 1 or B * HW >= 2^31 are AGAN_EINVAL, a workspace below *_ws_bytes AGAN_EWORKSPACE, before any
+ * launch (the size queries answer 0 for a dimension < 1).
+ *   agan_cbn_last_launch: launch log of the calling thread's last agan_cbn_* call (tests), as agan_bn_last_launch: code =
+ *     kind*100000 + act*10000 + width.  kind: 1 statistics of [B, C] rows, 2 one-launch statistics (B * HW <= 8192; width = values
+ *     per thread 2, 8, 32), 3 two-pass statistics, 4 forward apply, 5 backward sums by waves, 6 backward sums by workgroups,
+ *     7 backward final, 8 backward apply.  width: values per thread and loop step (4 where HW is a multiple of 4, else 1; 1 for
+ *     the final).  A statistics entry stands for that path's launches and carries act 0.
+ * ---------------------------------------------------------------------------------------------- */
+size_t agan_cbn_train_fwd_ws_bytes(int B, int C, int HW);
+int agan_cbn_train_fwd(const float* x, const float* gamma, const float* beta, const float* delta, float* out, float* mean,
+                       float* invstd, float* running_mean, float* running_var, int64_t* num_batches_tracked, int B, int C, int HW,
+                       float eps, float momentum, int act, void* ws, size_t ws_bytes, void* stream, float* out_amax);
+int agan_cbn_act_fwd(const float* x, const float* mean, const float* invstd, const float* gamma, const float* beta,
+                     const float* delta, float* out, int B, int C, int HW, int act, void* stream, float* out_amax);
+size_t agan_cbn_act_bwd_ws_bytes(int B, int C, int HW);
+int agan_cbn_act_bwd(const float* x, const float* dout, const float* mean, const float* invstd, const float* gamma,
+                     const float* beta, const float* delta, float* dx, float* ddelta, float* dgamma, float* dbeta, int B, int C,
+                     int HW, int act, int accumulate, void* ws, size_t ws_bytes, void* stream, float* dx_amax);
+int agan_cbn_last_launch(int* codes, int capacity);
 
 /* ------------------------------------------------------------------------------------------------
  * Word-context attention: AttentionModule.forward, networks/attention.py:25-79
