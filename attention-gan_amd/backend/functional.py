@@ -1034,6 +1034,169 @@ def cond_bn_act(x, gamma, beta, delta, running_mean, running_var, nbt, training:
                               grad_dst(gamma), grad_dst(beta))
 
 
+# --------------------------------------------------------------------------------------------------------------
+# self-attention over the positions of a feature map and the block's gate (utilities/layers.py: SelfAttention2d;
+# include/agan.h: agan_self_attn_*, agan_scaled_residual_*)
+# --------------------------------------------------------------------------------------------------------------
+def _self_attn_dims(q: Tensor, k: Tensor, v: Tensor, what: str) -> Tuple[int, int, int, int, int]:
+    """-> (B, N, M, Dk, Dv) of q [B, Dk, N...], k [B, Dk, M...], v [B, Dv, M...], or ValueError"""
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if t.dim() < 3 or t.numel() == 0:
+            raise ValueError(f"{what}: {name} must be [B, channels, positions...] and not empty, got {tuple(t.shape)}")
+    B, Dk, Dv = int(q.shape[0]), int(q.shape[1]), int(v.shape[1])
+    N, M = q.numel() // (B * Dk), v.numel() // (int(v.shape[0]) * Dv)
+    if int(k.shape[0]) != B or int(v.shape[0]) != B or int(k.shape[1]) != Dk or k.numel() != B * Dk * M:
+        raise ValueError(f"{what}: q {tuple(q.shape)}, k {tuple(k.shape)} and v {tuple(v.shape)} do not fit "
+                         f"([B, Dk, N], [B, Dk, M], [B, Dv, M])")
+    return B, N, M, Dk, Dv
+
+
+def _fp32_storage_only(what: str, *tensors: Tensor) -> None:
+    if get_activation_storage() != L.DT_F32 or any(t.dtype in _DT_OF for t in tensors):
+        raise L.AganError(f"{what}: the self-attention kernels store fp32 only; 16-bit activation storage "
+                          f"(set_activation_storage) is not built for them")
+
+
+def self_attention_reference(q: Tensor, k: Tensor, v: Tensor, scale: float = 1.0) -> Tensor:
+    """What self_attention computes, in torch ops, in q's dtype, on any device, differentiable by autograd:
+
+        s[b, n, m] = scale * sum_d q[b, d, n] k[b, d, m]      p = softmax over m      o[b, e, n] = sum_m v[b, e, m] p[b, n, m]
+
+    q [B, Dk, N...], k [B, Dk, M...], v [B, Dv, M...] -> o [B, Dv, N...]."""
+    B, N, M, Dk, Dv = _self_attn_dims(q, k, v, "self_attention_reference")
+    s = scale * torch.bmm(q.reshape(B, Dk, N).transpose(1, 2), k.reshape(B, Dk, M))
+    o = torch.bmm(v.reshape(B, Dv, M), torch.softmax(s, dim=2).transpose(1, 2))
+    return o.reshape((B, Dv) + tuple(q.shape[2:]))
+
+
+def _at(t: Tensor, elems: int) -> c_void_p:
+    return c_void_p(t.data_ptr() + 4 * elems)
+
+
+def _self_attn_fwd(q, k, v, o, lse, dims, strides, scale) -> None:
+    B, N, M, Dk, Dv = dims
+    L.call("agan_self_attn_fwd", q, k, v, _p(o), _p(lse), B, N, M, Dk, Dv, *strides, Dv * N, float(scale), _stream())
+
+
+def _self_attn_bwd(q, k, v, o, lse, dout, dq, dk, dv, dims, strides, dstrides, scale) -> None:
+    B, N, M, Dk, Dv = dims
+    nbytes = L.load().agan_self_attn_bwd_ws_bytes(B, N, M, Dk, Dv)
+    ws, wsp = _ws(nbytes, o)
+    L.call("agan_self_attn_bwd", q, k, v, _p(o), _p(lse), _p(dout), dq, dk, dv, B, N, M, Dk, Dv, *strides, Dv * N, Dv * N, *dstrides,
+           float(scale), wsp, nbytes, _stream())
+
+
+class _SelfAttnFn(Function):
+    @staticmethod
+    def forward(ctx, q, k, v, scale):
+        dims = B, N, M, Dk, Dv = _self_attn_dims(q, k, v, "self_attention")
+        o = torch.empty((B, Dv) + tuple(q.shape[2:]), dtype=torch.float32, device=q.device)
+        lse = torch.empty((B, N), dtype=torch.float32, device=q.device)
+        _self_attn_fwd(_p(q), _p(k), _p(v), o, lse, dims, (Dk * N, Dk * M, Dv * M), scale)
+        ctx.save_for_backward(q, k, v, o, lse)
+        ctx.dims, ctx.scale = dims, scale
+        return o
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        q, k, v, o, lse = ctx.saved_tensors
+        B, N, M, Dk, Dv = ctx.dims
+        dout = _dev(dout, "self-attention grad")
+        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+        strides = (Dk * N, Dk * M, Dv * M)
+        _self_attn_bwd(_p(q), _p(k), _p(v), o, lse, dout, _p(dq), _p(dk), _p(dv), ctx.dims, strides, strides, ctx.scale)
+        return dq, dk, dv, None
+
+
+class _SelfAttnQkvFn(Function):
+    """q, k, v are the channel ranges [0, dk), [dk, 2 dk), [2 dk, 2 dk + dv) of one tensor; so are dq, dk, dv of its gradient"""
+
+    @staticmethod
+    def forward(ctx, qkv, dk, dv, scale):
+        B, C = int(qkv.shape[0]), int(qkv.shape[1])
+        N = qkv.numel() // (B * C)
+        dims = (B, N, N, dk, dv)
+        o = torch.empty((B, dv) + tuple(qkv.shape[2:]), dtype=torch.float32, device=qkv.device)
+        lse = torch.empty((B, N), dtype=torch.float32, device=qkv.device)
+        _self_attn_fwd(_at(qkv, 0), _at(qkv, dk * N), _at(qkv, 2 * dk * N), o, lse, dims, (C * N,) * 3, scale)
+        ctx.save_for_backward(qkv, o, lse)
+        ctx.dims, ctx.scale = dims, scale
+        return o
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        qkv, o, lse = ctx.saved_tensors
+        B, N, _, dk, dv = ctx.dims
+        C = 2 * dk + dv
+        dout = _dev(dout, "self-attention grad")
+        dqkv = torch.empty_like(qkv)
+        strides = (C * N,) * 3
+        _self_attn_bwd(_at(qkv, 0), _at(qkv, dk * N), _at(qkv, 2 * dk * N), o, lse, dout, _at(dqkv, 0), _at(dqkv, dk * N),
+                       _at(dqkv, 2 * dk * N), ctx.dims, strides, strides, ctx.scale)
+        return dqkv, None, None, None
+
+
+def self_attention(q: Tensor, k: Tensor, v: Tensor, scale: float = 1.0) -> Tensor:
+    """Attention of every query position over every key position on the HIP kernels (csrc/self_attn.hip), fp32, with autograd;
+    self_attention_reference states it in torch ops.  q [B, Dk, N...], k [B, Dk, M...], v [B, Dv, M...] -> o [B, Dv, N...] with
+    Dk <= 64 and Dv <= 128.  Nothing of size N x M is allocated in either direction: the backward keeps q, k, v, o and one
+    log-sum-exp per query and recomputes the probabilities."""
+    _self_attn_dims(q, k, v, "self_attention")
+    _fp32_storage_only("self_attention", q, k, v)
+    return _SelfAttnFn.apply(_dev(q, "self-attention q"), _dev(k, "self-attention k"), _dev(v, "self-attention v"), float(scale))
+
+
+def self_attention_qkv(qkv: Tensor, dk: int, dv: int, scale: float = 1.0) -> Tensor:
+    """self_attention(q, k, v) with q, k, v = qkv[:, :dk], qkv[:, dk:2 dk], qkv[:, 2 dk:] of one conv output [B, 2 dk + dv, H, W],
+    passed to the kernels by stride: no slice is copied, and the backward returns ONE gradient tensor of qkv's shape that the kernels
+    wrote in place (no cat)."""
+    if qkv.dim() < 3 or qkv.numel() == 0 or dk < 1 or dv < 1 or int(qkv.shape[1]) != 2 * dk + dv:
+        raise ValueError(f"self_attention_qkv: qkv must be [B, 2 dk + dv = {2 * dk + dv}, positions...], got {tuple(qkv.shape)}")
+    _fp32_storage_only("self_attention_qkv", qkv)
+    return _SelfAttnQkvFn.apply(_dev(qkv, "self-attention qkv"), int(dk), int(dv), float(scale))
+
+
+def scaled_residual_reference(x: Tensor, y: Tensor, g: Tensor) -> Tensor:
+    """What scaled_residual computes, in torch ops: x + g * y with the one-element gate g."""
+    return x + g * y
+
+
+class _ScaledResidualFn(Function):
+    @staticmethod
+    def forward(ctx, x, y, g, gdst):
+        gd = _dev(g.detach(), "scaled_residual gate")
+        out = torch.empty_like(x)
+        L.call("agan_scaled_residual_fwd", _p(x), _p(y), _p(gd), _p(out), x.numel(), _stream())
+        ctx.save_for_backward(y, gd)
+        ctx.gdst = gdst
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        y, g = ctx.saved_tensors
+        dout = _dev(dout, "scaled_residual grad")
+        dy = torch.empty_like(y)
+        dgbuf, gacc, dg = _grad_out(ctx.gdst if ctx.needs_input_grad[2] else None, g.shape, y)
+        n = y.numel()
+        nbytes = L.load().agan_scaled_residual_bwd_ws_bytes(n)
+        ws, wsp = _ws(nbytes, y)
+        L.call("agan_scaled_residual_bwd", _p(dout), _p(y), _p(g), _p(dy), _p(dgbuf), n, gacc, wsp, nbytes, _stream())
+        return dout, dy, dg, None
+
+
+def scaled_residual(x: Tensor, y: Tensor, g: Tensor) -> Tensor:
+    """x + g[0] * y on the HIP kernels with autograd: the gate g (one element) is read on the device, its gradient sum(dout * y)
+    goes to the parameter's flat-gradient slice like bn_act's gamma, and the gradient at x is dout itself."""
+    if x.shape != y.shape or x.numel() == 0 or g.numel() != 1:
+        raise ValueError(f"scaled_residual: x {tuple(x.shape)} and y {tuple(y.shape)} must agree and g must hold one element, "
+                         f"got {tuple(g.shape)}")
+    _fp32_storage_only("scaled_residual", x, y)
+    return _ScaledResidualFn.apply(_dev(x, "scaled_residual x"), _dev(y, "scaled_residual y"), g, grad_dst(g))
+
+
 class _ActFn(Function):
     @staticmethod
     def forward(ctx, x, act):

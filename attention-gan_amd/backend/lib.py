@@ -192,6 +192,13 @@ _SIGNATURES = {
     "agan_poly_kernel_sum": (c_int, [_P, _P] + [c_int] * 4 + [_P, _P, c_size_t, _P]),
     "agan_inception_score_ws_bytes": (c_size_t, [c_int] * 3),
     "agan_inception_score": (c_int, [_P, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
+    "agan_self_attn_fwd": (c_int, [_P] * 5 + [c_int] * 5 + [c_int64] * 4 + [c_float, _P]),
+    "agan_self_attn_bwd_ws_bytes": (c_size_t, [c_int] * 5),
+    "agan_self_attn_bwd": (c_int, [_P] * 9 + [c_int] * 5 + [c_int64] * 8 + [c_float, _P, c_size_t, _P]),
+    "agan_self_attn_last_launch": (c_int, [_P, c_int]),
+    "agan_scaled_residual_fwd": (c_int, [_P] * 4 + [c_size_t, _P]),
+    "agan_scaled_residual_bwd_ws_bytes": (c_size_t, [c_size_t]),
+    "agan_scaled_residual_bwd": (c_int, [_P] * 5 + [c_size_t, c_int, _P, c_size_t, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -13,9 +13,16 @@ class Generator(nn.Module):
     (utilities/layers.py: HipCondBatchNorm2d), which then reaches every scale and trains the CA-net through it.  Its extra weights
     ('...2.cond.weight', one per upBlock) start at zero without a random draw: under one seed every other parameter equals the
     unconditional generator's, and so does the function until they are trained.  Warm start: load an unconditional checkpoint with
-    strict=False -- only those keys are reported missing and they stay zero."""
+    strict=False -- only those keys are reported missing and they stay zero.
 
-    def __init__(self, gf_dim: int, emb_dim: int, z_dim: int, cond_dim: int, cond_bn: bool = False):
+    `self_attn` (not in the reference): 32 or 64 puts a self-attention block (utilities/layers.py: SelfAttention2d, keys
+    `gen1.self_attn.{qkv.weight, proj.weight, gamma}`) on the 32x32 map (between gen1.upsample3 and upsample4, 2 gf_dim channels) or
+    the 64x64 map (after upsample4, gf_dim channels) of the initial stage.  The block is built LAST, because its two convs draw from
+    the torch RNG: under one seed every other parameter equals the plain generator's, and with gamma = 0 so does the function.
+    Warm start: load a plain checkpoint with strict=False -- exactly the three new keys are reported missing."""
+
+    def __init__(self, gf_dim: int, emb_dim: int, z_dim: int, cond_dim: int, cond_bn: bool = False, self_attn: Optional[int] = None,
+                 _defer_self_attn: bool = False):
         super().__init__()
         self.gf_dim, self.emb_dim, self.z_dim, self.cond_dim, self.cond_bn = gf_dim, emb_dim, z_dim, cond_dim, bool(cond_bn)
         # creation order = the reference's, so the same torch seed yields the same initial weights
@@ -26,6 +33,8 @@ class Generator(nn.Module):
         self.img_out2 = GenMakeImage(gf_dim=gf_dim)
         self.gen3 = self._next_stage()
         self.img_out3 = GenMakeImage(gf_dim=gf_dim)
+        if not _defer_self_attn:         # (a subclass with further stages adds the block after them)
+            self.gen1.add_self_attn(self_attn)
 
     def _next_stage(self) -> GenNextStage:
         return GenNextStage(gf_dim=self.gf_dim, emb_dim=self.emb_dim, num_residual_blocks=2,
@@ -58,12 +67,13 @@ class Generator1(nn.Module):
     `vae.*`, `gen1.*`, `img_out1.*` entries load into it.  forward() keeps the Generator's signature and return shape
     (one image, no attention maps), so trainers.GanTrainStep drives it with a single discriminator."""
 
-    def __init__(self, gf_dim: int, emb_dim: int, z_dim: int, cond_dim: int, cond_bn: bool = False):
+    def __init__(self, gf_dim: int, emb_dim: int, z_dim: int, cond_dim: int, cond_bn: bool = False, self_attn: Optional[int] = None):
         super().__init__()
         self.gf_dim, self.emb_dim, self.z_dim, self.cond_dim, self.cond_bn = gf_dim, emb_dim, z_dim, cond_dim, bool(cond_bn)
         self.vae = VarAutoEncoder(emb_dim=emb_dim, cond_dim=cond_dim)
         self.gen1 = GenInitialStage(gf_dim=gf_dim * 16, z_dim=z_dim, cond_dim=cond_dim, cond_bn=cond_bn)
         self.img_out1 = GenMakeImage(gf_dim=gf_dim)
+        self.gen1.add_self_attn(self_attn)         # last: see Generator
 
     def forward(self, noise: Tensor, sent_emb: Tensor, word_embs: Optional[Tensor] = None, mask: Optional[Tensor] = None,
                 eps: Optional[Tensor] = None):

@@ -9,7 +9,7 @@ from torch import Tensor, nn
 
 from ..backend import functional as HF
 from ..backend import lib as L
-from ..utilities.layers import GLU, HipBatchNorm1d, HipConv2d, HipLinear, Layers
+from ..utilities.layers import GLU, HipBatchNorm1d, HipConv2d, HipLinear, Layers, SelfAttention2d
 from .attention import AttentionModule
 
 
@@ -27,12 +27,28 @@ class _FcBnGlu(nn.Module):
 
 class GenInitialStage(nn.Module):
     """(noise, condition) -> [B, gf_dim/16, 64, 64]: fc+BN1d+GLU, view [B,gf_dim,4,4], four upBlocks (:13-66).  `cond_bn`: the
-    upBlocks' BatchNorms are conditional on `condition` as well (not in the reference)."""
+    upBlocks' BatchNorms are conditional on `condition` as well (not in the reference).  `self_attn` (not in the reference): the
+    feature-map size at which a SelfAttention2d block sits -- 32: between upsample3 and upsample4 (gf_dim/8 channels), 64: after
+    upsample4 (gf_dim/16 channels); None: no block, no module, no key."""
 
-    def __init__(self, gf_dim: int, z_dim: int, cond_dim: int, cond_bn: bool = False):
+    def __init__(self, gf_dim: int, z_dim: int, cond_dim: int, cond_bn: bool = False, self_attn: Optional[int] = None):
         super().__init__()
         self.gf_dim, self.z_dim, self.cond_dim, self.cond_bn = gf_dim, z_dim, cond_dim, bool(cond_bn)
+        self.self_attn, self._self_attn_after = None, 0
         self.define_module()
+        self.add_self_attn(self_attn)
+
+    def add_self_attn(self, at: Optional[int]) -> None:
+        """Constructs the block (keys `self_attn.*`).  Its two convs draw from the torch RNG, so a network that wants every other
+        parameter to equal the plain network's under one seed calls this AFTER it has built everything else (Generator does)."""
+        if at is None:
+            return
+        if at not in (32, 64):
+            raise ValueError(f"self_attn={at!r}: the block sits on the 32x32 or the 64x64 map of the initial stage (32, 64 or None)")
+        if self.self_attn is not None:
+            raise ValueError("this stage already has a self-attention block")
+        self._self_attn_after = 3 if at == 32 else 4
+        self.self_attn = SelfAttention2d(self.gf_dim // (8 if at == 32 else 16))
 
     def define_module(self):
         ng = self.gf_dim
@@ -45,8 +61,10 @@ class GenInitialStage(nn.Module):
 
     def forward(self, noise: Tensor, condition: Tensor) -> Tensor:
         x = self.fc(torch.cat((noise, condition), 1)).view(-1, self.gf_dim, 4, 4)
-        for up in (self.upsample1, self.upsample2, self.upsample3, self.upsample4):
+        for i, up in enumerate((self.upsample1, self.upsample2, self.upsample3, self.upsample4)):
             x = up(x, condition) if self.cond_bn else up(x)
+            if self._self_attn_after == i + 1:
+                x = self.self_attn(x)
         return x
 
 

@@ -94,6 +94,29 @@ class HipCondBatchNorm2d(HipBatchNorm2d):
                               self.num_batches_tracked, self.training, act, self.eps, self.momentum)
 
 
+class SelfAttention2d(nn.Module):
+    """Self-attention block over the positions of a feature map (SAGAN's non-local block): x + gamma * proj(attention(qkv(x))),
+    where qkv is one bias-free 1x1 conv whose output channels are Dk = max(1, C // qk_ratio) queries, Dk keys and
+    Dv = max(1, C // v_ratio) values, the attention is HF.self_attention_qkv with scale 1 and proj a bias-free 1x1 conv back to C.
+    `gamma` starts at ZERO: the block starts as the identity, and a network built with it computes what the network without it
+    computes until gamma is trained.  The attention and the gate are fp32 in every precision mode (the 16-bit modes change how the
+    two convs multiply); 16-bit activation storage raises."""
+
+    def __init__(self, channels: int, qk_ratio: int = 8, v_ratio: int = 2):
+        super().__init__()
+        self.channels = channels
+        self.dk, self.dv = max(1, channels // qk_ratio), max(1, channels // v_ratio)
+        self.qkv = HipConv2d(channels, 2 * self.dk + self.dv, 1, 1, 0, bias=False)
+        self.proj = HipConv2d(self.dv, channels, 1, 1, 0, bias=False)
+        self.gamma = nn.Parameter(torch.zeros(1))
+
+    def forward(self, x: Tensor) -> Tensor:
+        if HF.get_activation_storage() != L.DT_F32 or x.dtype != torch.float32:
+            raise L.AganError("SelfAttention2d: the self-attention kernels store fp32 only; 16-bit activation storage "
+                              "(set_activation_storage) is not built for them")
+        return HF.scaled_residual(x, self.proj(HF.self_attention_qkv(self.qkv(x), self.dk, self.dv)), self.gamma)
+
+
 class HipBatchNorm1d(nn.BatchNorm1d, _BNState):
     def forward(self, x: Tensor) -> Tensor:
         return self.fused(x, L.ACT_NONE)

@@ -39,7 +39,8 @@ extern "C" {
  * uint8 shards (agan_image_prep); the two halves of a Lloyd iteration behind the pseudo-caption clustering (agan_kmeans_*); the
  * reductions of a generator's evaluation (agan_moments_*, agan_retrieval_rank; agan_knn_radius, agan_manifold_scan and
  * agan_poly_kernel_sum for precision / recall, density / coverage and the kernel distance; agan_inception_score for the Inception
- * Score's per-split reduction over classifier logits); the sentence-conditioned BatchNorm of the generator's up blocks (agan_cbn_*). */
+ * Score's per-split reduction over classifier logits); the sentence-conditioned BatchNorm of the generator's up blocks (agan_cbn_*); the
+ * pixel-to-pixel attention of the generator's self-attention block and its gate (agan_self_attn_*, agan_scaled_residual_*). */
 
 enum {
     AGAN_OK = 0,
@@ -934,6 +935,51 @@ int agan_poly_kernel_sum(const float* x /* [n, D] */, const float* y /* [m, D] *
 size_t agan_inception_score_ws_bytes(int N, int C, int splits);
 int agan_inception_score(const float* logits /* [N, C] */, int N, int C, int splits, double* scores /* [splits, 3] */,
                          void* ws, size_t ws_bytes, void* stream);
+
+/* ----------------------------------------------------------------------------------------------
+ * Self-attention over the positions of a feature map (csrc/self_attn.hip; utilities/layers.py: SelfAttention2d).  fp32.
+ * Per sample b, with N query positions and M key positions:
+ *     s[n, m] = scale * sum_d q[b, d, n] * k[b, d, m]                 q [B, Dk, N]   k [B, Dk, M]
+ *     p[n, :] = softmax_m s[n, :]        lse[b, n] = log sum_m exp s[n, m]          lse [B, N] contiguous
+ *     o[b, e, n] = sum_m v[b, e, m] * p[n, m]                          v [B, Dv, M]   o [B, Dv, N]
+ * and for the backward, with do the gradient at o:
+ *     delta[n] = sum_e do[e, n] o[e, n]     dp[n, m] = sum_e do[e, n] v[e, m]     ds[n, m] = p[n, m] (dp[n, m] - delta[n])
+ *     dq[d, n] = scale sum_m ds[n, m] k[d, m]     dk[d, m] = scale sum_n ds[n, m] q[d, n]     dv[e, m] = sum_n p[n, m] do[e, n]
+ * Every operand but lse carries its own batch stride in ELEMENTS (*_bs); inside a sample its channel rows are contiguous with row
+ * stride N (q, o, do, dq) or M (k, v, dk, dv).  q, k and v may therefore be channel ranges of one [B, 2 Dk + Dv, N] tensor, and dq,
+ * dk, dv channel ranges of one gradient tensor of that shape.
+ * Nothing of size N x M is written to memory: the forward runs an online softmax (scores beyond +-88 do not overflow) and writes o
+ * and lse once; the backward recomputes p from lse in two kernels -- one whose workgroups each own a block of keys and sweep the
+ * queries (dk, dv), one whose workgroups each own a block of queries and sweep the keys (dq) -- after a small pass for delta (the
+ * workspace holds it).  Every output element is written once by one workgroup in a fixed order: no atomics, no hand-off between
+ * workgroups, two runs give the same bits.  A key past M contributes exactly 0.
+ * Domain: B, N, M >= 1, 1 <= Dk <= 64, 1 <= Dv <= 128, B * N * max(Dk, Dv) and B * M * max(Dk, Dv) below 2^31, every batch stride at
+ * least rows x row length, a finite scale.  Anything else, or a null pointer, is AGAN_EINVAL with the entry's name in
+ * agan_last_error(); a workspace below agan_self_attn_bwd_ws_bytes is AGAN_EWORKSPACE; both before any HIP call (the size query
+ * answers 0 for a refused shape).  Only enqueues on `stream`: no allocation, no synchronisation.
+ *   agan_self_attn_last_launch: launch log of the calling thread's last agan_self_attn_* / agan_scaled_residual_* call (tests), as
+ *     agan_cbn_last_launch: code = kind*100000 + block*100 + dk_tiles*10 + dv_tiles.  kind: 1 forward, 2 delta pass, 3 backward dk / dv,
+ *     4 backward dq, 5 gate forward, 6 gate backward, 7 gate backward final.  block = positions a workgroup owns (32, 64 or 128: the
+ *     largest whose LDS fits and that gives 256 workgroups, else 32); dk_tiles / dv_tiles = 32-row accumulator tiles along Dk (1, 2)
+ *     and Dv (1, 2, 4) of the kernel form, 0 where the kernel has none.
+ *
+ * The block's gate: out = x + g[0] * y over n elements, g read on the device (two roundings, as the torch statement).
+ *   agan_scaled_residual_bwd: dy = g[0] * dout; dg[0] = (accumulate ? dg[0] : 0) + sum dout * y, fp64 products summed per workgroup
+ *     and then over the workgroups, both in one fixed order.  The gradient at x is dout itself.
+ * n < 1 or a null pointer is AGAN_EINVAL, a short workspace AGAN_EWORKSPACE (agan_scaled_residual_bwd_ws_bytes(0) is 0).
+ * ---------------------------------------------------------------------------------------------- */
+int agan_self_attn_fwd(const float* q, const float* k, const float* v, float* o, float* lse, int B, int N, int M, int Dk, int Dv,
+                       long long q_bs, long long k_bs, long long v_bs, long long o_bs, float scale, void* stream);
+size_t agan_self_attn_bwd_ws_bytes(int B, int N, int M, int Dk, int Dv);
+int agan_self_attn_bwd(const float* q, const float* k, const float* v, const float* o, const float* lse, const float* dout, float* dq,
+                       float* dk, float* dv, int B, int N, int M, int Dk, int Dv, long long q_bs, long long k_bs, long long v_bs,
+                       long long o_bs, long long do_bs, long long dq_bs, long long dk_bs, long long dv_bs, float scale, void* ws,
+                       size_t ws_bytes, void* stream);
+int agan_self_attn_last_launch(int* codes, int capacity);
+int agan_scaled_residual_fwd(const float* x, const float* y, const float* g, float* out, size_t n, void* stream);
+size_t agan_scaled_residual_bwd_ws_bytes(size_t n);
+int agan_scaled_residual_bwd(const float* dout, const float* y, const float* g, float* dy, float* dg, size_t n, int accumulate, void* ws,
+                             size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }
