@@ -1307,6 +1307,149 @@ def attention(images: Tensor, words: Tensor, conv1_weight: Tensor, mask: Tensor,
 
 
 # --------------------------------------------------------------------------------------------------------------
+# dynamic memory of a refinement stage (networks/memory.py: DynamicMemory; include/agan.h: agan_mem_write_*, agan_mem_read_*)
+# --------------------------------------------------------------------------------------------------------------
+def _mem_fp32_only(what: str, *tensors: Tensor) -> None:
+    if get_activation_storage() != L.DT_F32 or any(t.dtype in _DT_OF for t in tensors):
+        raise L.AganError(f"{what}: the memory kernels store fp32 only; 16-bit activation storage (set_activation_storage) is not "
+                          f"built for them")
+
+
+def _mem_write_dims(U: Tensor, Q: Tensor, what: str) -> Tuple[int, int, int]:
+    """-> (B, T, Md) of U [B, T, Md + 1] and Q [B, Md + 1], or ValueError"""
+    if U.dim() != 3 or Q.dim() != 2 or U.numel() == 0 or U.shape[2] < 2 or tuple(Q.shape) != (U.shape[0], U.shape[2]):
+        raise ValueError(f"{what}: U must be [B, T, memory_dim + 1] and Q [B, memory_dim + 1], got {tuple(U.shape)} and {tuple(Q.shape)}")
+    return int(U.shape[0]), int(U.shape[1]), int(U.shape[2]) - 1
+
+
+def _mem_read_dims(h: Tensor, kv: Tensor, mask: Tensor, rw: Tensor, rb: Tensor, what: str) -> Tuple[int, int, int, int, int]:
+    """-> (B, C, T, H, W) of h [B, C, H, W], kv [B, T, 2C], mask [B, T], rw (2C elements) and rb (1 element), or ValueError"""
+    if h.dim() != 4 or kv.dim() != 3 or h.numel() == 0 or kv.numel() == 0:
+        raise ValueError(f"{what}: h must be [B, C, H, W] and kv [B, T, 2C], got {tuple(h.shape)} and {tuple(kv.shape)}")
+    B, C, H, W = (int(s) for s in h.shape)
+    T = int(kv.shape[1])
+    if int(kv.shape[0]) != B or int(kv.shape[2]) != 2 * C or tuple(mask.shape) != (B, T) or rw.numel() != 2 * C or rb.numel() != 1:
+        raise ValueError(f"{what}: h {tuple(h.shape)}, kv {tuple(kv.shape)}, mask {tuple(mask.shape)}, response weight {tuple(rw.shape)} "
+                         f"and bias {tuple(rb.shape)} do not fit ([B, C, H, W], [B, T, 2C], [B, T], 2C, 1)")
+    return B, C, T, H, W
+
+
+def memory_write_reference(U: Tensor, Q: Tensor) -> Tensor:
+    """What memory_write computes, in torch ops, in U's dtype, on any device, differentiable by autograd:
+
+        g = sigmoid(U[b, t, Md] + Q[b, Md])        m[b, t, d] = relu(U[b, t, d]) g + relu(Q[b, d]) (1 - g)
+
+    U [B, T, Md + 1], Q [B, Md + 1] -> m [B, T, Md]."""
+    _, _, Md = _mem_write_dims(U, Q, "memory_write_reference")
+    g = torch.sigmoid(U[:, :, Md:] + Q[:, None, Md:])
+    return torch.relu(U[:, :, :Md]) * g + torch.relu(Q[:, None, :Md]) * (1 - g)
+
+
+def memory_read_reference(h: Tensor, kv: Tensor, mask: Tensor, rw: Tensor, rb: Tensor) -> Tuple[Tensor, Tensor]:
+    """What memory_read computes, in torch ops, in h's dtype, on any device, differentiable by autograd.  With k = kv[:, :, :C],
+    v = kv[:, :, C:] and p a pixel:
+
+        s[t] = sum_c k[b, t, c] h[b, c, p], -inf where mask[b, t] == 0      attn = softmax_t s      o[c] = sum_t v[b, t, c] attn[t]
+        z = sum_c (rw[c] h[b, c, p] + rw[C + c] o[c]) + rb      g = sigmoid(z)      r[c] = h[b, c, p] (1 - g) + g o[c]
+
+    h [B, C, H, W], kv [B, T, 2C], mask [B, T], rw 2C elements, rb one -> (x = cat(r, r) [B, 2C, H, W], attn [B, T, H, W])."""
+    B, C, T, H, W = _mem_read_dims(h, kv, mask, rw, rb, "memory_read_reference")
+    hf = h.reshape(B, C, H * W)
+    s = torch.bmm(kv[:, :, :C], hf).masked_fill(mask.to(h.device).view(B, T, 1) == 0, float("-inf"))
+    attn = torch.softmax(s, dim=1)
+    o = torch.bmm(kv[:, :, C:].transpose(1, 2), attn)
+    w = rw.reshape(2 * C)
+    z = (w[:C].view(1, C, 1) * hf).sum(dim=1, keepdim=True) + (w[C:].view(1, C, 1) * o).sum(dim=1, keepdim=True) + rb.reshape(1, 1, 1)
+    g = torch.sigmoid(z)
+    r = hf * (1 - g) + g * o
+    return torch.cat((r, r), 1).reshape(B, 2 * C, H, W), attn.reshape(B, T, H, W)
+
+
+class _MemoryWriteFn(Function):
+    @staticmethod
+    def forward(ctx, U, Q):
+        B, T, Md = _mem_write_dims(U, Q, "memory_write")
+        m = torch.empty((B, T, Md), dtype=torch.float32, device=U.device)
+        L.call("agan_mem_write_fwd", _p(U), _p(Q), _p(m), B, T, Md, _stream())
+        ctx.save_for_backward(U, Q)
+        return m
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dm):
+        U, Q = ctx.saved_tensors
+        B, T, Md = _mem_write_dims(U, Q, "memory_write")
+        dm = _dev(dm, "memory_write grad")
+        dU, dQ = torch.empty_like(U), torch.empty_like(Q)
+        L.call("agan_mem_write_bwd", _p(U), _p(Q), _p(dm), _p(dU), _p(dQ), B, T, Md, _stream())
+        return dU, dQ
+
+
+def memory_write(U: Tensor, Q: Tensor) -> Tensor:
+    """The gated write of the words into the memory on the HIP kernels (csrc/memory.hip), fp32, with autograd; memory_write_reference
+    states it in torch ops.  U [B, T, Md + 1] (T <= 64), Q [B, Md + 1] -> m [B, T, Md]."""
+    _mem_write_dims(U, Q, "memory_write")
+    _mem_fp32_only("memory_write", U, Q)
+    return _MemoryWriteFn.apply(_dev(U, "memory_write U"), _dev(Q, "memory_write Q"))
+
+
+class _MemoryReadFn(Function):
+    @staticmethod
+    def forward(ctx, h, kv, mask, rw, rb, wdst, bdst):
+        B, C, T, H, W = _mem_read_dims(h, kv, mask, rw, rb, "memory_read")
+        w, bias = _dev(rw.detach(), "memory_read response weight"), _dev(rb.detach(), "memory_read response bias")
+        m = mask.to(device=h.device, dtype=torch.int64).contiguous()
+        x = torch.empty((B, 2 * C, H, W), dtype=torch.float32, device=h.device)
+        attn = torch.empty((B, T, H, W), dtype=torch.float32, device=h.device)
+        L.call("agan_mem_read_fwd", _p(h), _p(kv), _p(m), _p(w), _p(bias), _p(x), _p(attn), B, C, T, H * W, _stream())
+        ctx.save_for_backward(h, kv, m, w, bias, attn)
+        ctx.wdst, ctx.bdst = wdst, bdst
+        ctx.set_materialize_grads(False)     # the attention map usually feeds nothing: no zero-filled gradient of its size
+        return x, attn
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dx, dattn):
+        h, kv, m, w, bias, attn = ctx.saved_tensors
+        B, C, H, W = h.shape
+        T = kv.shape[1]
+        dx = _dev(dx, "memory_read dx") if dx is not None else torch.zeros((B, 2 * C, H, W), dtype=torch.float32, device=h.device)
+        dattn = _dev(dattn, "memory_read dattn") if dattn is not None else None
+        dh, dkv = torch.empty_like(h), torch.empty_like(kv)
+        # a frozen response layer still gets its sums computed: they go to scratch, not into the owner's flat buffer
+        dwbuf, wacc, dw = _grad_out(ctx.wdst if ctx.needs_input_grad[3] else None, w.shape, h)
+        dbbuf, bacc, db = _grad_out(ctx.bdst if ctx.needs_input_grad[4] else None, bias.shape, h)
+        nbytes = L.load().agan_mem_read_bwd_ws_bytes(B, C, T, H * W)
+        ws, wsp = _ws(nbytes, h)
+        L.call("agan_mem_read_bwd", _p(h), _p(kv), _p(m), _p(w), _p(bias), _p(attn), _p(dx), _p(dattn), _p(dh), _p(dkv), _p(dwbuf),
+               _p(dbbuf), B, C, T, H * W, wacc, bacc, wsp, nbytes, _stream())
+        return (dh, dkv, None, dw if ctx.needs_input_grad[3] else None, db if ctx.needs_input_grad[4] else None, None, None)
+
+
+def memory_read(h: Tensor, kv: Tensor, mask: Tensor, rw: Tensor, rb: Tensor) -> Tuple[Tensor, Tensor]:
+    """Address, read and respond of the dynamic memory in one HIP pass per direction (csrc/memory.hip), fp32, with autograd;
+    memory_read_reference states it in torch ops.  h [B, C, H, W] (C <= 64), kv [B, T, 2C] (keys | values, T <= 64), mask [B, T]
+    (0 = ignore the word), rw the response gate's weight (2C elements, any shape) and rb its bias ->
+    (x [B, 2C, H, W] = cat(r, r), attn [B, T, H, W]).  The backward keeps the attention map only and recomputes the rest; the
+    gradients of rw and rb go to their flat-gradient slices (grad_dst) where the parameters have one."""
+    _mem_read_dims(h, kv, mask, rw, rb, "memory_read")
+    _mem_fp32_only("memory_read", h, kv)
+    return _MemoryReadFn.apply(_dev(h, "memory_read h"), _dev(kv, "memory_read kv"), mask, rw, rb, grad_dst(rw), grad_dst(rb))
+
+
+def spatial_mean(x: Tensor) -> Tensor:
+    """mean over the positions of x [B, C, H, W] -> [B, C] on the HIP kernel (agan_global_avgpool_fwd), fp32.  NOT differentiable:
+    the result is detached (the dynamic memory's write gate reads the image through it without a gradient)."""
+    xd = _dev(x.detach(), "spatial_mean input")
+    if xd.dim() < 3 or xd.numel() == 0:
+        raise ValueError(f"spatial_mean: x must be [B, C, positions...] and not empty, got {tuple(x.shape)}")
+    B, C = int(xd.shape[0]), int(xd.shape[1])
+    y = torch.empty((B, C), dtype=torch.float32, device=xd.device)
+    L.call("agan_global_avgpool_fwd", _p(xd), _p(y), B, C, xd.numel() // (B * C), _stream())
+    return y
+
+
+# --------------------------------------------------------------------------------------------------------------
 # small heads
 # --------------------------------------------------------------------------------------------------------------
 class _ReparamFn(Function):

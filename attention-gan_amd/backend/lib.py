@@ -199,6 +199,11 @@ _SIGNATURES = {
     "agan_scaled_residual_fwd": (c_int, [_P] * 4 + [c_size_t, _P]),
     "agan_scaled_residual_bwd_ws_bytes": (c_size_t, [c_size_t]),
     "agan_scaled_residual_bwd": (c_int, [_P] * 5 + [c_size_t, c_int, _P, c_size_t, _P]),
+    "agan_mem_write_fwd": (c_int, [_P] * 3 + [c_int] * 3 + [_P]),
+    "agan_mem_write_bwd": (c_int, [_P] * 5 + [c_int] * 3 + [_P]),
+    "agan_mem_read_fwd": (c_int, [_P] * 7 + [c_int] * 4 + [_P]),
+    "agan_mem_read_bwd_ws_bytes": (c_size_t, [c_int] * 4),
+    "agan_mem_read_bwd": (c_int, [_P] * 12 + [c_int] * 6 + [_P, c_size_t, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -286,6 +286,7 @@ __device__ __forceinline__ float act1(float v) {
     if (ACT == AGAN_ACT_LRELU) return v > 0.f ? v : v * kSlope;
     if (ACT == AGAN_ACT_TANH) return tanhf(v);
     if (ACT == AGAN_ACT_SIGMOID) return 1.f / (1.f + expf(-v));
+    if (ACT == AGAN_ACT_RELU) return v > 0.f ? v : 0.f;
     return v;
 }
 // derivative expressed from the OUTPUT y (lrelu keeps the sign, so y works there too)
@@ -294,6 +295,7 @@ __device__ __forceinline__ float dact1(float y, float d) {
     if (ACT == AGAN_ACT_LRELU) return y > 0.f ? d : d * kSlope;      // (y > 0 exactly where the input is > 0)
     if (ACT == AGAN_ACT_TANH) return d * (1.f - y * y);
     if (ACT == AGAN_ACT_SIGMOID) return d * y * (1.f - y);
+    if (ACT == AGAN_ACT_RELU) return y > 0.f ? d : 0.f;               // (torch's rule: no gradient at exactly 0)
     return d;
 }
 
@@ -537,6 +539,7 @@ template <class F> bool bare_act(int act, F&& f) {
     if (act == AGAN_ACT_LRELU) f(Int<AGAN_ACT_LRELU>{});
     else if (act == AGAN_ACT_TANH) f(Int<AGAN_ACT_TANH>{});
     else if (act == AGAN_ACT_SIGMOID) f(Int<AGAN_ACT_SIGMOID>{});
+    else if (act == AGAN_ACT_RELU) f(Int<AGAN_ACT_RELU>{});
     else return false;
     return true;
 }

@@ -19,12 +19,19 @@ class Generator(nn.Module):
     `gen1.self_attn.{qkv.weight, proj.weight, gamma}`) on the 32x32 map (between gen1.upsample3 and upsample4, 2 gf_dim channels) or
     the 64x64 map (after upsample4, gf_dim channels) of the initial stage.  The block is built LAST, because its two convs draw from
     the torch RNG: under one seed every other parameter equals the plain generator's, and with gamma = 0 so does the function.
-    Warm start: load a plain checkpoint with strict=False -- exactly the three new keys are reported missing."""
+    Warm start: load a plain checkpoint with strict=False -- exactly the three new keys are reported missing.
+
+    `memory` (not in the reference): every refinement stage (gen2, gen3) replaces its attention module and the concat by a dynamic
+    memory (networks/memory.py: DynamicMemory, DM-GAN's stage; keys `gen{2,3}.memory.{word,image,kv,response}.{weight,bias}`, no
+    `gen{2,3}.attention.*`), `memory_dim` wide (None: 2 emb_dim).  gf_dim <= 64 and at most 64 words.  Its layers draw from the torch RNG
+    where the attention's conv drew, so a memory generator shares neither initial values nor checkpoints with the plain one.  The
+    defaults build exactly the plain generator."""
 
     def __init__(self, gf_dim: int, emb_dim: int, z_dim: int, cond_dim: int, cond_bn: bool = False, self_attn: Optional[int] = None,
-                 _defer_self_attn: bool = False):
+                 _defer_self_attn: bool = False, memory: bool = False, memory_dim: Optional[int] = None):
         super().__init__()
         self.gf_dim, self.emb_dim, self.z_dim, self.cond_dim, self.cond_bn = gf_dim, emb_dim, z_dim, cond_dim, bool(cond_bn)
+        self.memory, self.memory_dim = bool(memory), memory_dim
         # creation order = the reference's, so the same torch seed yields the same initial weights
         self.vae = VarAutoEncoder(emb_dim=emb_dim, cond_dim=cond_dim)
         self.gen1 = GenInitialStage(gf_dim=gf_dim * 16, z_dim=z_dim, cond_dim=cond_dim, cond_bn=cond_bn)
@@ -38,7 +45,7 @@ class Generator(nn.Module):
 
     def _next_stage(self) -> GenNextStage:
         return GenNextStage(gf_dim=self.gf_dim, emb_dim=self.emb_dim, num_residual_blocks=2,
-                            cond_bn_dim=self.cond_dim if self.cond_bn else None)
+                            cond_bn_dim=self.cond_dim if self.cond_bn else None, memory=self.memory, memory_dim=self.memory_dim)
 
     def _run_stage(self, stage: GenNextStage, images: Tensor, word_embs: Tensor, mask: Tensor, condition: Tensor):
         if self.cond_bn:

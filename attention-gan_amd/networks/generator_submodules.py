@@ -11,6 +11,7 @@ from ..backend import functional as HF
 from ..backend import lib as L
 from ..utilities.layers import GLU, HipBatchNorm1d, HipConv2d, HipLinear, Layers, SelfAttention2d
 from .attention import AttentionModule
+from .memory import DynamicMemory
 
 
 class _FcBnGlu(nn.Module):
@@ -71,15 +72,24 @@ class GenInitialStage(nn.Module):
 class GenNextStage(nn.Module):
     """attention -> concat -> residual blocks -> upBlock (:69-120).  Returns (images [B,gf,2h,2w], attn [B,T,h,w]).
     `cond_bn_dim`: the upBlock's BatchNorm is conditional on a [B, cond_bn_dim] code that forward() then takes (not in the
-    reference); the residual blocks' BatchNorms stay as they are."""
+    reference); the residual blocks' BatchNorms stay as they are.  `memory` (not in the reference): a DynamicMemory (networks/memory.py,
+    keys `memory.*`, `memory_dim` wide) stands where the attention module and the concat stand -- the stage then has no `attention`
+    child, and the residual blocks run on the module's [B, 2 gf_dim, h, w] output."""
 
-    def __init__(self, gf_dim: int, emb_dim: int, num_residual_blocks: int, cond_bn_dim: Optional[int] = None):
+    def __init__(self, gf_dim: int, emb_dim: int, num_residual_blocks: int, cond_bn_dim: Optional[int] = None, memory: bool = False,
+                 memory_dim: Optional[int] = None):
         super().__init__()
         self.gf_dim, self.emb_dim, self.num_residual_blocks, self.cond_bn_dim = gf_dim, emb_dim, num_residual_blocks, cond_bn_dim
+        self.use_memory, self.memory_dim = bool(memory), memory_dim
+        if memory_dim is not None and not self.use_memory:
+            raise ValueError("memory_dim is the width of the dynamic memory: it needs memory=True")
         self.define_module()
 
     def define_module(self):
-        self.attention = AttentionModule(nc_in=self.gf_dim, emb_dim=self.emb_dim)
+        if self.use_memory:
+            self.memory = DynamicMemory(nc_in=self.gf_dim, emb_dim=self.emb_dim, memory_dim=self.memory_dim)
+        else:
+            self.attention = AttentionModule(nc_in=self.gf_dim, emb_dim=self.emb_dim)
         self.residual = self._make_layer(Layers.ResBlock, self.gf_dim * 2)
         self.upsample = Layers.upBlock(self.gf_dim * 2, self.gf_dim, self.cond_bn_dim)
 
@@ -89,9 +99,14 @@ class GenNextStage(nn.Module):
     def forward(self, images: Tensor, word_embs: Tensor, mask: Tensor, condition: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
         if self.cond_bn_dim is not None and condition is None:
             raise ValueError("GenNextStage was built with cond_bn_dim: forward() needs the [B, cond_bn_dim] condition")
-        self.attention.apply_mask(mask=mask)
-        context, attn = self.attention(images, word_embs)
-        x = self.residual(torch.cat((images, context), 1))
+        if self.use_memory:
+            self.memory.apply_mask(mask=mask)
+            x, attn = self.memory(images, word_embs)
+            x = self.residual(x)
+        else:
+            self.attention.apply_mask(mask=mask)
+            context, attn = self.attention(images, word_embs)
+            x = self.residual(torch.cat((images, context), 1))
         if self.cond_bn_dim is None:
             return self.upsample(x), attn
         return self.upsample(x, condition), attn

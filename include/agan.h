@@ -40,7 +40,9 @@ extern "C" {
  * reductions of a generator's evaluation (agan_moments_*, agan_retrieval_rank; agan_knn_radius, agan_manifold_scan and
  * agan_poly_kernel_sum for precision / recall, density / coverage and the kernel distance; agan_inception_score for the Inception
  * Score's per-split reduction over classifier logits); the sentence-conditioned BatchNorm of the generator's up blocks (agan_cbn_*); the
- * pixel-to-pixel attention of the generator's self-attention block and its gate (agan_self_attn_*, agan_scaled_residual_*). */
+ * pixel-to-pixel attention of the generator's self-attention block and its gate (agan_self_attn_*, agan_scaled_residual_*); the dynamic
+ * memory of the generator's refinement stages (agan_mem_write_*, agan_mem_read_*), for which agan_act_fwd / agan_act_bwd also take
+ * AGAN_ACT_RELU. */
 
 enum {
     AGAN_OK = 0,
@@ -265,7 +267,8 @@ int agan_bn_train_fwd_dt(const void* x, const float* gamma, const float* beta, c
 int agan_bn_act_bwd_dt(const void* x, const void* dout, const float* mean, const float* invstd, const float* gamma,
                        const float* beta, void* dx, float* dgamma, float* dbeta, int B, int C, int HW, int act, int accumulate,
                        int groups, void* ws, size_t ws_bytes, void* stream, float* dx_amax, int x_dtype, int out_dtype);
-/* plain activations without BN (first D conv + LeakyReLU layers.py:139-140; tanh generator_submodules.py:137) */
+/* plain activations without BN (first D conv + LeakyReLU layers.py:139-140; tanh generator_submodules.py:137; ReLU of the dynamic
+ * memory's keys and values): act AGAN_ACT_LRELU, AGAN_ACT_TANH, AGAN_ACT_SIGMOID or AGAN_ACT_RELU (no gradient at exactly 0) */
 int agan_act_fwd(const float* x, float* out, size_t n, int act, void* stream);
 int agan_act_bwd(const float* out, const float* dout, float* dx, size_t n, int act, void* stream);
 /* standalone GLU over channel halves of [B,C,HW] (utilities/layers.py:13-26; the CA-net's "relu", generator_submodules.py:153) */
@@ -980,6 +983,37 @@ int agan_scaled_residual_fwd(const float* x, const float* y, const float* g, flo
 size_t agan_scaled_residual_bwd_ws_bytes(size_t n);
 int agan_scaled_residual_bwd(const float* dout, const float* y, const float* g, float* dy, float* dg, size_t n, int accumulate, void* ws,
                              size_t ws_bytes, void* stream);
+
+/* ----------------------------------------------------------------------------------------------
+ * Dynamic memory of a refinement stage (csrc/memory.hip; networks/memory.py: DynamicMemory; DM-GAN, Zhu et al., CVPR 2019).  fp32.
+ * Write, per sample b and word t, with U [B, T, Md + 1] the word projection and Q [B, Md + 1] the projection of the mean image feature:
+ *     g = sigmoid(U[b, t, Md] + Q[b, Md])          m[b, t, d] = relu(U[b, t, d]) g + relu(Q[b, d]) (1 - g)        m [B, T, Md]
+ *   agan_mem_write_bwd: dm -> dU, dQ (ReLU passes no gradient at exactly 0); dQ sums over the words in word order inside one
+ *     workgroup per sample.  One launch per direction.
+ * Read and respond, per pixel p of h [B, C, HW], with kv [B, T, 2C] (k = kv[:, :, :C], v = kv[:, :, C:]), mask int64 [B, T]
+ * (0 = ignore the word), rw [2C] and rb [1]:
+ *     s[t] = sum_c k[b, t, c] h[b, c, p], -inf where mask[b, t] == 0      attn[b, t, p] = softmax_t s      o[c] = sum_t v[b, t, c] attn[b, t, p]
+ *     z = sum_c (rw[c] h[b, c, p] + rw[C + c] o[c]) + rb[0]      g_r = sigmoid(z)      r[c] = h[b, c, p] (1 - g_r) + g_r o[c]
+ *     x[b, c, p] = x[b, C + c, p] = r[c]                              x [B, 2C, HW]   attn [B, T, HW]
+ *   One pass: h is read once, both halves of x and attn are written once.  A sample whose words are all masked gives NaN.
+ *   agan_mem_read_bwd: from dx [B, 2C, HW] (dr = dx[:, :C] + dx[:, C:]) and the optional dattn [B, T, HW] (NULL = zero) to dh [B, C, HW],
+ *     dkv [B, T, 2C], drw [2C] and drb [1].  Nothing but attn is kept from the forward: o and g_r are recomputed.  `mask` is not read (a
+ *     masked word has attn = 0 and takes no gradient).  accumulate_rw / accumulate_rb != 0: the sums are ADDED to drw / drb (the
+ *     parameter is used again in one backward; agan_attn_bwd's convention).  Every sum over pixels and samples goes through one partial
+ *     slab per workgroup of 256 pixels in `ws` and an ordered reduce: no float atomics, two runs give the same bits.
+ * Domain: B, T, Md, C, HW >= 1, T <= 64, C <= 64, B <= 65535, B * T * (Md + 1), B * 2C * HW and B * T * HW below 2^31.  Anything else, or
+ * a null pointer (dattn excepted), is AGAN_EINVAL with the entry's name in agan_last_error() before any HIP call
+ * (agan_mem_read_bwd_ws_bytes then answers 0); a workspace below agan_mem_read_bwd_ws_bytes is AGAN_EWORKSPACE.  Only enqueues on
+ * `stream`: no allocation, no synchronisation; graph-capturable.
+ * ---------------------------------------------------------------------------------------------- */
+int agan_mem_write_fwd(const float* U, const float* Q, float* m, int B, int T, int Md, void* stream);
+int agan_mem_write_bwd(const float* U, const float* Q, const float* dm, float* dU, float* dQ, int B, int T, int Md, void* stream);
+int agan_mem_read_fwd(const float* h, const float* kv, const int64_t* mask, const float* rw, const float* rb, float* x, float* attn,
+                      int B, int C, int T, int HW, void* stream);
+size_t agan_mem_read_bwd_ws_bytes(int B, int C, int T, int HW);
+int agan_mem_read_bwd(const float* h, const float* kv, const int64_t* mask, const float* rw, const float* rb, const float* attn,
+                      const float* dx, const float* dattn, float* dh, float* dkv, float* drw, float* drb, int B, int C, int T, int HW,
+                      int accumulate_rw, int accumulate_rb, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }
