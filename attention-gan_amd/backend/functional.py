@@ -1437,6 +1437,85 @@ def memory_read(h: Tensor, kv: Tensor, mask: Tensor, rw: Tensor, rb: Tensor) -> 
     return _MemoryReadFn.apply(_dev(h, "memory_read h"), _dev(kv, "memory_read kv"), mask, rw, rb, grad_dst(rw), grad_dst(rb))
 
 
+# --------------------------------------------------------------------------------------------------------------
+# channel-wise word attention of a refinement stage (networks/attention.py: ChannelAttention; include/agan.h: agan_chan_attn_*)
+# --------------------------------------------------------------------------------------------------------------
+def _chan_attn_dims(h: Tensor, wt: Tensor, mask: Tensor, what: str) -> Tuple[int, int, int, int, int]:
+    """-> (B, C, T, H, W) of h [B, C, H, W], wt [B, T, H * W] and mask [B, T], or ValueError"""
+    if h.dim() != 4 or wt.dim() != 3 or h.numel() == 0 or wt.numel() == 0:
+        raise ValueError(f"{what}: h must be [B, C, H, W] and wt [B, T, H * W], got {tuple(h.shape)} and {tuple(wt.shape)}")
+    B, C, H, W = (int(s) for s in h.shape)
+    T = int(wt.shape[1])
+    if int(wt.shape[0]) != B or int(wt.shape[2]) != H * W or tuple(mask.shape) != (B, T):
+        raise ValueError(f"{what}: h {tuple(h.shape)}, wt {tuple(wt.shape)} and mask {tuple(mask.shape)} do not fit "
+                         f"([B, C, H, W], [B, T, H * W], [B, T])")
+    return B, C, T, H, W
+
+
+def _chan_attn_scale(scale: Optional[float], hw: int) -> float:
+    return 1.0 / math.sqrt(hw) if scale is None else float(scale)
+
+
+def channel_attention_reference(h: Tensor, wt: Tensor, mask: Tensor, scale: Optional[float] = None) -> Tuple[Tensor, Tensor]:
+    """What channel_attention computes, in torch ops, in h's dtype, on any device, differentiable by autograd.  With p a pixel:
+
+        m[b, c, t] = scale * sum_p h[b, c, p] wt[b, t, p], -inf where mask[b, t] == 0      alpha = softmax_t m
+        f[b, c, p] = sum_t alpha[b, c, t] wt[b, t, p]
+
+    h [B, C, H, W], wt [B, T, H * W], mask [B, T], scale None = 1 / sqrt(H * W) -> (f [B, C, H, W], alpha [B, C, T])."""
+    B, C, T, H, W = _chan_attn_dims(h, wt, mask, "channel_attention_reference")
+    m = torch.bmm(h.reshape(B, C, H * W), wt.transpose(1, 2)) * _chan_attn_scale(scale, H * W)
+    alpha = torch.softmax(m.masked_fill(mask.to(h.device).view(B, 1, T) == 0, float("-inf")), dim=2)
+    return torch.bmm(alpha, wt).reshape(B, C, H, W), alpha
+
+
+class _ChannelAttentionFn(Function):
+    @staticmethod
+    def forward(ctx, h, wt, mask, scale):
+        B, C, T, H, W = _chan_attn_dims(h, wt, mask, "channel_attention")
+        m = mask.to(device=h.device, dtype=torch.int64).contiguous()
+        f = torch.empty_like(h)
+        alpha = torch.empty((B, C, T), dtype=torch.float32, device=h.device)
+        nbytes = L.load().agan_chan_attn_fwd_ws_bytes(B, C, T, H * W)
+        ws, wsp = _ws(nbytes, h)
+        L.call("agan_chan_attn_fwd", _p(h), _p(wt), _p(m), scale, _p(alpha), _p(f), B, C, T, H * W, wsp, nbytes, _stream())
+        ctx.save_for_backward(h, wt, alpha)
+        ctx.scale = scale
+        ctx.set_materialize_grads(False)     # alpha usually feeds nothing: no zero-filled gradient for it
+        return f, alpha
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, df, dalpha):
+        h, wt, alpha = ctx.saved_tensors
+        B, C, H, W = h.shape
+        T = wt.shape[1]
+        need_h, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if (df is None and dalpha is None) or not (need_h or need_w):
+            return None, None, None, None
+        df = _dev(df, "channel_attention df") if df is not None else torch.zeros_like(h)
+        dalpha = _dev(dalpha, "channel_attention dalpha") if dalpha is not None else None
+        dh = torch.empty_like(h) if need_h else None          # a NULL destination: the kernel computes nothing for it
+        dwt = torch.empty_like(wt) if need_w else None
+        nbytes = L.load().agan_chan_attn_bwd_ws_bytes(B, C, T, H * W)
+        ws, wsp = _ws(nbytes, h)
+        L.call("agan_chan_attn_bwd", _p(h), _p(wt), _p(alpha), _p(df), _p(dalpha), ctx.scale, _p(dh), _p(dwt), B, C, T, H * W, wsp, nbytes,
+               _stream())
+        return dh, dwt, None, None
+
+
+def channel_attention(h: Tensor, wt: Tensor, mask: Tensor, scale: Optional[float] = None) -> Tuple[Tensor, Tensor]:
+    """Channel-wise word attention on the HIP kernels (csrc/chan_attn.hip), fp32, with autograd; channel_attention_reference states
+    it in torch ops.  h [B, C, H, W] (C <= 64), wt [B, T, H * W] (the words seen through the perception layer, T <= 64), mask [B, T]
+    (0 = ignore the word), scale None = 1 / sqrt(H * W) -> (f [B, C, H, W], alpha [B, C, T]).  Three launches per direction; nothing of
+    the backward is computed for an input that needs no gradient."""
+    B, C, T, H, W = _chan_attn_dims(h, wt, mask, "channel_attention")
+    if get_activation_storage() != L.DT_F32 or any(t.dtype in _DT_OF for t in (h, wt)):
+        raise L.AganError("channel_attention: the channel-attention kernels are fp32 only; 16-bit activation storage "
+                          "(set_activation_storage) and 16-bit tensors are not built for them")
+    return _ChannelAttentionFn.apply(_dev(h, "channel_attention h"), _dev(wt, "channel_attention wt"), mask, _chan_attn_scale(scale, H * W))
+
+
 def spatial_mean(x: Tensor) -> Tensor:
     """mean over the positions of x [B, C, H, W] -> [B, C] on the HIP kernel (agan_global_avgpool_fwd), fp32.  NOT differentiable:
     the result is detached (the dynamic memory's write gate reads the image through it without a gradient)."""

@@ -204,6 +204,10 @@ _SIGNATURES = {
     "agan_mem_read_fwd": (c_int, [_P] * 7 + [c_int] * 4 + [_P]),
     "agan_mem_read_bwd_ws_bytes": (c_size_t, [c_int] * 4),
     "agan_mem_read_bwd": (c_int, [_P] * 12 + [c_int] * 6 + [_P, c_size_t, _P]),
+    "agan_chan_attn_fwd_ws_bytes": (c_size_t, [c_int] * 4),
+    "agan_chan_attn_fwd": (c_int, [_P] * 3 + [c_float, _P, _P] + [c_int] * 4 + [_P, c_size_t, _P]),
+    "agan_chan_attn_bwd_ws_bytes": (c_size_t, [c_int] * 4),
+    "agan_chan_attn_bwd": (c_int, [_P] * 5 + [c_float, _P, _P] + [c_int] * 4 + [_P, c_size_t, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

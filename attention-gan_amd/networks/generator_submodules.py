@@ -10,7 +10,7 @@ from torch import Tensor, nn
 from ..backend import functional as HF
 from ..backend import lib as L
 from ..utilities.layers import GLU, HipBatchNorm1d, HipConv2d, HipLinear, Layers, SelfAttention2d
-from .attention import AttentionModule
+from .attention import AttentionModule, ChannelAttention
 from .memory import DynamicMemory
 
 
@@ -74,15 +74,20 @@ class GenNextStage(nn.Module):
     `cond_bn_dim`: the upBlock's BatchNorm is conditional on a [B, cond_bn_dim] code that forward() then takes (not in the
     reference); the residual blocks' BatchNorms stay as they are.  `memory` (not in the reference): a DynamicMemory (networks/memory.py,
     keys `memory.*`, `memory_dim` wide) stands where the attention module and the concat stand -- the stage then has no `attention`
-    child, and the residual blocks run on the module's [B, 2 gf_dim, h, w] output."""
+    child, and the residual blocks run on the module's [B, 2 gf_dim, h, w] output.  `channel_attn_hw` (not in the reference): the side
+    of the stage's input map; a ChannelAttention (networks/attention.py, key `channel_attn.perception.weight` [hw * hw, emb_dim]) then
+    runs next to the attention module and the stage is cat(images, context, f) -> residual blocks of width 3 gf_dim ->
+    upBlock(3 gf_dim, gf_dim); the returned map is still the spatial one.  Not together with `memory`, which has its own channel plan."""
 
     def __init__(self, gf_dim: int, emb_dim: int, num_residual_blocks: int, cond_bn_dim: Optional[int] = None, memory: bool = False,
-                 memory_dim: Optional[int] = None):
+                 memory_dim: Optional[int] = None, channel_attn_hw: Optional[int] = None):
         super().__init__()
         self.gf_dim, self.emb_dim, self.num_residual_blocks, self.cond_bn_dim = gf_dim, emb_dim, num_residual_blocks, cond_bn_dim
-        self.use_memory, self.memory_dim = bool(memory), memory_dim
+        self.use_memory, self.memory_dim, self.channel_attn_hw = bool(memory), memory_dim, channel_attn_hw
         if memory_dim is not None and not self.use_memory:
             raise ValueError("memory_dim is the width of the dynamic memory: it needs memory=True")
+        if channel_attn_hw is not None and self.use_memory:
+            raise ValueError("channel_attn_hw and memory=True do not combine: the memory stage has its own channel plan")
         self.define_module()
 
     def define_module(self):
@@ -90,8 +95,12 @@ class GenNextStage(nn.Module):
             self.memory = DynamicMemory(nc_in=self.gf_dim, emb_dim=self.emb_dim, memory_dim=self.memory_dim)
         else:
             self.attention = AttentionModule(nc_in=self.gf_dim, emb_dim=self.emb_dim)
-        self.residual = self._make_layer(Layers.ResBlock, self.gf_dim * 2)
-        self.upsample = Layers.upBlock(self.gf_dim * 2, self.gf_dim, self.cond_bn_dim)
+        width = 2
+        if self.channel_attn_hw is not None:
+            self.channel_attn = ChannelAttention(nc_in=self.gf_dim, emb_dim=self.emb_dim, hw=self.channel_attn_hw)
+            width = 3
+        self.residual = self._make_layer(Layers.ResBlock, self.gf_dim * width)
+        self.upsample = Layers.upBlock(self.gf_dim * width, self.gf_dim, self.cond_bn_dim)
 
     def _make_layer(self, block, channel_num: int):
         return nn.Sequential(*[block(channel_num) for _ in range(self.num_residual_blocks)])
@@ -106,7 +115,12 @@ class GenNextStage(nn.Module):
         else:
             self.attention.apply_mask(mask=mask)
             context, attn = self.attention(images, word_embs)
-            x = self.residual(torch.cat((images, context), 1))
+            if self.channel_attn_hw is None:
+                x = self.residual(torch.cat((images, context), 1))
+            else:
+                self.channel_attn.apply_mask(mask=mask)
+                f, _ = self.channel_attn(images, word_embs)
+                x = self.residual(torch.cat((images, context, f), 1))
         if self.cond_bn_dim is None:
             return self.upsample(x), attn
         return self.upsample(x, condition), attn

@@ -19,9 +19,10 @@ class Generator4(Generator):
     """Generator with a 4th stage: returns 4 images (64, 128, 256, 512) and 3 attention maps."""
 
     def __init__(self, gf_dim: int, emb_dim: int, z_dim: int, cond_dim: int, cond_bn: bool = False, self_attn: Optional[int] = None,
-                 memory: bool = False, memory_dim: Optional[int] = None):
-        super().__init__(gf_dim, emb_dim, z_dim, cond_dim, cond_bn, _defer_self_attn=True, memory=memory, memory_dim=memory_dim)
-        self.gen4 = self._next_stage()
+                 memory: bool = False, memory_dim: Optional[int] = None, channel_attn: bool = False):
+        super().__init__(gf_dim, emb_dim, z_dim, cond_dim, cond_bn, _defer_self_attn=True, memory=memory, memory_dim=memory_dim,
+                         channel_attn=channel_attn)
+        self.gen4 = self._next_stage("gen4")
         self.img_out4 = GenMakeImage(gf_dim=gf_dim)
         self.gen1.add_self_attn(self_attn)         # last: see Generator
 

@@ -42,7 +42,7 @@ extern "C" {
  * Score's per-split reduction over classifier logits); the sentence-conditioned BatchNorm of the generator's up blocks (agan_cbn_*); the
  * pixel-to-pixel attention of the generator's self-attention block and its gate (agan_self_attn_*, agan_scaled_residual_*); the dynamic
  * memory of the generator's refinement stages (agan_mem_write_*, agan_mem_read_*), for which agan_act_fwd / agan_act_bwd also take
- * AGAN_ACT_RELU. */
+ * AGAN_ACT_RELU; the channel-wise word attention of those stages (agan_chan_attn_*). */
 
 enum {
     AGAN_OK = 0,
@@ -1014,6 +1014,31 @@ size_t agan_mem_read_bwd_ws_bytes(int B, int C, int T, int HW);
 int agan_mem_read_bwd(const float* h, const float* kv, const int64_t* mask, const float* rw, const float* rb, const float* attn,
                       const float* dx, const float* dattn, float* dh, float* dkv, float* drw, float* drb, int B, int C, int T, int HW,
                       int accumulate_rw, int accumulate_rb, void* ws, size_t ws_bytes, void* stream);
+
+/* ----------------------------------------------------------------------------------------------
+ * Channel-wise word attention of a refinement stage (csrc/chan_attn.hip; networks/attention.py: ChannelAttention; ControlGAN, Li et
+ * al., NeurIPS 2019).  fp32.  Every CHANNEL of h [B, C, HW] attends over the words, seen through wt [B, T, HW] (the perception layer's
+ * output, one HW-long row per word), with mask int64 [B, T] (0 = ignore the word) and p a pixel:
+ *     m[b, c, t] = scale * sum_p h[b, c, p] wt[b, t, p], -inf for a masked word      alpha[b, c, :] = softmax_t m[b, c, :]
+ *     f[b, c, p] = sum_t alpha[b, c, t] wt[b, t, p]                                  alpha [B, C, T]   f [B, C, HW]
+ *   Three launches: the scores on the fp32 matrix cores, one partial [C, T] slab per workgroup of 256 pixels in `ws`; the ordered sum
+ *   of the slabs with the softmax; the read, one pixel per lane.  A sample whose words are all masked gives NaN.
+ *   agan_chan_attn_bwd: from df [B, C, HW] and the optional dalpha_out [B, C, T] (NULL = zero; the gradient at the returned alpha) to
+ *     dalpha[b, c, t] = sum_p df[b, c, p] wt[b, t, p] (+ dalpha_out)        dm = alpha * (dalpha - sum_t alpha dalpha)
+ *     dh[b, c, p] = scale * sum_t dm[b, c, t] wt[b, t, p]                   dwt[b, t, p] = sum_c (alpha[b, c, t] df[b, c, p] + scale dm[b, c, t] h[b, c, p])
+ *   Three launches of the same forms.  One of dh and dwt may be NULL: that gradient is then neither computed nor stored.  `mask` is
+ *   not read (a masked word has alpha = 0 and takes no gradient).  No float atomics: two runs give the same bits.
+ * Domain: B, C, T, HW >= 1, C <= 64, T <= 64, B <= 65535, B * C * HW and B * T * HW below 2^31.  Anything else, or a null pointer
+ * (dalpha_out and one of dh / dwt excepted), is AGAN_EINVAL with the entry's name in agan_last_error() before any HIP call (the
+ * workspace queries then answer 0); a workspace below agan_chan_attn_{fwd,bwd}_ws_bytes is AGAN_EWORKSPACE.  Only enqueues on
+ * `stream`: no allocation, no synchronisation; graph-capturable.
+ * ---------------------------------------------------------------------------------------------- */
+size_t agan_chan_attn_fwd_ws_bytes(int B, int C, int T, int HW);
+int agan_chan_attn_fwd(const float* h, const float* wt, const int64_t* mask, float scale, float* alpha, float* f, int B, int C, int T,
+                       int HW, void* ws, size_t ws_bytes, void* stream);
+size_t agan_chan_attn_bwd_ws_bytes(int B, int C, int T, int HW);
+int agan_chan_attn_bwd(const float* h, const float* wt, const float* alpha, const float* df, const float* dalpha_out, float scale,
+                       float* dh, float* dwt, int B, int C, int T, int HW, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }
