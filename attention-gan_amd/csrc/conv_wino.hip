@@ -68,7 +68,8 @@ struct WinoTraits {
     int step, extra, origin;    // raw patch of a block of T tiles per dimension: step * T + extra rows / columns from input row step * t0 + origin (class form: + py / px)
     int cch;                    // input channels per chunk
     int planes, classes;        // transformed-weight planes [plane][Cin / 8][Nld][8] in the workspace; grid entries per block that share them out (parity classes)
-    int stages, nacc;           // 4-MFMA stages per chunk and wave; accumulator fragments per wave
+    int threads;                // threads of a workgroup: 256 = one wave per SIMD; 512 = two, the positions of a cout fragment split over the wave pair (w, w + 4)
+    int stages, nacc;           // 4-MFMA stages per chunk and wave (wave pair: of the longer wave); accumulator fragments of a cout fragment
     int vfrags;                 // V fragments [tile][8 channels] per chunk = stages of all the waves of a cout fragment
     int pieces;                 // input-transform pieces per 32-tile group and chunk
     int ni32, ni64;             // raw staging values per thread and chunk, 32- / 64-tile blocks (0: that block size is not built)
@@ -80,7 +81,7 @@ struct WinoTraits {
 };
 constexpr WinoTraits wino_traits(WinoKind k) {
     WinoTraits t{};
-    t.origin = -1; t.classes = 1; t.lds_cap = 160 * 1024; t.s_u_second = 0; t.s_raw_load = 1;
+    t.origin = -1; t.classes = 1; t.lds_cap = 160 * 1024; t.s_u_second = 0; t.s_raw_load = 1; t.threads = 256;
     switch (k) {
     case WinoKind::conv3x3:             // F(2x2, 3x3), a wave = all 16 positions of one cout fragment
         t.step = 2; t.extra = 2; t.cch = 8; t.planes = 16; t.stages = 16; t.nacc = 16; t.vfrags = 16; t.pieces = 4; t.ni32 = 7; t.ni64 = 11;
@@ -90,13 +91,15 @@ constexpr WinoTraits wino_traits(WinoKind k) {
         t.step = 2; t.extra = 2; t.cch = 8; t.planes = 16; t.stages = 8; t.nacc = 8; t.vfrags = 16; t.pieces = 4; t.ni32 = 7;
         t.s_u_next = 4; t.s_transform = 1; t.s_raw_store = 6; t.lds_cap = 80 * 1024; t.mulshift = true;
         break;
-    case WinoKind::conv4x4_s2:          // four phases of F(2x2, 2x2): 36 (phase, position) planes into 9 accumulators; built for 128-channel tiles
-        t.step = 4; t.extra = 2; t.cch = 8; t.planes = 36; t.stages = 36; t.nacc = 9; t.vfrags = 36; t.pieces = 4; t.ni32 = 21;
-        t.s_u_next = 18; t.s_transform = 2; t.s_raw_store = 32; t.store1_late = true;
+    case WinoKind::conv4x4_s2:          // four phases of F(2x2, 2x2): 36 (phase, position) planes into 9 accumulators; built for 128-channel tiles.
+                                        // Wave pair: waves 0-3 positions 0-4 of every phase (20 stages), waves 4-7 positions 5-8 (16)
+        t.step = 4; t.extra = 2; t.cch = 8; t.planes = 36; t.threads = 512; t.stages = 20; t.nacc = 9; t.vfrags = 36; t.pieces = 4; t.ni32 = 11;
+        t.s_transform = 2; t.s_raw_store = 14; t.store1_late = true;
         break;
-    case WinoKind::dgrad2x2_class:      // F(2x2, 2x2) per parity class, 16 channels per chunk: stage = (position, 8-channel half); 128-channel tiles
-        t.step = 2; t.extra = 1; t.cch = 16; t.planes = 36; t.classes = 4; t.stages = 18; t.nacc = 9; t.vfrags = 18; t.pieces = 2; t.ni32 = 11;
-        t.s_u_next = 9; t.s_transform = 2; t.s_raw_store = 15; t.store1_late = true;
+    case WinoKind::dgrad2x2_class:      // F(2x2, 2x2) per parity class, 16 channels per chunk = (position, 8-channel half); 128-channel tiles.
+                                        // Wave pair: waves 0-3 positions 0-4 of both octets (10 stages), waves 4-7 positions 5-8 (8)
+        t.step = 2; t.extra = 1; t.cch = 16; t.planes = 36; t.classes = 4; t.threads = 512; t.stages = 10; t.nacc = 9; t.vfrags = 18; t.pieces = 2; t.ni32 = 6;
+        t.s_transform = 2; t.s_raw_store = 7; t.store1_late = true;
         break;
     }
     return t;
@@ -149,22 +152,26 @@ __device__ __forceinline__ void wino_output_2x2(const f32x16 (&acc)[NACC], int r
 // whole product of its (tile, output channel) and the output transform never leaves its registers.  (The first version gave every wave
 // one nu of all cout fragments: the nu-direction of the output transform went through 64 KB of LDS and four barriers per workgroup -- with
 // one workgroup per CU that epilogue and the prologue were a third of its time.)  The half form splits the positions over the wave pair
-// (fw, hh) instead: see conv_wino_h_f32_kernel.
+// (fw, hh) instead: see conv_wino_h_f32_kernel.  The two F(2x2, 2x2) forms run 512 threads: the waves (fw, hh = 0 / 1) split the POSITIONS
+// of their cout fragment 5 + 4 and swap accumulator halves for the output transform -- see accumulate_pair / epilogue_pair.
 template <WinoKind K, int NTG>
 struct WinoGather {
     static constexpr WinoTraits T = wino_traits(K);
     static constexpr bool kHalf = K == WinoKind::conv3x3_half, kS2 = K == WinoKind::conv4x4_s2, kCls = K == WinoKind::dgrad2x2_class;
     static constexpr bool k3x3 = T.nacc != 9;
+    static constexpr int NT = T.threads;                           // threads of the workgroup
+    static constexpr bool kPair = NT == 512;                       // two waves per SIMD: waves w and w + 4 share the stages of a cout fragment (hh = w / 4)
     static constexpr int NFW = kHalf ? 2 : 4 / NTG;                // cout fragments per workgroup
     static constexpr int NTL = 32 * NTG, LT = NTG == 1 ? 5 : 6;    // tiles per workgroup, log2 of that
     static constexpr int NI = NTG == 1 ? T.ni32 : T.ni64;          // raw staging values per thread and chunk
     static constexpr int CCH = T.cch, C8 = T.cch / 8;              // channels / channel octets per chunk
     static constexpr int S = T.stages, SH = T.stages / 2, NACC = T.nacc;
-    static constexpr int NPIECE = T.pieces * NTG;
+    static constexpr int NPIECE = T.pieces * NTG * 256 / NT;       // input-transform pieces per thread and chunk
     static constexpr int VBUF = T.vfrags * NTL * 8;                // floats per V buffer
     static constexpr int STEP = T.step;
     static_assert(NI > 0, "this block size of the variant is not built: plan_wino must not route to it");
-    static_assert(T.s_u_next == SH && T.s_transform + NPIECE <= S && T.s_raw_store < S, "slots of the chunk loop");
+    static_assert((kPair || T.s_u_next == SH) && T.s_transform + NPIECE <= S && T.s_raw_store < S, "slots of the chunk loop");
+    static_assert(!kPair || (NTG == 1 && !k3x3), "wave pairs: the F(2x2, 2x2) forms on 32-tile blocks");
 
     const Geom& g;
     const WinoPlan& wp;
@@ -183,7 +190,7 @@ struct WinoGather {
         extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
         tid = threadIdx.x; lane = tid & 63;
         w = __builtin_amdgcn_readfirstlane(tid >> 6);
-        fw = w % NFW; tg = kHalf ? 0 : w / NFW; hh = kHalf ? w / NFW : 0;
+        fw = w % NFW; tg = kHalf || kPair ? 0 : w / NFW; hh = kHalf || kPair ? w / NFW : 0;
         l31 = lane & 31; lh = lane >> 5;
         ks = py = px = 0;
         {
@@ -218,8 +225,10 @@ struct WinoGather {
     __device__ __forceinline__ void stage_items(int (&it_off)[NI], unsigned (&it_lds)[NI]) const {
 #pragma unroll
         for (int i = 0; i < NI; ++i) {
-            const int e = tid + i * 256;
-            int col, row, t2;                                      // t2 = (image of the block, channel of the chunk)
+            // (wave pairs: a thread past the patch's last item takes the last item again -- the same value to the same place -- so that
+            //  neither the loads nor the LDS stores of the chunk loop need a per-item predicate)
+            const int e = kPair ? min(tid + i * NT, wp.raw_items - 1) : tid + i * NT;
+            int col, row, t2;                                // t2 = (image of the block, channel of the chunk)
             if constexpr (T.mulshift) {                            // e / d = (e * ceil(65536 / d)) >> 16: two VALU instructions instead of the ~12 of a
                 const int t1 = (int)(__umul24(e, wp.mpc) >> 16);   // general division; 24-bit multiplies are full rate
                 col = e - (int)__umul24(t1, PC);
@@ -234,7 +243,8 @@ struct WinoGather {
                 it_off[i] = ok ? (int)__umul24(b * g.Cin + ci, ihw) + iy * g.IW + ix : -1;
                 it_lds[i] = (unsigned)((int)__umul24(__umul24(t2, PR) + row, PCP) + col);
             } else {
-                it_off[i] = ok ? (b * g.Cin + ci) * ihw + iy * g.IW + ix : -1;
+                // wave pairs: the byte offset of the load, or kOOB (= -1), formed here once
+                it_off[i] = ok ? ((b * g.Cin + ci) * ihw + iy * g.IW + ix) * (kPair ? 4 : 1) : -1;
                 it_lds[i] = (unsigned)((t2 * PR + row) * PCP + col);
             }
         }
@@ -242,14 +252,16 @@ struct WinoGather {
 
     __device__ __forceinline__ void load_raw(const int (&it_off)[NI], int ch, float (&rv)[NI]) const {
 #pragma unroll
-        for (int i = 0; i < NI; ++i)
-            rv[i] = buf_load_s(rx, it_off[i] >= 0 ? (unsigned)it_off[i] * 4u : kOOB, (unsigned)((c_beg + ch) * CCH * ihw) * 4u);
+        for (int i = 0; i < NI; ++i) {
+            if constexpr (kPair) rv[i] = buf_load_s(rx, (unsigned)it_off[i], (unsigned)((c_beg + ch) * CCH * ihw) * 4u);
+            else rv[i] = buf_load_s(rx, it_off[i] >= 0 ? (unsigned)it_off[i] * 4u : kOOB, (unsigned)((c_beg + ch) * CCH * ihw) * 4u);
+        }
     }
     __device__ __forceinline__ void store_raw(const unsigned (&it_lds)[NI], int ch, const float (&rv)[NI]) const {      // chunk ch's patch -> raw buffer ch & 1
         float* const rb = raw + (ch & 1) * RAWBUF;
 #pragma unroll
         for (int i = 0; i < NI; ++i)
-            if (tid + i * 256 < wp.raw_items) rb[it_lds[i]] = rv[i];
+            if (kPair || tid + i * NT < wp.raw_items) rb[it_lds[i]] = rv[i];
     }
     // half a chunk's stages at a time, so that two register sets of SH fragments suffice.  Stage s of wave half hh: plane hh * S + s / C8,
     // channel octet s % C8 of the chunk (past the last chunk: a harmless repeat of it)
@@ -269,8 +281,9 @@ struct WinoGather {
     //      likewise; td keeps t between the pieces);  stride 2: one phase (p, q) -- every second row / column of the tile's 6 x 6 pixels;
     //      class form: one channel half ----
     __device__ __forceinline__ void transform_piece(const float* rb, float* Vb, int pi, float (&td)[NTG][4][4]) const {
-        const int k = pi / T.pieces, sub = pi % T.pieces;
-        const int tt = (tid >> 3) + 32 * k, ci = (tid & 7) + (kCls ? 8 * sub : 0);
+        // (wave pairs: threads 256 .. 511 -- waves 4 - 7, hh = 1 -- take the second half of the pieces: stride 2 phases 2, 3, class form channels 8 - 15)
+        const int k = kPair ? 0 : pi / T.pieces, sub = kPair ? hh * NPIECE + pi : pi % T.pieces;
+        const int tt = (kPair ? (tid >> 3) & 31 : tid >> 3) + 32 * k, ci = (tid & 7) + (kCls ? 8 * sub : 0);
         const int p = kS2 ? sub >> 1 : 0, q = kS2 ? sub & 1 : 0;
         if (!k3x3 || sub == 0) {
             const int ttx = tt & (TX - 1), tty = (tt >> txl) & (TY - 1), ttb = tt >> (txl + tyl);
@@ -363,6 +376,97 @@ struct WinoGather {
         }
     }
 
+    // ---- the same for a wave pair (512 threads, two waves per SIMD): waves (fw, hh = 0 / 1) split the POSITIONS of their cout fragment --
+    //      hh = 0 positions 0 - 4 (five accumulator fragments), hh = 1 positions 5 - 8 (four) -- and run every phase / channel octet of
+    //      theirs, in the order the one-wave form runs them: an accumulator sums the same products in the same order as before, so the
+    //      results are bit for bit what they were.  Stride 2: stage st = (phase st / NP, position P0 + st % NP); class form: (position
+    //      P0 + st / 2, channel octet st % 2).  Every thread stages half the raw items and transforms half the pieces.  A wave's own VALU
+    //      instructions are not hidden by its own MFMAs, its partner's are.  epilogue_pair exchanges accumulator halves. ----
+    template <int HH>
+    struct Half {
+        static constexpr int P0 = HH ? 5 : 0, NP = HH ? 4 : 5;      // this wave's positions: P0 .. P0 + NP - 1
+        static constexpr int SW = (kS2 ? 4 : 2) * NP, SWH = SW / 2; // stages per chunk of this wave; per weight register set
+        static constexpr int pos(int st) { return P0 + (kS2 ? st % NP : st / 2); }
+        static constexpr int sub(int st) { return kS2 ? st / NP : st % 2; }      // phase / channel octet of the stage
+    };
+    template <int HH>
+    __device__ __forceinline__ void load_u_half(int ch, int half, u32x4 (&uf)[Half<0>::SWH]) const {
+        using H = Half<HH>;
+        const unsigned ulane = (unsigned)(min(n0 + fw * 32 + l31, g.Nld - 1) * 32 + lh * 16);
+        const int c = c_beg + min(ch, nch - 1);
+#pragma unroll
+        for (int q = 0; q < H::SWH; ++q) {
+            const int st = half * H::SWH + q;
+            const int row = kS2 ? (H::sub(st) * 9 + H::pos(st)) * nch8 + c : H::pos(st) * nch8 + c * C8 + H::sub(st);      // (plane, channel octet)
+            uf[q] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rU, ulane, (unsigned)(row * g.Nld) * 32u, 0));
+        }
+    }
+    template <int HH>
+    __device__ __forceinline__ void accumulate_pair(f32x16 (&acc)[Half<0>::NP]) const {
+        using H = Half<HH>;
+        static_assert(T.s_transform + NPIECE <= Half<1>::SW && T.s_raw_store < Half<1>::SW && T.s_raw_load < T.s_raw_store, "slots of the chunk loop");
+        int it_off[NI];
+        unsigned it_lds[NI];
+        stage_items(it_off, it_lds);
+        float rawv[NI];
+        float td[NTG][4][4];              // (F(2x2, 3x3) only: unused here)
+        u32x4 ua[Half<0>::SWH], ub[Half<0>::SWH];      // weights of the first / second half of the stages, as in accumulate
+#pragma unroll
+        for (int q = 0; q < H::NP; ++q)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[q][r] = 0.f;
+        {   // prologue, as accumulate's with one raw register set
+            load_raw(it_off, 0, rawv);
+            load_u_half<HH>(0, 0, ua);
+            store_raw(it_lds, 0, rawv);
+            if (nch > 1) load_raw(it_off, 1, rawv);
+            lds_barrier_w();
+#pragma unroll
+            for (int pi = 0; pi < NPIECE; ++pi) transform_piece(raw, V, pi, td);
+            if (nch > 1) store_raw(it_lds, 1, rawv);
+            lds_barrier_w();
+        }
+        // V fragment of a stage: stride 2 fragment (phase, position), pitch NTL * 8; class form position (pitch NTL * 16), channel octet
+        const unsigned vlane = (unsigned)(l31 * CCH + lh * 4);
+        auto voff = [](int st) { return kS2 ? (H::sub(st) * 9 + H::pos(st)) * NTL * 8 : H::pos(st) * NTL * 16 + H::sub(st) * 8; };
+#pragma unroll 1
+        for (int ch = 0; ch < nch; ++ch) {
+            const float* Vc = V + (ch & 1) * VBUF + vlane;
+            float* Vn = V + ((ch + 1) & 1) * VBUF;
+            const float* rn = raw + ((ch + 1) & 1) * RAWBUF;
+            u32x4 vf[2];
+            vf[0] = *reinterpret_cast<const u32x4*>(Vc + voff(0));
+#pragma unroll
+            for (int st = 0; st < H::SW; ++st) {
+                if (st + 1 < H::SW) vf[(st + 1) & 1] = *reinterpret_cast<const u32x4*>(Vc + voff(st + 1));
+                if (st == 0) load_u_half<HH>(ch, 1, ub);
+                if (st == H::SWH) load_u_half<HH>(ch + 1, 0, ua);
+                // no branch around the other work (past the last chunk it loads the last patch again and transforms into the buffers nobody
+                // reads any more): one basic block per stage, so that the pieces can be issued BETWEEN the stage's four MFMAs (below)
+                if (st == T.s_raw_load) load_raw(it_off, min(ch + 2, nch - 1), rawv);
+                if (st >= T.s_transform && st < T.s_transform + NPIECE) transform_piece(rn, Vn, st - T.s_transform, td);
+                if (st == T.s_raw_store) store_raw(it_lds, ch + 2, rawv);
+                const u32x4 uf = st < H::SWH ? ua[st % H::SWH] : ub[st % H::SWH];
+                const int a = H::pos(st) - H::P0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    acc[a] = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(uf[j]), __uint_as_float(vf[st & 1][j]), acc[a], 0, 0, 0);
+                // a wave issues in order: what FOLLOWS four back-to-back MFMAs waits for all of them, what stands in front delays them.  The
+                // stage's other instructions are spread over the four 64-cycle shadows instead (as in conv_wino_wgrad_f32_kernel)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);          // MFMA
+                    __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);          // DS read
+                    __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);          // VALU
+                    __builtin_amdgcn_sched_group_barrier(0x020, 3, 0);          // VMEM read
+                    __builtin_amdgcn_sched_group_barrier(0x200, 3, 0);          // DS write
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            lds_barrier_w();
+        }
+    }
+
     // ---- output transform in registers, 2 x 2 pixels per lane and register: two 8-byte stores; class form: lattice point (yq, xq) -> pixel
     //      (2 yq + py, 2 xq + px), the four outputs lie two pixels apart (scalar stores) ----
     __device__ __forceinline__ void epilogue(const f32x16 (&acc)[NACC], float* out) const {
@@ -392,6 +496,76 @@ struct WinoGather {
                 __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2_, f32x2_{y[2], y[3]}), ro, ok ? off + (unsigned)g.OW * 4u : kOOB, 0, 0);
             }
         }
+    }
+
+    // ---- the epilogue of a wave pair: the output transform needs the nine positions of a (tile, cout) pair in one lane.  After the chunk
+    //      loop the operand buffers are dead: every wave leaves the half of its accumulators that its partner finishes (its positions x 8
+    //      registers, 16 bytes per lane and slot, at most 10 slots: 80 KB per workgroup) in LDS, ONE barrier, and the lower group
+    //      finishes registers 0 - 7 of the fragment, the upper group registers 8 - 15, with the additions of wino_output_2x2 in the
+    //      order they have there ----
+    template <int HH>
+    __device__ __forceinline__ void epilogue_pair(const f32x16 (&acc)[Half<0>::NP], float* out) const {
+        using H = Half<HH>;
+        using O = Half<1 - HH>;
+        typedef float f32x2_ __attribute__((ext_vector_type(2)));
+        typedef unsigned u32x2_ __attribute__((ext_vector_type(2)));
+        const int tx = l31 & (TX - 1), ty = (l31 >> txl) & (TY - 1), tb = l31 >> (txl + tyl);
+        const int b = tb0 + tb, oy = 2 * (ty0 + ty), ox = 2 * (tx0 + tx);
+        const bool pvalid = (b < g.B) & (oy < (kCls ? g.OHs : g.OH)) & (ox < (kCls ? g.OWs : g.OW));
+        const __amdgpu_buffer_rsrc_t ro = make_rsrc(out + (size_t)ks * wp.slab, (size_t)g.B * g.Cout * ohw * sizeof(float));
+        // lane part of the addresses once; the register's channel (r & 3) + 8 (r >> 2) goes into the scalar offset
+        const int nl = n0 + fw * 32 + 4 * lh;
+        const unsigned vp = pvalid ? (unsigned)((b * g.Cout + nl) * ohw + (kCls ? (2 * oy + py) * g.OW + 2 * ox + px : oy * g.OW + ox)) * 4u : kOOB;
+        f32x4* const X = reinterpret_cast<f32x4*>(raw);          // [wave 8][slot 10][lane 64]
+#pragma unroll
+        for (int q = 0; q < H::NP; ++q)
+#pragma unroll
+            for (int rq = 0; rq < 2; ++rq) {
+                f32x4 v;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = acc[q][8 * (1 - HH) + 4 * rq + e];
+                X[(w * 10 + q * 2 + rq) * 64 + lane] = v;
+            }
+        lds_barrier_w();
+#pragma unroll
+        for (int rq = 0; rq < 2; ++rq) {
+            f32x4 oth[O::NP];                                    // the partner's positions of registers 8 HH + 4 rq ... + 3
+#pragma unroll
+            for (int q = 0; q < O::NP; ++q) oth[q] = X[((w ^ 4) * 10 + q * 2 + rq) * 64 + lane];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int r = 8 * HH + 4 * rq + e;
+                float m[9];
+#pragma unroll
+                for (int p = 0; p < 9; ++p) m[p] = (p >= H::P0 && p < H::P0 + H::NP) ? acc[p - H::P0][r] : oth[p - O::P0][e];
+                float c0[3], c1[3];                              // wino_output_2x2's F(2x2, 2x2) form, term for term
+#pragma unroll
+                for (int nu = 0; nu < 3; ++nu) {
+                    c0[nu] = m[nu] + m[3 + nu];
+                    c1[nu] = m[3 + nu] + m[6 + nu];
+                }
+                const float y[4] = {c0[0] + c0[1], c0[1] + c0[2], c1[0] + c1[1], c1[1] + c1[2]};
+                const int dn = (r & 3) + 8 * (r >> 2);
+                const unsigned vo = nl + dn < g.Cout ? vp : kOOB;
+                const unsigned so = (unsigned)(dn * ohw) * 4u;
+                if constexpr (kCls) {
+                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, y[0]), ro, vo, so, 0);
+                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, y[1]), ro, vo, so + 8u, 0);
+                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, y[2]), ro, vo, so + (unsigned)(2 * g.OW) * 4u, 0);
+                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, y[3]), ro, vo, so + (unsigned)(2 * g.OW + 2) * 4u, 0);
+                } else {
+                    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2_, f32x2_{y[0], y[1]}), ro, vo, so, 0);
+                    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2_, f32x2_{y[2], y[3]}), ro, vo, so + (unsigned)g.OW * 4u, 0);
+                }
+            }
+        }
+    }
+    // one wave of the pair, start to end
+    template <int HH>
+    __device__ __forceinline__ void run_pair(float* out) const {
+        f32x16 acc[Half<0>::NP];
+        accumulate_pair<HH>(acc);
+        epilogue_pair<HH>(acc, out);
     }
 };
 
@@ -482,15 +656,17 @@ __global__ __launch_bounds__(256, 2) void conv_wino_h_f32_kernel(const float* __
 //     instead of 16:   B^T = [[1,-1,0],[0,1,0],[0,-1,1]],  G = [[1,0],[1,1],[0,1]],  A^T = [[1,1,0],[0,1,1]]  (all +-1: exact transforms
 //     up to the adds).  The output transform is the same for the four phases, so their products are summed in the SAME nine
 //     accumulators: 36 products per 2x2 outputs and input channel instead of 64.
-// 32 tiles x 128 output channels per workgroup, a wave = one cout fragment x all 9 positions (144 accumulator registers), input channels 8
-// at a time = 36 stages (phase, position); the raw patch of a tile is 6 x 6 pixels (rows / columns 4 t .. 4 t + 5 of the block's patch).
+// 32 tiles x 128 output channels per workgroup, input channels 8 at a time = 36 stages (phase, position); the raw patch of a tile is 6 x 6
+// pixels (rows / columns 4 t .. 4 t + 5 of the block's patch).  8 waves, two per SIMD: waves w and w + 4 share cout fragment w -- positions
+// 0-4 of the four phases in waves 0-3 (80 accumulator registers, 20 stages), positions 5-8 in waves 4-7 (64, 16 stages); every
+// accumulator sums its products in the order of the one-wave form -- and swap accumulator halves once, in the epilogue
+// (WinoGather::accumulate_pair / epilogue_pair).
 template <int NFW>
-__global__ __launch_bounds__(256, 1) void conv_wino_s2_f32_kernel(const float* __restrict__ x, const float* __restrict__ U, float* __restrict__ out,
+__global__ __launch_bounds__(512, 1) void conv_wino_s2_f32_kernel(const float* __restrict__ x, const float* __restrict__ U, float* __restrict__ out,
                                                                   const Geom g, const WinoPlan wp) {
     WinoGather<WinoKind::conv4x4_s2, 4 / NFW> k(x, U, g, wp);
-    f32x16 acc[k.NACC];
-    k.accumulate(acc);
-    k.epilogue(acc, out);
+    if (k.hh == 0) k.template run_pair<0>(out);
+    else k.template run_pair<1>(out);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -498,14 +674,14 @@ __global__ __launch_bounds__(256, 1) void conv_wino_s2_f32_kernel(const float* _
 // (include/agan.h: DY = -1, offsets (0, 1)).  Per class Winograd F(2x2, 2x2) on the class lattice: 9 products per 2x2 lattice points instead of
 // 16.  out[2 yq + py][2 xq + px] = sum_{r,s} Wc[r][s] dy[yq + py - r][xq + px - s] = correlation of the ascending window
 // (dy[yq + py - 1], dy[yq + py]) with g = (Wc[1], Wc[0]).  A channel chunk is 16 channels = 18 stages (position, 8-channel half); the
-// four classes are grid entries.
+// four classes are grid entries.  8 waves, two per SIMD: waves w and w + 4 share cout fragment w, positions 0-4 / 5-8 of both channel
+// octets (10 / 8 stages per wave), and swap accumulator halves in the epilogue as the stride-2 forward does.
 template <int NFW>
-__global__ __launch_bounds__(256, 1) void conv_wino_cls_f32_kernel(const float* __restrict__ x, const float* __restrict__ U, float* __restrict__ out,
+__global__ __launch_bounds__(512, 1) void conv_wino_cls_f32_kernel(const float* __restrict__ x, const float* __restrict__ U, float* __restrict__ out,
                                                                    const Geom g, const WinoPlan wp) {
     WinoGather<WinoKind::dgrad2x2_class, 4 / NFW> k(x, U, g, wp);
-    f32x16 acc[k.NACC];
-    k.accumulate(acc);
-    k.epilogue(acc, out);
+    if (k.hh == 0) k.template run_pair<0>(out);
+    else k.template run_pair<1>(out);
 }
 
 // (G g G^T) of a 2x2 kernel g, G = [[1,0],[1,1],[0,1]]: nine planes [xi * 3 + nu], `pp` floats apart from o on
@@ -886,9 +1062,10 @@ WinoPlan plan_wino(const Geom& g) {
     p.mpc = (65536 + PC - 1) / PC;
     p.mpr = (65536 + PR - 1) / PR;
     p.raw_items = TB * T.cch * PR * PC;
-    if (p.raw_items > (lt == 5 ? T.ni32 : T.ni64) * 256) return p;      // (the kernel's staging registers: WinoGather::NI)
+    if (p.raw_items > (lt == 5 ? T.ni32 : T.ni64) * T.threads) return p;      // (the kernel's staging registers: WinoGather::NI)
     p.raw_bytes = (TB * T.cch * PR * p.pcp * 4 + 15) & ~15;
     p.smem_bytes = 2 * p.raw_bytes + 2 * T.vfrags * (1 << lt) * 8 * 4;      // two raw patches, two V buffers
+    if (T.threads == 512) p.smem_bytes = std::max(p.smem_bytes, 8 * 10 * 64 * 16);     // the wave pairs' exchange of accumulator halves (WinoGather::epilogue_pair)
     if (p.smem_bytes > T.lds_cap) return p;
     p.u_bytes = ((size_t)T.planes * (g.Cin / 8) * g.Nld * 8 * sizeof(float) + 255) / 256 * 256;
     p.ws_bytes = p.u_bytes + (p.ksplit > 1 ? p.slab * p.ksplit * sizeof(float) : 0);
@@ -900,7 +1077,7 @@ namespace {
 template <auto Kernel, WinoKind K>
 void launch_gather_kernel(dim3 grid, const float* in, const float* U, float* out, const Geom& g, const WinoPlan& p, hipStream_t st) {
     allow_dynamic_lds<Kernel>(wino_traits(K).lds_cap);
-    AGAN_LAUNCH(Kernel, grid, dim3(256), (size_t)p.smem_bytes, st, in, U, out, g, p);
+    AGAN_LAUNCH(Kernel, grid, dim3(wino_traits(K).threads), (size_t)p.smem_bytes, st, in, U, out, g, p);
 }
 }  // namespace
 
