@@ -1925,6 +1925,114 @@ def sentence_loss(cnn_code, rnn_code, class_ids, gamma3, slambda, eps=1e-8, labe
 
 
 # --------------------------------------------------------------------------------------------------------------
+# word-level discriminator score (include/agan.h: agan_word_corr_*; csrc/word_corr.hip; ControlGAN section 3.2)
+# --------------------------------------------------------------------------------------------------------------
+def _word_corr_dims(regions: Tensor, words: Tensor, shift, what: str) -> Tuple[int, int, int, int]:
+    """-> (B, D, S, T) of regions [B, D, S] (or [B, D, h, w]) and words [B, D, T], or ValueError"""
+    if regions.dim() not in (3, 4):
+        raise ValueError(f"{what}: regions must be [B, D, S] or [B, D, h, w], got {tuple(regions.shape)}")
+    if words.dim() != 3 or words.shape[0] != regions.shape[0] or words.shape[1] != regions.shape[1]:
+        raise ValueError(f"{what}: words must be [{regions.shape[0]}, {regions.shape[1]}, T], got {tuple(words.shape)}")
+    if words.requires_grad:
+        raise ValueError(f"{what}: the words are constants of the score (the text encoder is frozen in the GAN step); detach them")
+    if regions.device != words.device:
+        raise ValueError(f"{what}: regions are on {regions.device}, words on {words.device}")
+    B, D = int(regions.shape[0]), int(regions.shape[1])
+    S, T = regions.numel() // max(B * D, 1), int(words.shape[2])
+    if B < 1 or D < 1 or S < 1 or T < 1:
+        raise ValueError(f"{what}: empty operand (B={B}, D={D}, S={S}, T={T})")
+    if isinstance(shift, bool) or not isinstance(shift, int) or not 0 <= shift < B:
+        raise ValueError(f"{what}: shift must be an integer in [0, B = {B}), got {shift!r}")
+    return B, D, S, T
+
+
+def word_corr_reference(regions: Tensor, words: Tensor, lens, shift: int = 0, gamma1: float = 4.0, gamma2: float = 5.0,
+                        eps: float = 1e-8) -> Tuple[Tensor, Tensor, Tensor]:
+    """What word_corr computes, line by line as include/agan.h states it, in torch ops, in the operands' dtype, on any device,
+    differentiable by autograd w.r.t. the regions: -> (p [B], r [B, T], g [B, T]).  `lens` is read on the host."""
+    B, D, S, T = _word_corr_dims(regions, words, shift, "word_corr_reference")
+    if regions.dtype != words.dtype:
+        raise ValueError(f"word_corr_reference: regions are {regions.dtype}, words {words.dtype}")
+    lens = [int(v) for v in torch.as_tensor(lens).reshape(-1).tolist()]
+    if len(lens) != B:
+        raise ValueError(f"word_corr_reference: lens must have one entry per caption (got {len(lens)} for {B})")
+    regions = regions.reshape(B, D, S)
+    ps, rs, gs = [], [], []
+    for b in range(B):
+        c = (b + shift) % B
+        Lc = min(lens[c], T)
+        w, n = words[c, :, :Lc].t(), regions[b]                              # w [L, D], n [D, S]
+        m = w @ n                                                            # m[l, s] = <w_l, n_s>
+        sbar = torch.softmax(m, dim=0)                                       # over the L words
+        alpha = torch.softmax(gamma1 * sbar, dim=1)                          # over the S regions
+        ctx = alpha @ n.t()                                                  # ctx_l = sum_s alpha[l, s] n_s
+        r = (ctx * w).sum(1) / (ctx.norm(dim=1) * w.norm(dim=1)).clamp(min=eps)
+        g = torch.softmax(w @ w.mean(0), dim=0)                              # <mean_k w_k, w_l>
+        ps.append((g * torch.sigmoid(gamma2 * r)).sum())
+        rs.append(torch.nn.functional.pad(r, (0, T - Lc)))
+        gs.append(torch.nn.functional.pad(g, (0, T - Lc)))
+    return torch.stack(ps), torch.stack(rs), torch.stack(gs)
+
+
+class _WordCorrFn(Function):
+    @staticmethod
+    def forward(ctx, regions, words, lens, shift, g1, g2, eps):
+        regions, words = _dev(regions, "word_corr regions"), _dev(words, "word_corr words")
+        B, D, S = regions.shape
+        T = words.shape[2]
+        lib = L.load()
+        n_save = lib.agan_word_corr_save_elems(B, D, T, S)
+        if n_save == 0:
+            raise L.AganError(f"word_corr: {lib.agan_last_error().decode()}")
+        dev = regions.device
+        p = torch.empty(B, dtype=torch.float32, device=dev)
+        r = torch.empty((B, T), dtype=torch.float32, device=dev)
+        g = torch.empty((B, T), dtype=torch.float32, device=dev)
+        save = torch.empty(n_save, dtype=torch.float32, device=dev)
+        L.call("agan_word_corr_fwd", _p(regions), _p(words), _p(lens), shift, g1, g2, eps, _p(p), _p(r), _p(g), _p(save), B, D, T, S,
+               _stream())
+        ctx.save_for_backward(regions, words, lens, save)
+        ctx.hp = (shift, g1, g2, eps)
+        ctx.mark_non_differentiable(r, g)
+        return p, r, g
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dp, _dr, _dg):
+        regions, words, lens, save = ctx.saved_tensors
+        B, D, S = regions.shape
+        T = words.shape[2]
+        shift, g1, g2, eps = ctx.hp
+        dregions = torch.empty_like(regions)
+        dp = _dev(dp, "word_corr d(p)")
+        nbytes = L.load().agan_word_corr_bwd_ws_bytes(B, D, T, S)
+        ws, wsp = _ws(nbytes, regions)
+        L.call("agan_word_corr_bwd", _p(regions), _p(words), _p(lens), shift, _p(save), _p(dp), g1, g2, eps, _p(dregions), B, D, T, S,
+               wsp, nbytes, _stream())
+        return dregions, None, None, None, None, None, None
+
+
+def word_corr(regions: Tensor, words: Tensor, lens, shift: int = 0, gamma1: float = 4.0, gamma2: float = 5.0,
+              eps: float = 1e-8) -> Tuple[Tensor, Tensor, Tensor]:
+    """The word-level discriminator's score on the HIP kernels (csrc/word_corr.hip), fp32, with autograd: regions [B, D, S] (or
+    [B, D, h, w]) and words [B, D, T], lens [B] -> (p [B], r [B, T], g [B, T]); image b is scored against caption (b + shift) mod B
+    (include/agan.h states the formulas, word_corr_reference restates them in torch ops).  One launch per direction; a device int64
+    `lens` is read by the kernels (no host round trip, HIP-graph capturable).  The gradient reaches the regions from p only: r and
+    g are non-differentiable, and the words are constants -- ValueError if they require grad.  ValueError too for CPU tensors
+    (word_corr_reference runs anywhere), mismatched shapes and a shift outside [0, B)."""
+    B, D, S, T = _word_corr_dims(regions, words, shift, "word_corr")
+    if not regions.is_cuda:
+        raise ValueError(f"word_corr: the operands are on {regions.device}; the kernels run on the GPU (word_corr_reference runs anywhere)")
+    if isinstance(lens, Tensor) and lens.is_cuda and lens.dtype == torch.int64:
+        lens = lens.contiguous()                           # already resident: no host round trip (HIP-graph capturable)
+    else:
+        lens = torch.as_tensor(lens).to(device=regions.device, dtype=torch.int64).contiguous()
+    if lens.numel() != B:
+        raise ValueError(f"word_corr: lens must have one entry per caption (got {lens.numel()} for {B})")
+    return _WordCorrFn.apply(regions.reshape(B, D, S), words, lens.reshape(-1), int(shift), float(gamma1), float(gamma2), float(eps))
+
+
+# --------------------------------------------------------------------------------------------------------------
 # fused Adam on a flat buffer
 # --------------------------------------------------------------------------------------------------------------
 def adam_step_(param: Tensor, grad: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor, step_state: Tensor, lr: float, beta1: float,

@@ -208,6 +208,10 @@ _SIGNATURES = {
     "agan_chan_attn_fwd": (c_int, [_P] * 3 + [c_float, _P, _P] + [c_int] * 4 + [_P, c_size_t, _P]),
     "agan_chan_attn_bwd_ws_bytes": (c_size_t, [c_int] * 4),
     "agan_chan_attn_bwd": (c_int, [_P] * 5 + [c_float, _P, _P] + [c_int] * 4 + [_P, c_size_t, _P]),
+    "agan_word_corr_save_elems": (c_size_t, [c_int] * 4),
+    "agan_word_corr_fwd": (c_int, [_P, _P, _P, c_int, c_float, c_float, c_float, _P, _P, _P, _P] + [c_int] * 4 + [_P]),
+    "agan_word_corr_bwd_ws_bytes": (c_size_t, [c_int] * 4),
+    "agan_word_corr_bwd": (c_int, [_P, _P, _P, c_int, _P, _P, c_float, c_float, c_float, _P] + [c_int] * 4 + [_P, c_size_t, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

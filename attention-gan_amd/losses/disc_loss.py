@@ -121,3 +121,26 @@ class StandardDiscLoss(DiscLoss):
             observe(p_real.detach())
         loss_real = bce(p_real, self.make_labels_for_real_imgs(p_real.shape[0], device=p_real.device))
         return (loss_fake + loss_real) / 2
+
+
+class WordLevelDiscLoss:
+    """The word-level discriminator's loss (ControlGAN's word-level terms in this project's non-saturating log form with its 1e-8
+    guards), p = networks.discriminators.WordLevelDisc:
+
+        m(-log(p(x, c) + 1e-8)) + (m(-log(1 - p(x, c') + 1e-8)) + m(-log(1 - p(G, c) + 1e-8))) / 2,     m = mean over B
+
+    x the real images' regions, G the fakes', c the captions and c' the cyclic mismatch (image b with caption (b + 1) mod B, the
+    pairs ConditionalDiscLoss uses).  The perception layer runs ONCE over [real; fake]: the real rows feed both real terms.  The
+    log terms are stock ATen elementwise ops on [B] probabilities: deterministic, and capturable."""
+
+    def get_loss(self, word_disc: Module, fake_regions: Tensor, real_regions: Tensor, words: Tensor, lens) -> Tensor:
+        b = real_regions.shape[0]
+        if b < 2:
+            raise ValueError("WordLevelDiscLoss: the mismatched pairs need at least 2 captions")
+        if fake_regions.shape != real_regions.shape:
+            raise ValueError(f"WordLevelDiscLoss: real regions {tuple(real_regions.shape)}, fake regions {tuple(fake_regions.shape)}")
+        n = word_disc.perceive(torch.cat([real_regions, fake_regions], dim=0))
+        p_real = word_disc.score(n[:b], words, lens, 0)[0]
+        p_wrong = word_disc.score(n[:b], words, lens, 1)[0]
+        p_fake = word_disc.score(n[b:], words, lens, 0)[0]
+        return (-torch.log(p_real + 1e-8)).mean() + ((-torch.log(1 - p_wrong + 1e-8)).mean() + (-torch.log(1 - p_fake + 1e-8)).mean()) / 2

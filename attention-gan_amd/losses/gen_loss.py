@@ -50,3 +50,11 @@ class StandardGenLoss(GenLoss):
             fake_images = augment(fake_images)
         p = discriminator(fake_images)
         return torch.nn.functional.binary_cross_entropy(p, self.make_labels_for_real_imgs(p.shape[0], device=p.device))
+
+
+class WordLevelGenLoss:
+    """m(-log(p(G, c) + 1e-8)): the generator's term against the word-level discriminator (networks.discriminators.WordLevelDisc),
+    on the fakes' region features and the matching captions."""
+
+    def get_loss(self, word_disc: Module, fake_regions: Tensor, words: Tensor, lens) -> Tensor:
+        return (-torch.log(word_disc(fake_regions, words, lens, 0) + 1e-8)).mean()

@@ -200,3 +200,49 @@ class Disc256(_Disc):
     def features(self, X: Tensor) -> Tensor:
         x = self.img_code_s64(self.img_code_s32(self.img_code_s16(X)))
         return self.img_code_s64_2(self.img_code_s64_1(x))
+
+
+class WordLevelDisc(nn.Module):
+    """ControlGAN's word-level discriminator (Li et al., NeurIPS 2019, section 3.2; not in the reference): how well every WORD of a
+    caption is shown by the regions of an image, pooled into one probability per (image, caption) pair.
+
+    regions [B, nef, h, w] are the frozen image encoder's region features, words [B, nef, T] the frozen text encoder's word
+    embeddings, lens [B] the caption lengths.  `perception` (the paper's F', a bias-free 1x1 conv on the image side, the module's only
+    parameter: key `perception.weight`) starts as the IDENTITY, so that at step 0 the score is the pretrained encoders' own
+    word-region correlation and not noise.  Then backend.functional.word_corr (include/agan.h states the formulas): func_attention of
+    the words over the perceived regions, the cosine r_l of every word with its context, the word self-attention weight g_l, and
+    p = sum_l g_l sigmoid(gamma2 r_l) in (0, 1).  Image b is scored against caption (b + shift) mod B: shift 0 the matching pairs,
+    shift 1 the cyclic mismatched ones.  One departure from the paper, whose self-attention weight multiplies the context before the
+    (scale-invariant) cosine and so cancels: here it weights the word's term of the pooled score.
+
+    The gradient reaches the regions and `perception.weight`; the words are constants (ValueError if they require grad).  CUDA
+    tensors run the HIP kernels (h * w <= 320, nef <= 320, T <= 32, B <= 128); CPU tensors run word_corr_reference on stock ops."""
+
+    def __init__(self, nef: int, gamma1: float = 4.0, gamma2: float = 5.0):
+        super().__init__()
+        if isinstance(nef, bool) or not isinstance(nef, int) or nef < 1:
+            raise ValueError(f"nef={nef!r}: the embedding width, a positive integer")
+        self.nef, self.gamma1, self.gamma2 = nef, float(gamma1), float(gamma2)
+        self.perception = Layers.conv1x1(nef, nef)
+        with torch.no_grad():
+            self.perception.weight.copy_(torch.eye(nef).view(nef, nef, 1, 1))
+
+    def perceive(self, regions: Tensor) -> Tensor:
+        """F'(regions): [k, nef, h, w] -> [k, nef, h, w]"""
+        if regions.dim() != 4 or regions.shape[1] != self.nef:
+            raise ValueError(f"WordLevelDisc: regions must be [B, {self.nef}, h, w], got {tuple(regions.shape)}")
+        if regions.is_cuda:
+            return self.perception(regions)
+        return torch.nn.functional.conv2d(regions, self.perception.weight)
+
+    def score(self, perceived: Tensor, words: Tensor, lens, shift: int = 0):
+        """(p, r, g) from regions that went through `perceive` already (the discriminator loss scores the real batch twice)"""
+        fn = HF.word_corr if perceived.is_cuda else HF.word_corr_reference
+        return fn(perceived, words, lens, shift, self.gamma1, self.gamma2)
+
+    def correlations(self, regions: Tensor, words: Tensor, lens, shift: int = 0):
+        """-> (p [B], r [B, T], g [B, T]): the score, the per-word cosines and the word weights (0 beyond a caption's length)"""
+        return self.score(self.perceive(regions), words, lens, shift)
+
+    def forward(self, regions: Tensor, words: Tensor, lens, shift: int = 0) -> Tensor:
+        return self.correlations(regions, words, lens, shift)[0]

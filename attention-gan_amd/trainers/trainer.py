@@ -17,8 +17,8 @@ from torch.nn import Module
 from ..augment import GEO_UNIFORMS, AdaController, parse_geometry, parse_policy
 from ..backend import functional as HF
 from ..dataparallel import GradBuckets, any_rank, averaged_buffers, broadcast_module_, rank_of, world_size
-from ..losses.disc_loss import ConditionalDiscLoss, NonSaturatingDiscLoss
-from ..losses.gen_loss import ConditionalGenLoss, NonSaturatingGenLoss
+from ..losses.disc_loss import ConditionalDiscLoss, NonSaturatingDiscLoss, WordLevelDiscLoss
+from ..losses.gen_loss import ConditionalGenLoss, NonSaturatingGenLoss, WordLevelGenLoss
 from ..losses.KL_loss import KL_loss
 from ..losses.sentence_loss import SentenceLoss
 from ..losses.words_loss import WordsLoss
@@ -198,6 +198,18 @@ class GanTrainStep(ModelTrainer):
     and capture_segments() alike; `augment`, `geometry`, `augment_p` / `ada_target` (fed the UNCONDITIONAL real scores), `ema` and
     torch.distributed work unchanged, and checkpoints need nothing new: the head's parameters live in the discriminators' state_dict
     (AttnGAN's keys) and flat optimisers.  With False (default) no module, launch, random draw or result key is added.
+
+    `word_disc`: ControlGAN's word-level discriminator (networks.discriminators.WordLevelDisc; needs `image_encoder`, ValueError
+    otherwise), with `word_lambda` the weight of its term in the generator's loss.  It is broadcast like the other modules and has its
+    own FlatAdam (the discriminators' lr and betas) and GradBuckets.  One more phase, after the image discriminators' updates and before
+    the generator's: the regions of real_imgs[-1] and of fakes[-1].detach() come from the frozen encoder under no_grad, then
+    losses.disc_loss.WordLevelDiscLoss, backward, exchange and the optimiser step (observer tag "DW"; result "dw_loss").  In the
+    generator update the regions the DAMSM branch computes anyway also go through the (frozen) module and word_lambda *
+    losses.gen_loss.WordLevelGenLoss joins the total (result "gw_loss").  Eager step, capture() and capture_segments() -- two more
+    graphs, DW backward and DW Adam -- alike; `conditional`, `augment`, `geometry`, `ada_target`, `ema` and torch.distributed work
+    unchanged, and the encoder, hence this discriminator, sees un-augmented images as the DAMSM branch does.  state_dict() carries
+    "word_disc" and "word_optim"; a checkpoint without them loads: the module stays as it is and its optimiser starts fresh.  With None
+    (default) no module, launch, random draw, result key or checkpoint key is added.
     """
 
     def __init__(self, generator: Module, discriminators: Sequence[Module], image_encoder: Optional[Callable] = None,
@@ -205,8 +217,11 @@ class GanTrainStep(ModelTrainer):
                  wlambda: float = 5.0, slambda: float = 5.0, bucket_bytes: int = 64 << 20, group=None, seed: int = 0,
                  g_bucket_bytes: Optional[int] = None, augment: Optional[str] = None, ema: Optional[float] = None,
                  ema_warmup: bool = True, augment_p: Optional[float] = None, ada_target: Optional[float] = None, ada_interval: int = 4,
-                 ada_kimg: float = 500.0, ada_p_max: float = 1.0, geometry: Optional[str] = None, conditional: bool = False):
+                 ada_kimg: float = 500.0, ada_p_max: float = 1.0, geometry: Optional[str] = None, conditional: bool = False,
+                 word_disc: Optional[Module] = None, word_lambda: float = 1.0):
         super().__init__()
+        if word_disc is not None and image_encoder is None:
+            raise ValueError("GanTrainStep: word_disc scores the image encoder's region features: it needs image_encoder")
         if conditional and any(getattr(d, "COND_DNET", None) is None for d in discriminators):
             raise ValueError("GanTrainStep: conditional=True needs every discriminator built with cond_dim=<sentence-embedding width> "
                              "(networks.discriminators: COND_DNET)")
@@ -226,7 +241,8 @@ class GanTrainStep(ModelTrainer):
         self.geometry = parse_geometry(geometry)            # bit mask of the geometric stages; 0 = no warp
         self.G, self.Ds, self.image_encoder = generator, list(discriminators), image_encoder
         self.group = group
-        for m in [self.G] + self.Ds:
+        self.word_disc, self.word_lambda = word_disc, float(word_lambda)
+        for m in [self.G] + self.Ds + ([word_disc] if word_disc is not None else []):
             broadcast_module_(m, 0, group)
         # noise and the CA-net's eps come from a generator of this object, seeded per RANK: replicas share the initial weights
         # (broadcast above) but must draw different z / eps for their different captions
@@ -247,6 +263,10 @@ class GanTrainStep(ModelTrainer):
         # 8 MB buckets instead, so all but the last travel under the ~10 ms of backward that remain
         self.g_buckets = GradBuckets(self.g_opt, min(bucket_bytes, 8 << 20) if g_bucket_bytes is None else g_bucket_bytes, group)
         self.d_buckets = [GradBuckets(o, bucket_bytes, group) for o in self.d_opts]
+        # the word-level discriminator: an optimiser and buckets of its own, like every other discriminator
+        self.w_opt = FlatAdam(word_disc.parameters(), lr=disc_lr, betas=(0.5, 0.999)) if word_disc is not None else None
+        self.w_buckets = GradBuckets(self.w_opt, bucket_bytes, group) if word_disc is not None else None
+        self.word_disc_loss, self.word_gen_loss = WordLevelDiscLoss(), WordLevelGenLoss()
         # issue order of the three independent discriminator updates: LARGEST first (Disc256: 273 MB of gradients, the long pole of
         # the exchange), so that its buckets travel while the smaller discriminators still compute.  Results do not depend on it.
         self.d_order = sorted(range(len(self.Ds)), key=lambda i: -self.d_opts[i].numel)
@@ -311,6 +331,10 @@ class GanTrainStep(ModelTrainer):
         if streams is not None:
             for st in streams:
                 main.wait_stream(st)
+        # ---- word-level discriminator update: after the image discriminators', before the generator's ----
+        if self.word_disc is not None:
+            self._dw_backward(fw, word_embs, lengths, real_imgs, out, arm=True)
+            self._apply("DW", self.w_opt, self.w_buckets.finish())
         # ---- generator update (train.py:132-151) ----
         self._g_backward(fw, word_embs, sent_embs, lengths, class_ids, out, streams, arm=True)
         self._apply("G", self.g_opt, self.g_buckets.finish())
@@ -396,6 +420,19 @@ class GanTrainStep(ModelTrainer):
         loss.backward()
         out[f"d_loss{i}"] = loss.detach()
 
+    def _dw_backward(self, fw: "_Forward", word_embs, lengths, real_imgs, out: Dict[str, Tensor], arm: bool = False) -> None:
+        """The word-level discriminator's gradients on the current stream: regions of the largest real and fake images from the frozen
+        encoder (un-augmented, no graph), then WordLevelDiscLoss."""
+        self.w_opt.zero_grad()
+        if arm:
+            self.w_buckets.arm()
+        with torch.no_grad():
+            real_regions, _ = self.image_encoder(real_imgs[-1])
+            fake_regions, _ = self.image_encoder(fw.fakes[-1].detach())
+        loss = self.word_disc_loss.get_loss(self.word_disc, fake_regions, real_regions, word_embs.detach(), lengths)
+        loss.backward()
+        out["dw_loss"] = loss.detach()
+
     def _observe(self, i: int, score: Tensor) -> None:
         if self.on_real_scores is not None:
             self.on_real_scores(i, score)
@@ -409,7 +446,8 @@ class GanTrainStep(ModelTrainer):
         if arm:
             self.g_buckets.arm()
         main = torch.cuda.current_stream() if streams is not None else None
-        for d in self.Ds:
+        frozen = self.Ds + ([self.word_disc] if self.word_disc is not None else [])
+        for d in frozen:
             d.requires_grad_(False)
         try:
             # adversarial terms: one stream per discriminator again (forward here, autograd replays the dgrad chains on the same
@@ -430,6 +468,10 @@ class GanTrainStep(ModelTrainer):
                         sl = self.sent_loss.get_loss(code, sent_embs, fw.labels, class_ids)
                         terms += [wl, sl]
                         out["w_loss"], out["s_loss"] = wl.detach(), sl.detach()
+                        if self.word_disc is not None:      # the same regions through the frozen word-level discriminator
+                            gw = self.word_gen_loss.get_loss(self.word_disc, regions, word_embs.detach(), lengths)
+                            terms.append(gw * self.word_lambda)
+                            out["gw_loss"] = gw.detach()
             if streams is not None:
                 for st in streams:
                     main.wait_stream(st)
@@ -441,7 +483,7 @@ class GanTrainStep(ModelTrainer):
             out["kl"], out["g_total"] = kl.detach(), total.detach()
             total.backward()
         finally:
-            for d in self.Ds:
+            for d in frozen:
                 d.requires_grad_(True)
 
     def _apply(self, tag: str, opt: FlatAdam, scale: float) -> None:
@@ -499,7 +541,7 @@ class GanTrainStep(ModelTrainer):
     def _mark_replayed(self) -> None:
         """A replayed graph ran every Adam step and the averaging update without their host code: say what adam_step_ and ema_update_
         say, or the next EAGER use of a network (generate_images, step) runs on packs of the weights from before the replay."""
-        for holder in [self.g_opt, self.g_ema] + self.d_opts:
+        for holder in [self.g_opt, self.g_ema, self.w_opt] + self.d_opts:
             if holder is not None:
                 HF.mark_flat_written(holder.flat)
 
@@ -507,7 +549,8 @@ class GanTrainStep(ModelTrainer):
     def capture_segments(self, word_embs: Tensor, sent_embs: Tensor, lengths: Tensor, real_imgs: Sequence[Tensor], warmup: int = 2,
                          noise: Optional[Tensor] = None, eps: Optional[Tensor] = None, aug_u: Optional[Tensor] = None,
                          aug_q: Optional[Tensor] = None, aug_g: Optional[Tensor] = None) -> "SegmentedStep":
-        """The train step as NINE HIP graphs with the gradient exchange launched between them -- the form for world_size > 1, where
+        """The train step as NINE HIP graphs (eleven with `word_disc`: its backward and its Adam step, replayed on the main stream between
+        the discriminators' and the generator's) with the gradient exchange launched between them -- the form for world_size > 1, where
         the whole-step graph of capture() cannot be used (the RCCL collectives are not captured) and an eager step costs every rank
         ~11 ms of Python per 27 ms step on host cores the 8 ranks share:
 
@@ -531,7 +574,7 @@ class GanTrainStep(ModelTrainer):
         # the one-rank nccl rehearsal, round 3)
         mode = "thread_local"
         seg = SegmentedStep(self)
-        buckets = [self.g_buckets] + self.d_buckets
+        buckets = [self.g_buckets] + self.d_buckets + ([self.w_buckets] if self.w_buckets is not None else [])
         armed = [bk._armed for bk in buckets]
         for bk in buckets:
             bk._armed = False                              # no hook-driven collectives inside a capture
@@ -557,6 +600,16 @@ class GanTrainStep(ModelTrainer):
                 with torch.cuda.graph(ga, pool=d_pools[i], capture_error_mode=mode):
                     opt.step(self.d_buckets[i].scale)
                 seg.d_backward[i], seg.d_adam[i] = gb, ga
+            # ---- word-level discriminator update: runs alone between the discriminators and the generator, in the shared pool ----
+            if self.word_disc is not None:
+                gwb = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(gwb, pool=pool, capture_error_mode=mode):
+                    self._dw_backward(fw, word_embs, lengths, real_imgs, out)
+                    self.w_opt.join_and_rebind()
+                gwa = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(gwa, pool=pool, capture_error_mode=mode):
+                    self.w_opt.step(self.w_buckets.scale)
+                seg.dw_backward, seg.dw_adam = gwb, gwa
             # ---- generator update: one stream, no class ids (as in the warm-up steps) ----
             gg = torch.cuda.CUDAGraph()
             with torch.cuda.graph(gg, pool=pool, capture_error_mode=mode):
@@ -604,6 +657,8 @@ class GanTrainStep(ModelTrainer):
             averaged.append((self.G_ema, sd["generator_ema"]))
         if self.ada is not None and self.ada.adaptive:
             sd["ada"] = self.ada.state_dict()              # (one host read; single-process by construction)
+        if self.word_disc is not None:                     # (no buffers: nothing to average over the ranks)
+            sd["word_disc"], sd["word_optim"] = self.word_disc.state_dict(), self.w_opt.state_dict()
         if all_ranks and w > 1:
             import torch.distributed as dist
             for m, msd in averaged:
@@ -655,6 +710,16 @@ class GanTrainStep(ModelTrainer):
                 self.ada.load_state_dict(sd["ada"])
             else:
                 self.ada.reset()                           # a checkpoint of a run without adaptation: p at its initial value
+        if self.word_disc is not None:
+            if "word_disc" in sd and "word_optim" in sd:
+                self.word_disc.load_state_dict(sd["word_disc"])
+                self.w_opt.load_state_dict(sd["word_optim"])
+            else:                                          # a checkpoint of a run without the module: it stays as it is, its optimiser starts fresh
+                with torch.no_grad():
+                    self.w_opt.exp_avg.zero_()
+                    self.w_opt.exp_avg_sq.zero_()
+                    self.w_opt.step_state.zero_()
+                self.w_opt.step_count = 0
         for d, o, ds, os_ in zip(self.Ds, self.d_opts, sd["discriminators"], sd["d_optims"]):
             d.load_state_dict(ds)
             o.load_state_dict(os_)
@@ -768,6 +833,7 @@ class SegmentedStep:
         self.d_backward: Dict[int, object] = {}
         self.d_adam: Dict[int, object] = {}
         self.g_backward = self.g_adam = None
+        self.dw_backward = self.dw_adam = None              # with a word-level discriminator only
         self.out: Dict[str, Tensor] = {}
 
     def replay(self) -> Dict[str, Tensor]:
@@ -782,6 +848,10 @@ class SegmentedStep:
                 self.d_adam[i].replay()
         for st in streams:
             main.wait_stream(st)
+        if self.dw_backward is not None:
+            self.dw_backward.replay()
+            t.w_buckets.exchange_all()
+            self.dw_adam.replay()
         self.g_backward.replay()
         t.g_buckets.exchange_all()
         self.g_adam.replay()

@@ -42,7 +42,8 @@ extern "C" {
  * Score's per-split reduction over classifier logits); the sentence-conditioned BatchNorm of the generator's up blocks (agan_cbn_*); the
  * pixel-to-pixel attention of the generator's self-attention block and its gate (agan_self_attn_*, agan_scaled_residual_*); the dynamic
  * memory of the generator's refinement stages (agan_mem_write_*, agan_mem_read_*), for which agan_act_fwd / agan_act_bwd also take
- * AGAN_ACT_RELU; the channel-wise word attention of those stages (agan_chan_attn_*). */
+ * AGAN_ACT_RELU; the channel-wise word attention of those stages (agan_chan_attn_*); the word-level
+ * discriminator's word-region correlation score (agan_word_corr_*). */
 
 enum {
     AGAN_OK = 0,
@@ -1039,6 +1040,41 @@ int agan_chan_attn_fwd(const float* h, const float* wt, const int64_t* mask, flo
 size_t agan_chan_attn_bwd_ws_bytes(int B, int C, int T, int HW);
 int agan_chan_attn_bwd(const float* h, const float* wt, const float* alpha, const float* df, const float* dalpha_out, float scale,
                        float* dh, float* dwt, int B, int C, int T, int HW, void* ws, size_t ws_bytes, void* stream);
+
+/* ----------------------------------------------------------------------------------------------
+ * Word-level discriminator score (csrc/word_corr.hip; networks/discriminators.py: WordLevelDisc; ControlGAN, Li et al., NeurIPS
+ * 2019, section 3.2).  fp32.
+ *   regions [B, D, S]: the image regions after the perception layer.  words [B, D, T].  lens [B] int64 on the device.
+ *   shift, an integer in [0, B); gamma1, gamma2, eps.
+ * Image b is paired with caption c = (b + shift) mod B: shift = 0 gives the matching pairs, shift = 1 the cyclic mismatched pairs
+ * that ConditionalDiscLoss already uses.  With L = min(lens[c], T), w_l = words[c, :, l] for l < L and n_s = regions[b, :, s]:
+ *     m[l, s]     = <w_l, n_s>
+ *     sbar[l, s]  = softmax over l of m[., s]                  (over the L words)
+ *     alpha[l, s] = softmax over s of gamma1 * sbar[l, .]      (over the S regions)
+ *     ctx_l       = sum_s alpha[l, s] n_s
+ *     r_l         = <ctx_l, w_l> / max(|ctx_l| |w_l|, eps)     (WordsLoss.cosine_similarity's clamp)
+ *     g_l         = softmax over l of <mean_k w_k, w_l>        (word-level self-attention, mean over the L words)
+ *     p_b         = sum_l g_l * sigmoid(gamma2 * r_l)
+ * m, sbar, alpha and ctx are func_attention as above, without its 1 / sqrt(D).  One departure from the paper and its released code,
+ * where the self-attention weight multiplies ctx_l BEFORE the cosine: the cosine is scale-invariant, so there the weight cancels;
+ * here it weights word l's term of the pooled score.  p_b lies in (0, 1) because the weights sum to 1.
+ *   Outputs: p [B]; r [B, T] and g [B, T], written as 0 for l >= L.  words[c, :, l >= L] is never read.  lens[c] <= 0 gives p_b = 0.
+ *   agan_word_corr_fwd also leaves the per-word statistics the backward needs in `save` (agan_word_corr_save_elems floats).
+ *   agan_word_corr_bwd: dregions [B, D, S] from dp [B] only.  The words are constants (the text encoder is frozen in the GAN step, and
+ *   g depends on nothing else).  It recomputes m, alpha and ctx from `regions`; every image is in exactly one pair, so dregions[b] has
+ *   one owner: no atomics, no workspace (agan_word_corr_bwd_ws_bytes answers 0; `ws` may be NULL), the same bits every run.
+ * One launch per direction, one workgroup per pair, every contraction on the fp32 matrix cores; `lens` is read on the device: no
+ * host synchronisation, no allocation, graph-capturable.
+ * Domain (the DAMSM entries'): B in [1, 128], D and S in [1, 320], T in [1, 32], shift in [0, B).  Outside it, or with a null pointer,
+ * every entry answers AGAN_EINVAL before touching the device; the size queries answer 0 and set agan_last_error().
+ * ---------------------------------------------------------------------------------------------- */
+size_t agan_word_corr_save_elems(int B, int D, int T, int S);
+int agan_word_corr_fwd(const float* regions, const float* words, const int64_t* lens, int shift, float gamma1, float gamma2, float eps,
+                       float* p, float* r, float* g, float* save, int B, int D, int T, int S, void* stream);
+size_t agan_word_corr_bwd_ws_bytes(int B, int D, int T, int S);
+int agan_word_corr_bwd(const float* regions, const float* words, const int64_t* lens, int shift, const float* save, const float* dp,
+                       float gamma1, float gamma2, float eps, float* dregions, int B, int D, int T, int S, void* ws, size_t ws_bytes,
+                       void* stream);
 
 #ifdef __cplusplus
 }
