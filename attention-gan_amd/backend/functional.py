@@ -2033,6 +2033,121 @@ def word_corr(regions: Tensor, words: Tensor, lens, shift: int = 0, gamma1: floa
 
 
 # --------------------------------------------------------------------------------------------------------------
+# spectral normalisation of a weight (include/agan.h: agan_spectral_*; csrc/spectral.hip; Miyato et al. 2018)
+# --------------------------------------------------------------------------------------------------------------
+def _spectral_dims(weight: Tensor, u: Tensor, v: Tensor, second: Optional[Tensor], what: str) -> Tuple[int, int, int]:
+    """-> (Cout, K0, K1) of weight [Cout, ...] and the optional second column segment [Cout, ...], or ValueError"""
+    if weight.dim() < 2 or weight.numel() == 0:
+        raise ValueError(f"{what}: the weight must be [Cout, ...] with at least two axes, got {tuple(weight.shape)}")
+    cout = int(weight.shape[0])
+    k0, k1 = weight.numel() // cout, 0
+    if second is not None:
+        if second.dim() < 2 or second.numel() == 0 or second.numel() % cout:
+            raise ValueError(f"{what}: the second segment must hold {cout} rows, got {tuple(second.shape)}")
+        k1 = second.numel() // cout
+    if tuple(u.shape) != (cout,) or tuple(v.shape) != (k0 + k1,):
+        raise ValueError(f"{what}: u must be [{cout}] and v [{k0 + k1}], got {tuple(u.shape)} and {tuple(v.shape)}")
+    if u.requires_grad or v.requires_grad:
+        raise ValueError(f"{what}: u and v are state, not parameters")
+    for t in (u, v) + (() if second is None else (second,)):
+        if t.device != weight.device or t.dtype != weight.dtype:
+            raise ValueError(f"{what}: every operand must be {weight.dtype} on {weight.device}, got {t.dtype} on {t.device}")
+    return cout, k0, k1
+
+
+def spectral_weight_reference(weight: Tensor, u: Tensor, v: Tensor, training: bool, second: Optional[Tensor] = None):
+    """What spectral_weight computes, as include/agan.h states it and as torch.nn.utils.spectral_norm does with one power iteration,
+    in torch ops, in the operands' dtype, on any device, differentiable by autograd with u and v as constants.  `second` [Cout, K1]
+    (viewed so): the weight is the row-wise concatenation [weight | second], stored as two tensors.  Training mode writes u' and v
+    into `u` and `v`.  -> weight_sn, or (weight_sn, second_sn)."""
+    cout, k0, k1 = _spectral_dims(weight, u, v, second, "spectral_weight_reference")
+    W = weight.reshape(cout, k0) if second is None else torch.cat([weight.reshape(cout, k0), second.reshape(cout, k1)], dim=1)
+    if training:
+        with torch.no_grad():
+            vn = torch.nn.functional.normalize(torch.mv(W.t(), u), dim=0, eps=1e-12)
+            un = torch.nn.functional.normalize(torch.mv(W, vn), dim=0, eps=1e-12)
+            u.copy_(un)
+            v.copy_(vn)
+        u, v = un, vn                                            # this forward's own values: a later iteration moves the buffers
+    else:
+        u, v = u.clone(), v.clone()
+    sigma = torch.dot(u, torch.mv(W, v))
+    return weight / sigma if second is None else (weight / sigma, second / sigma)
+
+
+class _SpectralFn(Function):
+    """-> (weight_sn, second_sn or an empty tensor, u', v).  Everything a backward needs -- W_sn, u', v, sigma of THIS forward -- is in
+    fresh tensors saved per call: a discriminator runs two forwards before one backward (StandardDiscLoss, batch_pairs = False)."""
+
+    @staticmethod
+    def forward(ctx, weight, second, u, v, iterate, wdst, sdst):
+        w0 = _dev(weight.detach(), "spectral weight")
+        w1 = _dev(second.detach(), "spectral weight (second segment)") if second is not None else None
+        cout = w0.shape[0]
+        k0, k1 = w0.numel() // cout, (w1.numel() // cout if w1 is not None else 0)
+        u, v = _dev(u, "spectral u"), _dev(v, "spectral v")
+        lib = L.load()
+        wsn0 = torch.empty_like(w0)
+        wsn1 = torch.empty_like(w1) if w1 is not None else w0.new_empty(0)
+        sigma = torch.empty(1, dtype=torch.float32, device=w0.device)
+        if iterate:
+            un, vn = torch.empty_like(u), torch.empty_like(v)
+        else:
+            un, vn = u.clone(), v.clone()
+        nbytes = lib.agan_spectral_fwd_ws_bytes(cout, k0, k1)
+        ws, wsp = _ws(nbytes, w0)
+        L.call("agan_spectral_fwd", _p(w0), _p(w1), _p(u), _p(v), _p(un), _p(vn), _p(sigma), _p(wsn0), _p(wsn1 if w1 is not None else None),
+               cout, k0, k1, int(iterate), wsp, nbytes, _stream())
+        ctx.save_for_backward(wsn0, wsn1, un, vn, sigma)
+        ctx.dims, ctx.wdst, ctx.sdst, ctx.two = (cout, k0, k1), wdst, sdst, w1 is not None
+        ctx.mark_non_differentiable(un, vn)
+        if w1 is None:
+            ctx.mark_non_differentiable(wsn1)
+        return wsn0, wsn1, un, vn
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d0, d1, _du, _dv):
+        wsn0, wsn1, un, vn, sigma = ctx.saved_tensors
+        cout, k0, k1 = ctx.dims
+        d0 = _dev(d0, "spectral d(weight_sn)") if d0 is not None else torch.zeros_like(wsn0)
+        dw0buf, acc0, dw0 = _grad_out(ctx.wdst, wsn0.shape, wsn0)
+        dw1buf = dw1 = None
+        acc1 = 0
+        if ctx.two:
+            d1 = _dev(d1, "spectral d(second_sn)") if d1 is not None else torch.zeros_like(wsn1)
+            dw1buf, acc1, dw1 = _grad_out(ctx.sdst, wsn1.shape, wsn1)
+        else:
+            d1 = None
+        nbytes = L.load().agan_spectral_bwd_ws_bytes(cout, k0, k1)
+        ws, wsp = _ws(nbytes, wsn0)
+        L.call("agan_spectral_bwd", _p(d0), _p(d1), _p(wsn0), _p(wsn1 if ctx.two else None), _p(un), _p(vn), _p(sigma), _p(dw0buf), _p(dw1buf),
+               cout, k0, k1, acc0, acc1, wsp, nbytes, _stream())
+        return dw0, dw1, None, None, None, None, None
+
+
+def spectral_weight(weight: Tensor, u: Tensor, v: Tensor, training: bool, second: Optional[Tensor] = None):
+    """weight / sigma on the HIP kernels (csrc/spectral.hip), fp32 in every precision mode, with autograd: sigma is the estimate of the
+    largest singular value of weight viewed [Cout, K] that one power iteration from the stored (u, v) gives -- torch.nn.utils.spectral_norm's
+    rule (include/agan.h states the formulas, spectral_weight_reference restates them in torch ops).  `training` iterates once and stores
+    u' and v back into `u` and `v`; eval mode leaves them.  `second`: the weight is [weight | second] row by row, held in two tensors;
+    both are divided by the ONE sigma and (weight_sn, second_sn) comes back.  The result is a FRESH tensor at every call, and the
+    backward uses the u', v and sigma of its own forward: two forwards followed by one backward are fine.  The weight gradient goes to
+    grad_dst(weight) (grad_dst(second)) where the flat optimiser tagged the parameter.  The consumer must not cache a packed form of the
+    result (HF.conv2d / HF.linear with cache=None).  CPU tensors take spectral_weight_reference."""
+    _spectral_dims(weight, u, v, second, "spectral_weight")
+    if not weight.is_cuda:
+        return spectral_weight_reference(weight, u, v, training, second)
+    wsn0, wsn1, un, vn = _SpectralFn.apply(weight, second, u, v, bool(training), grad_dst(weight),
+                                           grad_dst(second) if second is not None else None)
+    if training:
+        with torch.no_grad():
+            u.copy_(un)
+            v.copy_(vn)
+    return wsn0 if second is None else (wsn0, wsn1)
+
+
+# --------------------------------------------------------------------------------------------------------------
 # fused Adam on a flat buffer
 # --------------------------------------------------------------------------------------------------------------
 def adam_step_(param: Tensor, grad: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor, step_state: Tensor, lr: float, beta1: float,

@@ -212,6 +212,11 @@ _SIGNATURES = {
     "agan_word_corr_fwd": (c_int, [_P, _P, _P, c_int, c_float, c_float, c_float, _P, _P, _P, _P] + [c_int] * 4 + [_P]),
     "agan_word_corr_bwd_ws_bytes": (c_size_t, [c_int] * 4),
     "agan_word_corr_bwd": (c_int, [_P, _P, _P, c_int, _P, _P, c_float, c_float, c_float, _P] + [c_int] * 4 + [_P, c_size_t, _P]),
+    "agan_spectral_fwd_ws_bytes": (c_size_t, [c_int] * 3),
+    "agan_spectral_fwd": (c_int, [_P] * 9 + [c_int] * 4 + [_P, c_size_t, _P]),
+    "agan_spectral_bwd_ws_bytes": (c_size_t, [c_int] * 3),
+    "agan_spectral_bwd": (c_int, [_P] * 9 + [c_int] * 5 + [_P, c_size_t, _P]),
+    "agan_spectral_last_launch": (c_int, [_P, c_int]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

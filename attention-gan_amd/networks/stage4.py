@@ -9,7 +9,7 @@ from typing import List, Optional
 
 from torch import Tensor, nn
 
-from ..utilities.layers import Layers
+from ..utilities.layers import Layers, draw_spectral_state_
 from .discriminators import _Disc, _LogitHead
 from .generator import Generator
 from .generator_submodules import GenMakeImage
@@ -40,16 +40,19 @@ class Generator4(Generator):
 
 
 class Disc512(_Disc):
-    def __init__(self, df_dim: int):
+    def __init__(self, df_dim: int, norm: str = "batch"):
         super().__init__()
-        self.img_code_s16 = Layers.encode_image_by_16times(df_dim)
-        self.img_code_s32 = Layers.downBlock(df_dim * 8, df_dim * 16)
-        self.img_code_s64 = Layers.downBlock(df_dim * 16, df_dim * 32)
-        self.img_code_s128 = Layers.downBlock(df_dim * 32, df_dim * 64)
-        self.img_code_s128_1 = Layers.Block3x3_leakRelu(df_dim * 64, df_dim * 32)
-        self.img_code_s128_2 = Layers.Block3x3_leakRelu(df_dim * 32, df_dim * 16)
-        self.img_code_s128_3 = Layers.Block3x3_leakRelu(df_dim * 16, df_dim * 8)
-        self.outlogits = _LogitHead(df_dim * 8)
+        kw = self._set_norm(norm)
+        self.img_code_s16 = Layers.encode_image_by_16times(df_dim, **kw)
+        self.img_code_s32 = Layers.downBlock(df_dim * 8, df_dim * 16, **kw)
+        self.img_code_s64 = Layers.downBlock(df_dim * 16, df_dim * 32, **kw)
+        self.img_code_s128 = Layers.downBlock(df_dim * 32, df_dim * 64, **kw)
+        self.img_code_s128_1 = Layers.Block3x3_leakRelu(df_dim * 64, df_dim * 32, **kw)
+        self.img_code_s128_2 = Layers.Block3x3_leakRelu(df_dim * 32, df_dim * 16, **kw)
+        self.img_code_s128_3 = Layers.Block3x3_leakRelu(df_dim * 16, df_dim * 8, **kw)
+        self.outlogits = _LogitHead(df_dim * 8, bool(kw))
+        if kw:
+            draw_spectral_state_(self)
 
     def forward(self, X: Tensor) -> Tensor:
         x = self.img_code_s128(self.img_code_s64(self.img_code_s32(self.img_code_s16(X))))

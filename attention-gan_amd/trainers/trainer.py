@@ -722,7 +722,16 @@ class GanTrainStep(ModelTrainer):
                 self.w_opt.step_count = 0
         for d, o, ds, os_ in zip(self.Ds, self.d_opts, sd["discriminators"], sd["d_optims"]):
             d.load_state_dict(ds)
-            o.load_state_dict(os_)
+            if getattr(d, "norm", "batch") == "spectral" and any(k.endswith(".running_mean") for k in ds):
+                # a norm="batch" checkpoint warm-starts a spectrally normalised discriminator: its weights are loaded (the module ignores
+                # the BatchNorm entries); the saved moments belong to another parameter list, so the optimiser starts fresh
+                with torch.no_grad():
+                    o.exp_avg.zero_()
+                    o.exp_avg_sq.zero_()
+                    o.step_state.zero_()
+                o.step_count = 0
+            else:
+                o.load_state_dict(os_)
         # noise streams, per rank (checkpoints written before these were saved simply restart them from the seed)
         for key, gen in (("rng", self.rng), ("sample_rng", self.sample_rng)):
             if sd.get(key) is not None:

@@ -20,10 +20,56 @@ from ..backend import functional as HF
 from ..backend import lib as L
 
 
-class HipConv2d(nn.Conv2d):
-    """Parameter holder with nn.Conv2d's init; forward is the HIP implicit-GEMM conv."""
+class SpectralState:
+    """mixin of a weight holder under spectral normalisation (Miyato et al. 2018; HF.spectral_weight): the parameter is `weight_orig`,
+    the power iteration's state the buffers `weight_u` [Cout] and `weight_v` [K] -- the state_dict keys of
+    torch.nn.utils.spectral_norm, whose modules load these entries with strict=True and the other way round.  u and v are drawn as
+    normalised N(0, 1) vectors (`draw=False` leaves them zero for an owner that draws later: draw_spectral_state_).  A checkpoint
+    that has `weight` and no `weight_orig` loads as a warm start: `weight` becomes `weight_orig`, u and v stay as they are."""
 
-    def __init__(self, cin: int, cout: int, k: int, stride: int, pad: int, bias: bool, kind: Optional[str] = None):
+    spectral = False
+
+    def _init_spectral(self, draw: bool = True) -> None:
+        self.spectral = True
+        w = self.weight
+        del self._parameters["weight"]
+        self.register_parameter("weight_orig", w)
+        self.register_buffer("weight_u", w.detach().new_zeros(w.shape[0]))
+        self.register_buffer("weight_v", w.detach().new_zeros(w.numel() // w.shape[0]))
+        if draw:
+            self.draw_spectral_state_()
+
+    @torch.no_grad()
+    def draw_spectral_state_(self) -> None:
+        for b in (self.weight_u, self.weight_v):
+            b.copy_(nn.functional.normalize(b.normal_(0, 1), dim=0, eps=1e-12))
+
+    def weight_sn(self) -> Tensor:
+        """this forward's normalised weight: one power iteration in train mode, none in eval mode (torch's rule)"""
+        return HF.spectral_weight(self.weight_orig, self.weight_u, self.weight_v, self.training)
+
+    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
+        if self.spectral and prefix + "weight" in state_dict and prefix + "weight_orig" not in state_dict:
+            state_dict[prefix + "weight_orig"] = state_dict.pop(prefix + "weight")      # (load_state_dict works on its own copy)
+            for name in ("weight_u", "weight_v"):
+                state_dict.setdefault(prefix + name, getattr(self, name))
+        super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
+
+
+def draw_spectral_state_(module: nn.Module) -> None:
+    """draw u and v of every spectrally normalised holder inside `module`, in module order (for owners that built them with draw=False)"""
+    for m in module.modules():
+        if getattr(m, "spectral", False):
+            m.draw_spectral_state_()
+
+
+class HipConv2d(SpectralState, nn.Conv2d):
+    """Parameter holder with nn.Conv2d's init; forward is the HIP implicit-GEMM conv.  `spectral=True`: the weight is divided by its
+    largest singular value at every forward (SpectralState); the normalised weight is a fresh tensor per call, so the conv runs
+    without a pack cache and without a flat gradient destination -- HF.spectral_weight's backward writes the parameter's gradient."""
+
+    def __init__(self, cin: int, cout: int, k: int, stride: int, pad: int, bias: bool, kind: Optional[str] = None, spectral: bool = False,
+                 draw: bool = True):
         super().__init__(cin, cout, kernel_size=k, stride=stride, padding=pad, bias=bias)
         if kind is None:
             if stride == 1 and pad == (k - 1) // 2 and k % 2 == 1:
@@ -36,10 +82,14 @@ class HipConv2d(nn.Conv2d):
                 raise NotImplementedError(f"conv k={k} s={stride} p={pad} is not on the AttnGAN hot path")
         self.kind = kind
         self._packed = {}        # packed-weight cache (layout copies for the kernels; not part of state_dict)
+        if spectral:
+            self._init_spectral(draw)
 
     def forward(self, x: Tensor, act: int = L.ACT_NONE, handoff_out=None, handoff_in=None) -> Tensor:
         """`act` (only where HF.conv_fuses_activation allows it) applies the following activation in the conv epilogue;
         the handoffs link such a conv to its single consumer (HF.ActHandoff)."""
+        if self.spectral:
+            return self._forward_spectral(x, act, handoff_out, handoff_in)
         if self.kind == "any":       # no fused activation, no handoff (FusedChain.run never asks for one)
             return HF.conv2d(x, self.weight, self.bias, "any", None, HF.grad_dst(self.weight),
                              HF.grad_dst(self.bias) if self.bias is not None else None, act, handoff_out, None,
@@ -47,13 +97,24 @@ class HipConv2d(nn.Conv2d):
         return HF.conv2d(x, self.weight, self.bias, self.kind, self._packed, HF.grad_dst(self.weight),
                          HF.grad_dst(self.bias) if self.bias is not None else None, act, handoff_out, handoff_in)
 
+    def _forward_spectral(self, x: Tensor, act: int, handoff_out, handoff_in) -> Tensor:
+        """the conv on this forward's normalised weight: no pack cache and no flat destination for a tensor that is new at every call"""
+        bdst = HF.grad_dst(self.bias) if self.bias is not None else None
+        if self.kind == "any":
+            return HF.conv2d(x, self.weight_sn(), self.bias, "any", None, None, bdst, act, handoff_out, None, self.stride, self.padding)
+        return HF.conv2d(x, self.weight_sn(), self.bias, self.kind, None, None, bdst, act, handoff_out, handoff_in)
 
-class HipLinear(nn.Linear):
-    def __init__(self, *args, **kwargs):
+
+class HipLinear(SpectralState, nn.Linear):
+    def __init__(self, *args, spectral: bool = False, draw: bool = True, **kwargs):
         super().__init__(*args, **kwargs)
         self._packed = {}
+        if spectral:
+            self._init_spectral(draw)
 
     def forward(self, x: Tensor) -> Tensor:
+        if self.spectral:
+            return HF.linear(x, self.weight_sn(), self.bias, None, None, HF.grad_dst(self.bias) if self.bias is not None else None)
         return HF.linear(x, self.weight, self.bias, self._packed, HF.grad_dst(self.weight),
                          HF.grad_dst(self.bias) if self.bias is not None else None)
 
@@ -263,20 +324,36 @@ class Layers:
         return FusedChain().add_stage(0, HipConv2d(in_planes, out_planes * 2, 3, 1, 1, False), 1, L.ACT_GLU)
 
     @staticmethod
-    def Block3x3_leakRelu(in_planes: int, out_planes: int) -> FusedChain:
-        return FusedChain().add_stage(0, HipConv2d(in_planes, out_planes, 3, 1, 1, False), 1, L.ACT_LRELU)
+    def _norm(norm: str) -> bool:
+        """is a discriminator block's `norm` the spectral mode?  ("batch", the default: the reference's conv + BatchNorm)"""
+        if norm not in ("batch", "spectral"):
+            raise ValueError(f"norm={norm!r}: 'batch' or 'spectral'")
+        return norm == "spectral"
+
+    # The discriminators' blocks take norm="spectral": the conv is spectrally normalised (HipConv2d(spectral=True)) and the stage has NO
+    # BatchNorm (BatchNorm cancels any rescaling of the weight before it) -- conv + LeakyReLU then run as one kernel (FusedChain.run).
+    # draw=False leaves u and v for the owner to draw after all its children exist (draw_spectral_state_).
+    @staticmethod
+    def Block3x3_leakRelu(in_planes: int, out_planes: int, norm: str = "batch", draw: bool = True) -> FusedChain:
+        sn = Layers._norm(norm)
+        return FusedChain().add_stage(0, HipConv2d(in_planes, out_planes, 3, 1, 1, False, spectral=sn, draw=draw), None if sn else 1,
+                                      L.ACT_LRELU)
 
     @staticmethod
-    def downBlock(in_planes: int, out_planes: int) -> FusedChain:
-        return FusedChain().add_stage(0, HipConv2d(in_planes, out_planes, 4, 2, 1, False), 1, L.ACT_LRELU)
+    def downBlock(in_planes: int, out_planes: int, norm: str = "batch", draw: bool = True) -> FusedChain:
+        sn = Layers._norm(norm)
+        return FusedChain().add_stage(0, HipConv2d(in_planes, out_planes, 4, 2, 1, False, spectral=sn, draw=draw), None if sn else 1,
+                                      L.ACT_LRELU)
 
     @staticmethod
-    def encode_image_by_16times(df_dims: int) -> FusedChain:
-        """Four stride-2 conv4x4 stages 3->df->2df->4df->8df; the first has no BN (keys 0,2,3,5,6,8,9)."""
+    def encode_image_by_16times(df_dims: int, norm: str = "batch", draw: bool = True) -> FusedChain:
+        """Four stride-2 conv4x4 stages 3->df->2df->4df->8df; the first has no BN (keys 0,2,3,5,6,8,9).  norm="spectral": none has,
+        and every conv is spectrally normalised (keys 0,2,5,8 .weight_orig / .weight_u / .weight_v)."""
         d = df_dims
-        chain = FusedChain().add_stage(0, HipConv2d(3, d, 4, 2, 1, False), None, L.ACT_LRELU)
+        sn = Layers._norm(norm)
+        chain = FusedChain().add_stage(0, HipConv2d(3, d, 4, 2, 1, False, spectral=sn, draw=draw), None, L.ACT_LRELU)
         for idx, (ci, co) in zip((2, 5, 8), ((d, 2 * d), (2 * d, 4 * d), (4 * d, 8 * d))):
-            chain.add_stage(idx, HipConv2d(ci, co, 4, 2, 1, False), idx + 1, L.ACT_LRELU)
+            chain.add_stage(idx, HipConv2d(ci, co, 4, 2, 1, False, spectral=sn, draw=draw), None if sn else idx + 1, L.ACT_LRELU)
         return chain
 
     @staticmethod

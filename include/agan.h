@@ -43,7 +43,8 @@ extern "C" {
  * pixel-to-pixel attention of the generator's self-attention block and its gate (agan_self_attn_*, agan_scaled_residual_*); the dynamic
  * memory of the generator's refinement stages (agan_mem_write_*, agan_mem_read_*), for which agan_act_fwd / agan_act_bwd also take
  * AGAN_ACT_RELU; the channel-wise word attention of those stages (agan_chan_attn_*); the word-level
- * discriminator's word-region correlation score (agan_word_corr_*). */
+ * discriminator's word-region correlation score (agan_word_corr_*); the spectral normalisation of a discriminator's weights
+ * (agan_spectral_*). */
 
 enum {
     AGAN_OK = 0,
@@ -1075,6 +1076,47 @@ size_t agan_word_corr_bwd_ws_bytes(int B, int D, int T, int S);
 int agan_word_corr_bwd(const float* regions, const float* words, const int64_t* lens, int shift, const float* save, const float* dp,
                        float gamma1, float gamma2, float eps, float* dregions, int B, int D, int T, int S, void* ws, size_t ws_bytes,
                        void* stream);
+
+/* ----------------------------------------------------------------------------------------------
+ * Spectral normalisation of a weight (csrc/spectral.hip; utilities/layers.py: HipConv2d / HipLinear(spectral=True); Miyato et al.,
+ * ICLR 2018).  fp32 in every precision mode.
+ * W is a weight seen as a matrix [Cout, K], K = Cin * kh * kw, row-major as the parameter lies.  W may consist of TWO COLUMN SEGMENTS
+ * [Cout, K0 | K1] held in two separate contiguous tensors (w0 [Cout, K0], w1 [Cout, K1]: the conditional head's joint conv); K1 = 0
+ * is the ordinary case, and w1 / wsn1 / dwsn1 / dw1 are then not read.  The state is u [Cout] and v [K], both unit vectors.
+ * eps = 1e-12.
+ *   agan_spectral_fwd with iterate = 1 (a training-mode forward) computes, exactly like torch.nn.utils.spectral_norm with one power
+ *   iteration:
+ *       v  = W^T u / max(|W^T u|, eps)
+ *       t  = W v
+ *       u' = t / max(|t|, eps)
+ *       sigma = <u', W v>            (= |t|)
+ *       W_sn  = W / sigma
+ *   and writes u' to u_out, v to v_out (they may be u and v themselves: the state stored back), sigma to sigma[0] and W_sn to
+ *   wsn0 (and wsn1).  `v` is not read.
+ *   With iterate = 0 (an eval-mode forward) u and v are left alone, sigma = <u, W v>; u_out and v_out are not written (may be NULL).
+ *   agan_spectral_bwd treats u and v as constants, as torch does.  From dW_sn, the W_sn, sigma and the (u', v) of ITS forward (u, v with
+ *   iterate = 0):
+ *       c  = <dW_sn, W_sn>           (over the whole matrix, both segments)
+ *       dW = (dW_sn - c * u' v^T) / sigma
+ *   dW is written into dw0 (dw1), or added to it where accumulate0 (accumulate1) is non-zero: the accumulate-flag convention of
+ *   agan_attn_bwd, one flag per segment because the two are separate parameters.
+ *   W = 0 gives 0 / 0 as it does in torch: outside the domain.
+ * Forms: at most 8192 weights run one workgroup and one launch per direction, without a workspace; above that the forward is four
+ * launches (three with iterate = 0) and the backward two, every sum over rows or columns through per-workgroup partials in `ws` and
+ * a fixed-order final sum.  No float atomics: two runs give the same bits.  agan_spectral_last_launch fills codes[0..3] with the form
+ * of the calling thread's last forward (1 small, 2 big), its slabs and column chunks, and the form of its last backward; returns 4.
+ * Domain: Cout >= 1, K0 >= 1, K1 >= 0, Cout * (K0 + K1) < 2^31, iterate 0 or 1.  Anything else, or a null pointer, is AGAN_EINVAL with
+ * the entry's name in agan_last_error() before any HIP call (the workspace queries then answer 0); a workspace below
+ * agan_spectral_{fwd,bwd}_ws_bytes is AGAN_EWORKSPACE.  Only enqueues on `stream`: no allocation, no host read; graph-capturable.
+ * ---------------------------------------------------------------------------------------------- */
+size_t agan_spectral_fwd_ws_bytes(int cout, int k0, int k1);
+int agan_spectral_fwd(const float* w0, const float* w1, const float* u, const float* v, float* u_out, float* v_out, float* sigma,
+                      float* wsn0, float* wsn1, int cout, int k0, int k1, int iterate, void* ws, size_t ws_bytes, void* stream);
+size_t agan_spectral_bwd_ws_bytes(int cout, int k0, int k1);
+int agan_spectral_bwd(const float* dwsn0, const float* dwsn1, const float* wsn0, const float* wsn1, const float* u, const float* v,
+                      const float* sigma, float* dw0, float* dw1, int cout, int k0, int k1, int accumulate0, int accumulate1, void* ws,
+                      size_t ws_bytes, void* stream);
+int agan_spectral_last_launch(int* codes, int capacity);
 
 #ifdef __cplusplus
 }
