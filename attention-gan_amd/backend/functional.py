@@ -88,6 +88,13 @@ def get_activation_storage() -> int:
     return L.DT_F32
 
 
+def _fp32_only(what: str, family: str, *tensors: Tensor) -> None:
+    """the guard of an entry point whose kernels have no 16-bit storage forms"""
+    if get_activation_storage() != L.DT_F32 or any(t.dtype in _DT_OF for t in tensors):
+        raise L.AganError(f"{what}: the {family} kernels store fp32 only; 16-bit activation storage (set_activation_storage) and "
+                          f"16-bit tensors are not built for them")
+
+
 def _dt(t: Tensor) -> int:
     return L.DT_F32 if t.dtype == torch.float32 else _DT_OF[t.dtype]
 
@@ -1023,9 +1030,7 @@ def cond_bn_act(x, gamma, beta, delta, running_mean, running_var, nbt, training:
     B, C, HW = _cond_bn_dims(x, gamma, delta, act, "cond_bn_act")
     if _BN_GROUPS[0] != 1:
         raise L.AganError(f"cond_bn_act: bn_groups({_BN_GROUPS[0]}) is in force; the conditional BatchNorm normalises the batch as one group")
-    if get_activation_storage() != L.DT_F32 or x.dtype in _DT_OF:
-        raise L.AganError("cond_bn_act: the conditional BatchNorm kernels store fp32 only; 16-bit activation storage "
-                          "(set_activation_storage) is not built for them")
+    _fp32_only("cond_bn_act", "conditional BatchNorm", x)
     if not delta.is_cuda or delta.dtype != torch.float32 or not delta.is_contiguous():
         raise L.AganError(f"cond_bn_act: delta must be a contiguous float32 [B, 2C] device tensor, got {delta.dtype} on {delta.device}"
                           f"{'' if delta.is_contiguous() else ', not contiguous'}")
@@ -1049,12 +1054,6 @@ def _self_attn_dims(q: Tensor, k: Tensor, v: Tensor, what: str) -> Tuple[int, in
         raise ValueError(f"{what}: q {tuple(q.shape)}, k {tuple(k.shape)} and v {tuple(v.shape)} do not fit "
                          f"([B, Dk, N], [B, Dk, M], [B, Dv, M])")
     return B, N, M, Dk, Dv
-
-
-def _fp32_storage_only(what: str, *tensors: Tensor) -> None:
-    if get_activation_storage() != L.DT_F32 or any(t.dtype in _DT_OF for t in tensors):
-        raise L.AganError(f"{what}: the self-attention kernels store fp32 only; 16-bit activation storage "
-                          f"(set_activation_storage) is not built for them")
 
 
 def self_attention_reference(q: Tensor, k: Tensor, v: Tensor, scale: float = 1.0) -> Tensor:
@@ -1144,7 +1143,7 @@ def self_attention(q: Tensor, k: Tensor, v: Tensor, scale: float = 1.0) -> Tenso
     Dk <= 64 and Dv <= 128.  Nothing of size N x M is allocated in either direction: the backward keeps q, k, v, o and one
     log-sum-exp per query and recomputes the probabilities."""
     _self_attn_dims(q, k, v, "self_attention")
-    _fp32_storage_only("self_attention", q, k, v)
+    _fp32_only("self_attention", "self-attention", q, k, v)
     return _SelfAttnFn.apply(_dev(q, "self-attention q"), _dev(k, "self-attention k"), _dev(v, "self-attention v"), float(scale))
 
 
@@ -1154,7 +1153,7 @@ def self_attention_qkv(qkv: Tensor, dk: int, dv: int, scale: float = 1.0) -> Ten
     wrote in place (no cat)."""
     if qkv.dim() < 3 or qkv.numel() == 0 or dk < 1 or dv < 1 or int(qkv.shape[1]) != 2 * dk + dv:
         raise ValueError(f"self_attention_qkv: qkv must be [B, 2 dk + dv = {2 * dk + dv}, positions...], got {tuple(qkv.shape)}")
-    _fp32_storage_only("self_attention_qkv", qkv)
+    _fp32_only("self_attention_qkv", "self-attention", qkv)
     return _SelfAttnQkvFn.apply(_dev(qkv, "self-attention qkv"), int(dk), int(dv), float(scale))
 
 
@@ -1193,7 +1192,7 @@ def scaled_residual(x: Tensor, y: Tensor, g: Tensor) -> Tensor:
     if x.shape != y.shape or x.numel() == 0 or g.numel() != 1:
         raise ValueError(f"scaled_residual: x {tuple(x.shape)} and y {tuple(y.shape)} must agree and g must hold one element, "
                          f"got {tuple(g.shape)}")
-    _fp32_storage_only("scaled_residual", x, y)
+    _fp32_only("scaled_residual", "self-attention", x, y)
     return _ScaledResidualFn.apply(_dev(x, "scaled_residual x"), _dev(y, "scaled_residual y"), g, grad_dst(g))
 
 
@@ -1309,12 +1308,6 @@ def attention(images: Tensor, words: Tensor, conv1_weight: Tensor, mask: Tensor,
 # --------------------------------------------------------------------------------------------------------------
 # dynamic memory of a refinement stage (networks/memory.py: DynamicMemory; include/agan.h: agan_mem_write_*, agan_mem_read_*)
 # --------------------------------------------------------------------------------------------------------------
-def _mem_fp32_only(what: str, *tensors: Tensor) -> None:
-    if get_activation_storage() != L.DT_F32 or any(t.dtype in _DT_OF for t in tensors):
-        raise L.AganError(f"{what}: the memory kernels store fp32 only; 16-bit activation storage (set_activation_storage) is not "
-                          f"built for them")
-
-
 def _mem_write_dims(U: Tensor, Q: Tensor, what: str) -> Tuple[int, int, int]:
     """-> (B, T, Md) of U [B, T, Md + 1] and Q [B, Md + 1], or ValueError"""
     if U.dim() != 3 or Q.dim() != 2 or U.numel() == 0 or U.shape[2] < 2 or tuple(Q.shape) != (U.shape[0], U.shape[2]):
@@ -1389,7 +1382,7 @@ def memory_write(U: Tensor, Q: Tensor) -> Tensor:
     """The gated write of the words into the memory on the HIP kernels (csrc/memory.hip), fp32, with autograd; memory_write_reference
     states it in torch ops.  U [B, T, Md + 1] (T <= 64), Q [B, Md + 1] -> m [B, T, Md]."""
     _mem_write_dims(U, Q, "memory_write")
-    _mem_fp32_only("memory_write", U, Q)
+    _fp32_only("memory_write", "memory", U, Q)
     return _MemoryWriteFn.apply(_dev(U, "memory_write U"), _dev(Q, "memory_write Q"))
 
 
@@ -1433,7 +1426,7 @@ def memory_read(h: Tensor, kv: Tensor, mask: Tensor, rw: Tensor, rb: Tensor) -> 
     (x [B, 2C, H, W] = cat(r, r), attn [B, T, H, W]).  The backward keeps the attention map only and recomputes the rest; the
     gradients of rw and rb go to their flat-gradient slices (grad_dst) where the parameters have one."""
     _mem_read_dims(h, kv, mask, rw, rb, "memory_read")
-    _mem_fp32_only("memory_read", h, kv)
+    _fp32_only("memory_read", "memory", h, kv)
     return _MemoryReadFn.apply(_dev(h, "memory_read h"), _dev(kv, "memory_read kv"), mask, rw, rb, grad_dst(rw), grad_dst(rb))
 
 
@@ -1510,9 +1503,7 @@ def channel_attention(h: Tensor, wt: Tensor, mask: Tensor, scale: Optional[float
     (0 = ignore the word), scale None = 1 / sqrt(H * W) -> (f [B, C, H, W], alpha [B, C, T]).  Three launches per direction; nothing of
     the backward is computed for an input that needs no gradient."""
     B, C, T, H, W = _chan_attn_dims(h, wt, mask, "channel_attention")
-    if get_activation_storage() != L.DT_F32 or any(t.dtype in _DT_OF for t in (h, wt)):
-        raise L.AganError("channel_attention: the channel-attention kernels are fp32 only; 16-bit activation storage "
-                          "(set_activation_storage) and 16-bit tensors are not built for them")
+    _fp32_only("channel_attention", "channel-attention", h, wt)
     return _ChannelAttentionFn.apply(_dev(h, "channel_attention h"), _dev(wt, "channel_attention wt"), mask, _chan_attn_scale(scale, H * W))
 
 

@@ -34,6 +34,45 @@ inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s);
 
 __host__ __device__ inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 __host__ __device__ inline size_t cdivz(size_t a, size_t b) { return (a + b - 1) / b; }
+inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }         // workspace regions start on 16-byte boundaries
+
+// The caller's workspace must hold `need` bytes; a null one passes only when nothing is needed.
+inline int check_ws(const char* who, size_t need, const void* ws, size_t ws_bytes) {
+    if (ws_bytes < need || (need && !ws)) {
+        set_error("%s: workspace of %zu bytes, %zu needed", who, ws_bytes, need);
+        return AGAN_EWORKSPACE;
+    }
+    return AGAN_OK;
+}
+
+// The kernel launches of a thread's last call into one kernel family, one code per launch (the family's agan_*_last_launch copies it out).
+template <int Cap>
+struct LaunchLog {
+    int codes[Cap];
+    int n = 0;                      // launches since reset(): may pass Cap, the codes past it are dropped
+    void reset() { n = 0; }
+    void add(int code) {
+        if (n < Cap) codes[n] = code;
+        ++n;
+    }
+    int copy_out(int* dst, int capacity) const {
+        const int m = n < Cap ? n : Cap;
+        for (int i = 0; i < m && i < capacity; ++i) dst[i] = codes[i];
+        return n;
+    }
+};
+
+// ---- scalar device helpers -------------------------------------------------------------------
+// LDS traffic between the lanes of ONE wave needs no s_barrier (a wave's LDS instructions execute in order); this only stops the
+// compiler from moving LDS accesses across the hand-over.
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+// The two sigmoids round differently: a call site keeps the one it was tested with.
+__device__ __forceinline__ float sigmoid_fast(float v) { return 1.f / (1.f + __expf(-v)); }    // hardware exp2 path
+__device__ __forceinline__ float sigmoid_exact(float v) { return 1.f / (1.f + expf(-v)); }     // libm-accurate exp
 
 // ---- wave / block reductions (64-lane wave) --------------------------------------------------
 __device__ __forceinline__ float wave_sum(float v) {
@@ -212,6 +251,18 @@ __device__ __forceinline__ float block_sum(float v, float* smem) {
 #pragma unroll
     for (int i = 0; i < NT / 64; ++i) r += smem[i];
     return r;
+}
+// fp64 sum over a block of NT threads (a power of two) by one fixed tree: the same bits on every run.  red: NT doubles of LDS, free to
+// overwrite on entry.  The total is left in red[0], behind a barrier, for the thread that uses it to read.
+template <int NT>
+__device__ __forceinline__ void block_tree_sum_d(double v, double* red) {
+    static_assert(NT >= 2 && (NT & (NT - 1)) == 0, "NT must be a power of two");
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int o = NT / 2; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
 }
 
 }  // namespace agan

@@ -8,6 +8,7 @@
 // Algorithmic bytes/pixel: 4*(C read + C write + T write); HBM-bound (116 MB at gen3).
 #include "agan_common.h"
 #include "dispatch.h"
+#include "mfma_tile.h"
 
 using namespace agan;
 
@@ -15,16 +16,6 @@ namespace {
 
 constexpr int kMaxC = 64;   // LDS budget for the projected words: kMaxC * TMAX floats
 constexpr int kAttLd = 68;  // row stride (floats) of the per-wave transposition tiles of the backward
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// LDS traffic between the lanes of ONE wave needs no s_barrier (a wave's LDS instructions execute in order); this only stops the
-// compiler from moving LDS accesses across the hand-over.
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // proj[b,c,t] = sum_e w[c,e] * words[b,e,t]        (attention.py:50-52: the 1x1 conv on the word axis)
 // one wave per (b, c): lanes stride the embedding axis, the T partial sums meet in one transposing butterfly
@@ -335,10 +326,7 @@ int agan_attn_bwd_dt(const void* images, const float* words, const float* w, con
     AGAN_REQUIRE(dtype == AGAN_DT_F32 || dtype == AGAN_DT_BF16 || dtype == AGAN_DT_F16, "attn_bwd: storage type %d", dtype);
     AGAN_REQUIRE(B > 0 && C > 0 && E > 0 && T > 0 && HW > 0, "attn_bwd: non-positive dimension");
     AGAN_REQUIRE(C <= kMaxC && T <= 64, "attn_bwd: nc_in %d / seq_len %d out of range", C, T);
-    if (ws_bytes < agan_attn_bwd_ws_bytes(B, C, T, HW)) {
-        set_error("attn_bwd: workspace too small");
-        return AGAN_EWORKSPACE;
-    }
+    if (int e = check_ws("attn_bwd", agan_attn_bwd_ws_bytes(B, C, T, HW), ws, ws_bytes)) return e;
     hipStream_t st = as_stream(stream);
     float* dproj = static_cast<float*>(ws);
     float* part = dproj + (size_t)B * C * T;

@@ -9,16 +9,12 @@ using namespace agan;
 namespace {
 
 // ---- launch log: one integer per kernel launch of the last agan_bn_* / agan_act_* / agan_glu_* call (agan_bn_last_launch) --------
-constexpr int kLogCap = 64;
-thread_local int g_log[kLogCap];
-thread_local int g_log_n = 0;
+thread_local LaunchLog<64> g_log;
 // kernel kinds of a log code (include/agan.h: agan_bn_last_launch)
 enum { kLogStatsPartial = 1, kLogStatsFinal, kLogStatsRows, kLogFwdApply, kLogSmallFwd, kLogSmallBwd, kLogBwdPartial, kLogBwdFinal,
        kLogBwdApply, kLogActFwd, kLogActBwd, kLogGluFwd, kLogGluBwd };
-inline void log_reset() { g_log_n = 0; }
 inline void log_launch(int kind, int act, int xdt, int odt, int width) {
-    if (g_log_n < kLogCap) g_log[g_log_n] = kind * 100000 + act * 10000 + xdt * 1000 + odt * 100 + width;
-    ++g_log_n;
+    g_log.add(kind * 100000 + act * 10000 + xdt * 1000 + odt * 100 + width);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -135,7 +131,7 @@ __global__ __launch_bounds__(256) void bn_act_fwd_kernel(const void* __restrict_
             float gv[V];
             ldv<XDT, V>(x, xi + (size_t)Co * HW, gv);
 #pragma unroll
-            for (int k = 0; k < V; ++k) yv[k] = norm_of(a, xv[k]) * sigmoidf_(norm_of(g, gv[k]));
+            for (int k = 0; k < V; ++k) yv[k] = norm_of(a, xv[k]) * sigmoid_fast(norm_of(g, gv[k]));
         } else {
 #pragma unroll
             for (int k = 0; k < V; ++k) {
@@ -285,7 +281,7 @@ template <int ACT>
 __device__ __forceinline__ float act1(float v) {
     if (ACT == AGAN_ACT_LRELU) return v > 0.f ? v : v * kSlope;
     if (ACT == AGAN_ACT_TANH) return tanhf(v);
-    if (ACT == AGAN_ACT_SIGMOID) return 1.f / (1.f + expf(-v));
+    if (ACT == AGAN_ACT_SIGMOID) return sigmoid_exact(v);
     if (ACT == AGAN_ACT_RELU) return v > 0.f ? v : 0.f;
     return v;
 }
@@ -331,7 +327,7 @@ __global__ __launch_bounds__(256) void glu_fwd_kernel(const float* __restrict__ 
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         const size_t plane = (size_t)Co * HW, b = i / plane, r = i - b * plane;
         const size_t xi = b * 2 * plane + r;
-        out[i] = x[xi] * sigmoidf_(x[xi + plane]);
+        out[i] = x[xi] * sigmoid_fast(x[xi + plane]);
     }
 }
 __global__ __launch_bounds__(256) void glu_bwd_kernel(const float* __restrict__ x, const float* __restrict__ dout, float* __restrict__ dx,
@@ -341,7 +337,7 @@ __global__ __launch_bounds__(256) void glu_bwd_kernel(const float* __restrict__ 
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         const size_t plane = (size_t)Co * HW, b = i / plane, r = i - b * plane;
         const size_t xi = b * 2 * plane + r;
-        const float a = x[xi], sg = sigmoidf_(x[xi + plane]), d = dout[i];
+        const float a = x[xi], sg = sigmoid_fast(x[xi + plane]), d = dout[i];
         dx[xi] = d * sg;
         dx[xi + plane] = d * a * sg * (1.f - sg);
     }
@@ -400,7 +396,7 @@ __global__ __launch_bounds__(256) void bn_small_fwd_kernel(const void* __restric
             const int b = i / HW, p = i - b * HW;
             const size_t oi = ((size_t)b * Co + c) * HW + p;
             float z = norm_of(a, va[j]);
-            if (GLU) z *= sigmoidf_(norm_of(g, vg[j]));
+            if (GLU) z *= sigmoid_fast(norm_of(g, vg[j]));
             else if (ACT == AGAN_ACT_LRELU) z = z > 0.f ? z : z * kSlope;
             if (!GLU && ACT == AGAN_ACT_NONE && res) z += ld1<ODT>(res, oi);
             st1<ODT>(out, oi, z);
@@ -589,10 +585,11 @@ int bn_stats_impl(const void* x, int B, int C, int HW, float eps, float* mean, f
         return check_launch("bn_stats_rows");
     }
     const int nchunk = bn_chunks(B, C, HW);
-    if (ws_bytes < agan_bn_stats_ws_bytes(B, C, HW) || !ws) {
-        set_error("bn_stats: workspace too small");
+    if (!ws) {
+        set_error("bn_stats: no workspace");
         return AGAN_EWORKSPACE;
     }
+    if (int e = check_ws("bn_stats", agan_bn_stats_ws_bytes(B, C, HW), ws, ws_bytes)) return e;
     double* part = static_cast<double*>(ws);
     log_launch(kLogStatsPartial, 0, x_dtype, x_dtype, vec_width(x_dtype != AGAN_DT_F32, HW));
     with_dt(x_dtype, [&](auto XD) {
@@ -627,7 +624,7 @@ int bn_act_fwd_impl(const void* x, const float* mean, const float* invstd, const
 
 int agan::bn_train_stats(const float* x, int B, int C, int HW, float eps, float* mean, float* invstd, float* running_mean,
                          float* running_var, int64_t* nbt, float momentum, void* ws, size_t ws_bytes, void* stream, int* form, int* width) {
-    log_reset();
+    g_log.reset();
     if (HW > 1 && (long long)B * HW <= kSmallN) {
         AGAN_REQUIRE(x && mean && invstd && B > 0 && C > 0, "bn_train_stats: bad argument");
         with_per(B * HW, [&](auto P) {
@@ -648,15 +645,11 @@ size_t agan_bn_stats_ws_bytes(int B, int C, int HW) {
     return (size_t)C * bn_chunks(B, C, HW) * 2 * sizeof(double);
 }
 
-int agan_bn_last_launch(int* codes, int capacity) {
-    const int n = std::min(std::min(g_log_n, kLogCap), capacity);
-    for (int i = 0; i < n; ++i) codes[i] = g_log[i];
-    return g_log_n;
-}
+int agan_bn_last_launch(int* codes, int capacity) { return g_log.copy_out(codes, capacity); }
 
 int agan_bn_stats_dt(const void* x, int B, int C, int HW, float eps, float* mean, float* invstd, float* running_mean,
                      float* running_var, int64_t* nbt, float momentum, void* ws, size_t ws_bytes, void* stream, int x_dtype) {
-    log_reset();
+    g_log.reset();
     return bn_stats_impl(x, B, C, HW, eps, mean, invstd, running_mean, running_var, nbt, momentum, ws, ws_bytes, stream, x_dtype);
 }
 int agan_bn_stats(const float* x, int B, int C, int HW, float eps, float* mean, float* invstd, float* running_mean,
@@ -667,7 +660,7 @@ int agan_bn_stats(const float* x, int B, int C, int HW, float eps, float* mean, 
 int agan_bn_act_fwd_dt(const void* x, const float* mean, const float* invstd, const float* gamma, const float* beta,
                        const void* residual, void* out, int B, int C, int HW, int act, void* stream, float* out_amax, int x_dtype,
                        int out_dtype) {
-    log_reset();
+    g_log.reset();
     return bn_act_fwd_impl(x, mean, invstd, gamma, beta, residual, out, B, C, HW, act, stream, out_amax, x_dtype, out_dtype);
 }
 int agan_bn_act_fwd(const float* x, const float* mean, const float* invstd, const float* gamma, const float* beta,
@@ -682,15 +675,12 @@ size_t agan_bn_act_bwd_ws_bytes(int B, int C, int HW) {
 int agan_bn_act_bwd_dt(const void* x, const void* dout, const float* mean, const float* invstd, const float* gamma,
                        const float* beta, void* dx, float* dgamma, float* dbeta, int B, int C, int HW, int act, int accumulate,
                        int groups, void* ws, size_t ws_bytes, void* stream, float* dx_amax, int x_dtype, int out_dtype) {
-    log_reset();
+    g_log.reset();
     if (int e = check_bn_args("bn_act_bwd", x && dout && mean && invstd && gamma && beta && dx && dgamma && dbeta && ws, "null pointer", act,
                               C, false, true, B, groups, x_dtype, out_dtype))
         return e;
     const int Bg = B / groups;
-    if (ws_bytes < agan_bn_act_bwd_ws_bytes(Bg, C, HW)) {
-        set_error("bn_act_bwd: workspace too small");
-        return AGAN_EWORKSPACE;
-    }
+    if (int e = check_ws("bn_act_bwd", agan_bn_act_bwd_ws_bytes(Bg, C, HW), ws, ws_bytes)) return e;
     hipStream_t st = as_stream(stream);
     const bool glu = act == AGAN_ACT_GLU;
     const int Co = glu ? C / 2 : C;
@@ -740,7 +730,7 @@ int agan_bn_act_bwd(const float* x, const float* dout, const float* mean, const 
 }
 
 int agan_act_fwd(const float* x, float* out, size_t n, int act, void* stream) {
-    log_reset();
+    g_log.reset();
     AGAN_REQUIRE(x && out && n > 0, "act_fwd: bad argument");
     hipStream_t st = as_stream(stream);
     log_launch(kLogActFwd, act, AGAN_DT_F32, AGAN_DT_F32, 4);
@@ -751,7 +741,7 @@ int agan_act_fwd(const float* x, float* out, size_t n, int act, void* stream) {
 }
 
 int agan_act_bwd(const float* y, const float* dout, float* dx, size_t n, int act, void* stream) {
-    log_reset();
+    g_log.reset();
     AGAN_REQUIRE(y && dout && dx && n > 0, "act_bwd: bad argument");
     hipStream_t st = as_stream(stream);
     log_launch(kLogActBwd, act, AGAN_DT_F32, AGAN_DT_F32, 4);
@@ -762,7 +752,7 @@ int agan_act_bwd(const float* y, const float* dout, float* dx, size_t n, int act
 }
 
 int agan_glu_fwd(const float* x, float* out, int B, int C, int HW, void* stream) {
-    log_reset();
+    g_log.reset();
     AGAN_REQUIRE(x && out && B > 0 && C > 0 && HW > 0, "glu_fwd: bad argument");
     AGAN_REQUIRE(C % 2 == 0, "channels dont divide 2!");
     log_launch(kLogGluFwd, AGAN_ACT_GLU, AGAN_DT_F32, AGAN_DT_F32, 1);
@@ -771,7 +761,7 @@ int agan_glu_fwd(const float* x, float* out, int B, int C, int HW, void* stream)
 }
 
 int agan_glu_bwd(const float* x, const float* dout, float* dx, int B, int C, int HW, void* stream) {
-    log_reset();
+    g_log.reset();
     AGAN_REQUIRE(x && dout && dx && B > 0 && C > 0 && HW > 0 && C % 2 == 0, "glu_bwd: bad argument");
     log_launch(kLogGluBwd, AGAN_ACT_GLU, AGAN_DT_F32, AGAN_DT_F32, 1);
     hipLaunchKernelGGL(glu_bwd_kernel, dim3(ew_blocks((size_t)B * (C / 2) * HW)), dim3(256), 0, as_stream(stream), x, dout, dx, B, C, HW);
@@ -787,7 +777,7 @@ int agan_bn_train_fwd_dt(const void* x, const float* gamma, const float* beta, c
                          float* invstd, float* running_mean, float* running_var, int64_t* nbt, int B, int C, int HW, float eps,
                          float momentum, int act, int groups, void* ws, size_t ws_bytes, void* stream, float* out_amax, int x_dtype,
                          int out_dtype) {
-    log_reset();
+    g_log.reset();
     if (int e = check_bn_args("bn_train_fwd", x && gamma && beta && out && mean && invstd && B > 0 && C > 0 && HW > 0, "bad argument", act, C,
                               residual != nullptr, (running_mean == nullptr) == (running_var == nullptr), B, groups, x_dtype, out_dtype))
         return e;

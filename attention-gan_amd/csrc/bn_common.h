@@ -64,8 +64,6 @@ __device__ __forceinline__ BnStats bn_finish_channel(double s, double q, int n, 
 // ---- device pieces the BatchNorm files with an activation share (bn_act.hip, cond_bn.hip) ---------------------------------------
 constexpr float kSlope = 0.2f;   // LeakyReLU slope, utilities/layers.py:124
 
-__device__ __forceinline__ float sigmoidf_(float v) { return 1.f / (1.f + __expf(-v)); }
-
 // Values per thread and loop step of the streaming sweeps: 8 where a 16-bit tensor is involved and rows are whole 8-groups (16-byte
 // accesses on it), else 4, else 1.  The host's choice of template width and the in-kernel loop choice both call this.
 __host__ __device__ __forceinline__ int vec_width(bool any16, int HW) { return (any16 && (HW & 7) == 0) ? 8 : ((HW & 3) == 0 ? 4 : 1); }
@@ -102,7 +100,7 @@ template <int ACT>
 __device__ __forceinline__ void dz_of(float xa, float xg, float d, const Affine& a, const Affine& g, float& dza, float& dzg) {
     if (ACT == AGAN_ACT_GLU) {
         const float za = norm_of(a, xa);
-        const float sg = sigmoidf_(norm_of(g, xg));
+        const float sg = sigmoid_fast(norm_of(g, xg));
         dza = d * sg;
         dzg = d * za * sg * (1.f - sg);
     } else if (ACT == AGAN_ACT_LRELU) {

@@ -190,10 +190,11 @@ int agan_bn_relu_slice_fwd(const float* x, const float* gamma, const float* beta
         });
         return check_launch("bn_relu_slice_fwd/small");
     }
-    if (!ws || ws_bytes < agan_bn_relu_slice_fwd_ws_bytes(B, C, HW)) {
-        set_error("bn_relu_slice_fwd: workspace too small");
+    if (!ws) {
+        set_error("bn_relu_slice_fwd: no workspace");
         return AGAN_EWORKSPACE;
     }
+    if (int e = check_ws("bn_relu_slice_fwd", agan_bn_relu_slice_fwd_ws_bytes(B, C, HW), ws, ws_bytes)) return e;
     if (int e = agan_bn_stats(x, B, C, HW, eps, mean, invstd, running_mean, running_var, num_batches_tracked, momentum, ws, ws_bytes,
                               stream))
         return e;
@@ -220,10 +221,11 @@ int agan_bn_slice_bwd(const float* x, const float* dout, int dout_c0, int dout_c
         });
         return check_launch("bn_slice_bwd/small");
     }
-    if (!ws || ws_bytes < agan_bn_slice_bwd_ws_bytes(B, C, HW)) {
-        set_error("bn_slice_bwd: workspace too small");
+    if (!ws) {
+        set_error("bn_slice_bwd: no workspace");
         return AGAN_EWORKSPACE;
     }
+    if (int e = check_ws("bn_slice_bwd", agan_bn_slice_bwd_ws_bytes(B, C, HW), ws, ws_bytes)) return e;
     const int nchunk = bn_chunks(B, C, HW);
     double* part = static_cast<double*>(ws);
     float* coef = reinterpret_cast<float*>(part + (size_t)C * nchunk * 2);

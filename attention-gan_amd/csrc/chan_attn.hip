@@ -21,6 +21,7 @@
 // Algorithmic bytes per pixel: forward 4 (C + T) + 4 (T + C); backward 4 (C + T) + 4 (2C + T + C + T).
 #include "agan_common.h"
 #include "dispatch.h"
+#include "mfma_tile.h"
 
 using namespace agan;
 
@@ -32,16 +33,6 @@ constexpr int kCU = 4;      // channels whose loads are issued together in the b
 // Row stride (floats) of the per-wave operand tiles.  The operand read of lane (i = l & 15, k = l >> 4) is a 4-byte LDS read at
 // i * kChLd + 4 step + k: served per 32-lane half (k in {0, 1} or {2, 3}) over 32 banks, bank 2 i + k (+ 4 step) -- all distinct.
 constexpr int kChLd = 66;
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// LDS traffic between the lanes of ONE wave needs no s_barrier (a wave's LDS instructions execute in order); this only stops the
-// compiler from moving LDS accesses across the hand-over.
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 constexpr int contract_tile(int TM, int CM) { return (TM + CM) * kChLd; }                               // floats per wave
 constexpr size_t contract_lds(int TM, int CM) { return sizeof(float) * 4 * contract_tile(TM, CM); }     // bytes per workgroup
@@ -271,10 +262,7 @@ int agan_chan_attn_fwd(const float* h, const float* wt, const int64_t* mask, flo
                        int HW, void* ws, size_t ws_bytes, void* stream) {
     AGAN_REQUIRE(h && wt && mask && alpha && f && ws, "chan_attn_fwd: null pointer");
     CHAN_REQUIRE_SHAPE("chan_attn_fwd");
-    if (ws_bytes < agan_chan_attn_fwd_ws_bytes(B, C, T, HW)) {
-        set_error("chan_attn_fwd: workspace too small (%zu bytes needed)", agan_chan_attn_fwd_ws_bytes(B, C, T, HW));
-        return AGAN_EWORKSPACE;
-    }
+    if (int e = check_ws("chan_attn_fwd", agan_chan_attn_fwd_ws_bytes(B, C, T, HW), ws, ws_bytes)) return e;
     hipStream_t st = as_stream(stream);
     float* part = static_cast<float*>(ws);
     const int nblk = cdiv(HW, 256);
@@ -295,10 +283,7 @@ int agan_chan_attn_bwd(const float* h, const float* wt, const float* alpha, cons
                        float* dh, float* dwt, int B, int C, int T, int HW, void* ws, size_t ws_bytes, void* stream) {
     AGAN_REQUIRE(h && wt && alpha && df && (dh || dwt) && ws, "chan_attn_bwd: null pointer");
     CHAN_REQUIRE_SHAPE("chan_attn_bwd");
-    if (ws_bytes < agan_chan_attn_bwd_ws_bytes(B, C, T, HW)) {
-        set_error("chan_attn_bwd: workspace too small (%zu bytes needed)", agan_chan_attn_bwd_ws_bytes(B, C, T, HW));
-        return AGAN_EWORKSPACE;
-    }
+    if (int e = check_ws("chan_attn_bwd", agan_chan_attn_bwd_ws_bytes(B, C, T, HW), ws, ws_bytes)) return e;
     hipStream_t st = as_stream(stream);
     float* part = static_cast<float*>(ws);
     float* dms = part + slab_floats(B, C, T, HW);

@@ -214,10 +214,11 @@ int agan_allreduce_bucket_dt(void* comm, float* buf, size_t n, int wire_dtype, v
     AGAN_REQUIRE(comm && buf && n > 0 && n % 4 == 0, "allreduce_bucket: bad argument");
     Comm* c = static_cast<Comm*>(comm);
     const size_t nw = agan_exchange_wire_elems(n, c->world), per = nw / (size_t)c->world;
-    if (!scratch || scratch_bytes < agan_allreduce_scratch_bytes(n, c->world, wire_dtype)) {
-        set_error("allreduce_bucket: scratch too small (agan_allreduce_scratch_bytes)");
+    if (!scratch) {
+        set_error("allreduce_bucket: no workspace");
         return AGAN_EWORKSPACE;
     }
+    if (int e = check_ws("allreduce_bucket", agan_allreduce_scratch_bytes(n, c->world, wire_dtype), scratch, scratch_bytes)) return e;
     hipStream_t st = as_stream(stream);
     unsigned short* send = static_cast<unsigned short*>(scratch);
     unsigned short* recv = send + nw;

@@ -10,16 +10,10 @@ using namespace agan;
 namespace {
 
 // ---- launch log: one integer per kernel launch of the last agan_cbn_* call (agan_cbn_last_launch) ------------------------------
-constexpr int kLogCap = 16;
-thread_local int g_log[kLogCap];
-thread_local int g_log_n = 0;
+thread_local LaunchLog<16> g_log;
 // kernel kinds of a log code (include/agan.h: agan_cbn_last_launch)
 enum { kLogStatsRows = 1, kLogStatsSmall, kLogStatsTwoPass, kLogFwdApply, kLogBwdPartialWave, kLogBwdPartialBlock, kLogBwdFinal, kLogBwdApply };
-inline void log_reset() { g_log_n = 0; }
-inline void log_launch(int kind, int act, int width) {
-    if (g_log_n < kLogCap) g_log[g_log_n] = kind * 100000 + act * 10000 + width;
-    ++g_log_n;
-}
+inline void log_launch(int kind, int act, int width) { g_log.add(kind * 100000 + act * 10000 + width); }
 
 // Planes (one sample's values of one channel, contiguous) of at most kWavePlane values are summed by ONE WAVE each, four planes per
 // workgroup: the 8x8 .. 32x32 maps have thousands of them (24 x 512 of 64 values) and a 256-thread workgroup per plane would idle.
@@ -70,7 +64,7 @@ __global__ __launch_bounds__(256) void cbn_fwd_kernel(const float* __restrict__ 
             float gv[V];
             ldv<AGAN_DT_F32, V>(x, xi + (size_t)Co * HW, gv);
 #pragma unroll
-            for (int k = 0; k < V; ++k) yv[k] = norm_of(a, xv[k]) * sigmoidf_(norm_of(g, gv[k]));
+            for (int k = 0; k < V; ++k) yv[k] = norm_of(a, xv[k]) * sigmoid_fast(norm_of(g, gv[k]));
         } else {
 #pragma unroll
             for (int k = 0; k < V; ++k) yv[k] = norm_of(a, xv[k]);
@@ -304,11 +298,7 @@ int cbn_fwd_launch(const float* x, const float* mean, const float* invstd, const
 
 extern "C" {
 
-int agan_cbn_last_launch(int* codes, int capacity) {
-    const int n = std::min(std::min(g_log_n, kLogCap), capacity);
-    for (int i = 0; i < n; ++i) codes[i] = g_log[i];
-    return g_log_n;
-}
+int agan_cbn_last_launch(int* codes, int capacity) { return g_log.copy_out(codes, capacity); }
 
 size_t agan_cbn_train_fwd_ws_bytes(int B, int C, int HW) {
     if (B < 1 || C < 1 || HW < 1) return 0;
@@ -318,14 +308,10 @@ size_t agan_cbn_train_fwd_ws_bytes(int B, int C, int HW) {
 int agan_cbn_train_fwd(const float* x, const float* gamma, const float* beta, const float* delta, float* out, float* mean, float* invstd,
                        float* running_mean, float* running_var, int64_t* nbt, int B, int C, int HW, float eps, float momentum, int act,
                        void* ws, size_t ws_bytes, void* stream, float* out_amax) {
-    log_reset();
+    g_log.reset();
     if (int e = check_cbn_args("cbn_train_fwd", x && gamma && beta && delta && out && mean && invstd, act, B, C, HW)) return e;
     AGAN_REQUIRE((running_mean == nullptr) == (running_var == nullptr), "cbn_train_fwd: running_mean/var must come together");
-    const size_t need = agan_cbn_train_fwd_ws_bytes(B, C, HW);
-    if (ws_bytes < need || (need && !ws)) {
-        set_error("cbn_train_fwd: workspace of %zu bytes, %zu needed", ws_bytes, need);
-        return AGAN_EWORKSPACE;
-    }
+    if (int e = check_ws("cbn_train_fwd", agan_cbn_train_fwd_ws_bytes(B, C, HW), ws, ws_bytes)) return e;
     int form = 0, width = 0;
     if (int e = bn_train_stats(x, B, C, HW, eps, mean, invstd, running_mean, running_var, nbt, momentum, ws, ws_bytes, stream, &form, &width))
         return e;
@@ -335,7 +321,7 @@ int agan_cbn_train_fwd(const float* x, const float* gamma, const float* beta, co
 
 int agan_cbn_act_fwd(const float* x, const float* mean, const float* invstd, const float* gamma, const float* beta, const float* delta,
                      float* out, int B, int C, int HW, int act, void* stream, float* out_amax) {
-    log_reset();
+    g_log.reset();
     if (int e = check_cbn_args("cbn_act_fwd", x && mean && invstd && gamma && beta && delta && out, act, B, C, HW)) return e;
     return cbn_fwd_launch(x, mean, invstd, gamma, beta, delta, out, B, C, HW, act, stream, out_amax);
 }
@@ -348,15 +334,11 @@ size_t agan_cbn_act_bwd_ws_bytes(int B, int C, int HW) {
 int agan_cbn_act_bwd(const float* x, const float* dout, const float* mean, const float* invstd, const float* gamma, const float* beta,
                      const float* delta, float* dx, float* ddelta, float* dgamma, float* dbeta, int B, int C, int HW, int act,
                      int accumulate, void* ws, size_t ws_bytes, void* stream, float* dx_amax) {
-    log_reset();
+    g_log.reset();
     if (int e = check_cbn_args("cbn_act_bwd", x && dout && mean && invstd && gamma && beta && delta && dx && ddelta && dgamma && dbeta && ws,
                                act, B, C, HW))
         return e;
-    const size_t need = agan_cbn_act_bwd_ws_bytes(B, C, HW);
-    if (ws_bytes < need) {
-        set_error("cbn_act_bwd: workspace of %zu bytes, %zu needed", ws_bytes, need);
-        return AGAN_EWORKSPACE;
-    }
+    if (int e = check_ws("cbn_act_bwd", agan_cbn_act_bwd_ws_bytes(B, C, HW), ws, ws_bytes)) return e;
     hipStream_t st = as_stream(stream);
     const bool glu = act == AGAN_ACT_GLU;
     const int Cc = glu ? C / 2 : C;

@@ -1023,14 +1023,6 @@ static WgradRoute route_wgrad(const agan_conv_geom* gg, int pack_mode, int prec,
     return r;
 }
 
-static int check_ws(const char* who, size_t need, const void* ws, size_t ws_bytes) {
-    if (need > ws_bytes || (need && !ws)) {
-        set_error("%s: workspace %zu < %zu", who, ws_bytes, need);
-        return AGAN_EWORKSPACE;
-    }
-    return AGAN_OK;
-}
-
 // the main kernel of a routed call, bracketed by the measurement hook
 template <class Launch>
 static int launch_main(hipStream_t st, int split, const char* what, Launch&& launch) {

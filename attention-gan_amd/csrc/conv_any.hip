@@ -336,10 +336,11 @@ SlabPlan plan_slabs(const agan_conv2d_desc& d) {
 size_t weight_bytes(const agan_conv2d_desc& d) { return (size_t)d.Cout * d.Cin * d.KH * d.KW * sizeof(float); }
 
 int need_ws(const char* who, size_t need, const void* ws, size_t ws_bytes) {
-    if (need > ws_bytes || !ws) {
-        set_error("%s: workspace %zu < %zu", who, ws_bytes, need);
+    if (!ws) {
+        set_error("%s: no workspace", who);
         return AGAN_EWORKSPACE;
     }
+    if (int e = check_ws(who, need, ws, ws_bytes)) return e;
     AGAN_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 15) == 0, "%s: workspace not 16-byte aligned", who);
     return AGAN_OK;
 }

@@ -2,13 +2,12 @@
 #pragma once
 #include "agan_common.h"
 #include "dispatch.h"
+#include "mfma_tile.h"
 
 #include <algorithm>
 
 namespace agan {
 namespace conv {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // Every kernel launch of the conv engine goes through AGAN_LAUNCH, which remembers the host stub of the kernel it launched (thread-local):
 // the measurement hook (agan_timer_arm / agan_timer_last_kernel, conv.hip) can then NAME the kernel a timed call ran -- the demangled
@@ -95,7 +94,6 @@ inline int check_geom(const agan_conv_geom* g) {
 
 // Raw buffer resources: the hardware range check turns every out-of-image / out-of-tile access into a zero load
 // (or a dropped store) -- no exec-mask branches around the gathers (cdna_hip_programming.md T8).
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr unsigned kOOB = 0xFFFFFFFFu;
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, size_t bytes) {

@@ -9,6 +9,7 @@
 // Region features are read coalesced along r (NCHW pixel axis) by the region-owning threads.
 #include "agan_common.h"
 #include "dispatch.h"
+#include "mfma_tile.h"
 
 using namespace agan;
 
@@ -173,7 +174,6 @@ __global__ __launch_bounds__(kNT) void words_pair_fwd_kernel(const float* __rest
 // per 16 rows.  12-float rows put lane (i, k) of an operand read on bank 12 i + k: all 64 banks, conflict-free.
 // Reductions stay in a fixed order (k ascending inside a tile, tiles independent): bit-reproducible like the vector form.
 // ---------------------------------------------------------------------------------------------------------
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int kMW = 12;        // LDS row width (words)
 constexpr int kMD = 256;       // channel rows
 constexpr int kMS = 292;       // region rows: 17 * 17 = 289 padded to a multiple of 4 (the k axis of the channel-indexed contractions)
@@ -188,8 +188,6 @@ struct PairMfmaSmem {
     float colmax[kMW], colsum[kMW];
     float dotw[kNT / 64][kMW];
 };
-
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
 // Feature operand of a wave: FOUR 16-row tiles at once whose rows interleave -- tile q, row i <-> feature row base + 4 i + q -- so that
 // the A values of lane (i, k) for the four tiles are ONE aligned 16-byte load (a dword per tile and MFMA cost four times the cache-line
@@ -940,10 +938,7 @@ int agan_words_loss_bwd(const float* feat, const float* wemb, const int64_t* len
     AGAN_REQUIRE(B >= 1 && B <= kMaxB, "words_loss_bwd: batch %d out of range [1,%d]", B, kMaxB);
     AGAN_REQUIRE(D >= 1 && D <= kNT && S >= 1 && S <= kNT, "words_loss_bwd: nef %d / regions %d out of range [1,%d]", D, S, kNT);
     AGAN_REQUIRE(T >= 1 && T <= 32, "words_loss_bwd: seq_len %d out of range [1,32]", T);
-    if (ws_bytes < agan_words_loss_bwd_ws_bytes(B, D, T, S)) {
-        set_error("words_loss_bwd: workspace %zu < %zu", ws_bytes, agan_words_loss_bwd_ws_bytes(B, D, T, S));
-        return AGAN_EWORKSPACE;
-    }
+    if (int e = check_ws("words_loss_bwd", agan_words_loss_bwd_ws_bytes(B, D, T, S), ws, ws_bytes)) return e;
     hipStream_t st = as_stream(stream);
     float* part_f = static_cast<float*>(ws);
     float* part_w = part_f + (size_t)B * B * D * S;

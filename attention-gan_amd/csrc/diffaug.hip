@@ -270,8 +270,6 @@ __global__ __launch_bounds__(kThreads) void apply_kernel(const float* __restrict
     }
 }
 
-size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
-
 bool in_domain(long long N, int C, int H, int W) {
     const long long lim = 1ll << 31;                                    // (factor by factor: the full product may not fit 64 bits)
     return N >= 1 && N < lim && C >= 1 && C <= 4 && H >= 1 && W >= 1 && (long long)H * W < lim && (long long)H * W * C < lim &&
@@ -315,10 +313,7 @@ int run(const char* what, const float* x0, const float* x1, int n0, int n1, cons
     const Geom g = geom_of(C, H, W, policy);
     const size_t need = ws_bytes_of(N, g);
     AGAN_REQUIRE(ws, "%s: no workspace (agan_diffaug_ws_bytes: %zu bytes)", what, need);
-    if (ws_bytes < need) {
-        set_error("%s: workspace of %zu bytes, %zu needed", what, ws_bytes, need);
-        return AGAN_EWORKSPACE;
-    }
+    if (int e = check_ws(what, need, ws, ws_bytes)) return e;
     double* partial = static_cast<double*>(ws);
     hipStream_t st = as_stream(stream);
     // 16-byte accesses need rows of whole float4s and aligned bases (checked, not assumed); a sample's offset is then aligned too

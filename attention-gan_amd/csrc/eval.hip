@@ -153,8 +153,6 @@ __global__ __launch_bounds__(kThreads) void moments_finish_kernel(const double* 
     cov[(size_t)i * D + j] = count > 1.0 ? (gram[(size_t)lo * D + hi] - count * m_lo * m_hi) / (count - 1.0) : 0.0;
 }
 
-size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
-
 bool moments_in_domain(int n, int D) { return n >= 1 && D >= 1 && D <= kMaxDim && (long long)n * D < (1ll << 31); }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -260,10 +258,7 @@ extern "C" int agan_moments_update(const float* x, int n, int D, double* sum, do
     AGAN_REQUIRE(x && sum && gram, "moments_update: null pointer");
     const size_t need = agan_moments_update_ws_bytes(n, D);
     AGAN_REQUIRE(ws, "moments_update: no workspace (agan_moments_update_ws_bytes: %zu bytes)", need);
-    if (ws_bytes < need) {
-        set_error("moments_update: workspace of %zu bytes, %zu needed", ws_bytes, need);
-        return AGAN_EWORKSPACE;
-    }
+    if (int e = check_ws("moments_update", need, ws, ws_bytes)) return e;
     hipStream_t st = as_stream(stream);
     double* partial = static_cast<double*>(ws);
     const int pieces = cdiv(n, kSumPiece), col_blocks = cdiv(D, kThreads);

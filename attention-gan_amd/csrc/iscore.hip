@@ -143,12 +143,7 @@ __device__ __forceinline__ double block_tree_sum(const double* __restrict__ v, i
     double s = 0.0;
     for (long long i = threadIdx.x; i < n; i += kThreads) s += v[i];
     __syncthreads();                                                // (red may still be read from the previous sum)
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = kThreads / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
+    block_tree_sum_d<kThreads>(s, red);
     return red[0];
 }
 
@@ -165,8 +160,6 @@ __global__ __launch_bounds__(kThreads) void iscore_finish_kernel(const double* _
         scores[3 * s + 2] = hc;
     }
 }
-
-size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 bool in_domain(int N, int C, int splits) {
     return N >= 1 && C >= 1 && C <= kMaxClasses && (long long)N * C < (1ll << 31) && splits >= 1 && splits <= std::min(N, kMaxSplits);
@@ -210,10 +203,7 @@ extern "C" int agan_inception_score(const float* logits, int N, int C, int split
     AGAN_REQUIRE(logits && scores, "inception_score: null pointer");
     const Workspace w(N, C, splits);
     AGAN_REQUIRE(ws, "inception_score: no workspace (agan_inception_score_ws_bytes: %zu bytes)", w.bytes);
-    if (ws_bytes < w.bytes) {
-        set_error("inception_score: workspace of %zu bytes, %zu needed", ws_bytes, w.bytes);
-        return AGAN_EWORKSPACE;
-    }
+    if (int e = check_ws("inception_score", w.bytes, ws, ws_bytes)) return e;
     hipStream_t st = as_stream(stream);
     char* base = static_cast<char*>(ws);
     double* lse = reinterpret_cast<double*>(base + w.lse);

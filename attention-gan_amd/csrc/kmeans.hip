@@ -184,8 +184,6 @@ __global__ __launch_bounds__(kThreads) void assign_final_kernel(const double* __
     if (threadIdx.x == 0) *inertia = red_sum[0], *n_changed = red_changed[0];
 }
 
-size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
-
 bool in_domain(int N, int D, int K) {
     return N >= 1 && D >= 1 && D <= kMaxDim && K >= 1 && K <= kMaxDim && (long long)N * D < (1ll << 31);
 }
@@ -379,10 +377,7 @@ extern "C" int agan_kmeans_assign(const float* x, const float* centroids, int32_
     AGAN_REQUIRE(x && centroids && labels && dist && n_changed && inertia, "kmeans_assign: null pointer");
     const AssignWs w(N, K);
     AGAN_REQUIRE(ws, "kmeans_assign: no workspace (agan_kmeans_assign_ws_bytes: %zu bytes)", w.total);
-    if (ws_bytes < w.total) {
-        set_error("kmeans_assign: workspace of %zu bytes, %zu needed", ws_bytes, w.total);
-        return AGAN_EWORKSPACE;
-    }
+    if (int e = check_ws("kmeans_assign", w.total, ws, ws_bytes)) return e;
     char* base = static_cast<char*>(ws);
     float* cnorm = reinterpret_cast<float*>(base + w.cnorm);
     double* part_sum = reinterpret_cast<double*>(base + w.part_sum);
@@ -409,10 +404,7 @@ extern "C" int agan_kmeans_update(const float* x, const int32_t* labels, float* 
     AGAN_REQUIRE(x && labels && centroids && counts, "kmeans_update: null pointer");
     const UpdateWs w(N, D, K);
     AGAN_REQUIRE(ws, "kmeans_update: no workspace (agan_kmeans_update_ws_bytes: %zu bytes)", w.total);
-    if (ws_bytes < w.total) {
-        set_error("kmeans_update: workspace of %zu bytes, %zu needed", ws_bytes, w.total);
-        return AGAN_EWORKSPACE;
-    }
+    if (int e = check_ws("kmeans_update", w.total, ws, ws_bytes)) return e;
     char* base = static_cast<char*>(ws);
     int32_t* hist = reinterpret_cast<int32_t*>(base + w.hist);
     int32_t* first_slot = reinterpret_cast<int32_t*>(base + w.first_slot);

@@ -21,8 +21,6 @@ namespace {
 constexpr int kRows = 4;         // batch rows per recurrence workgroup
 constexpr int kThreads = 256;
 
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
-
 __device__ __forceinline__ int clamp_len(const int32_t* lens, int b, int T) { return min(max(lens[b], 0), T); }
 
 // ---- embedding --------------------------------------------------------------------------------------------------------------------
@@ -104,8 +102,8 @@ __global__ __launch_bounds__(4 * H) void lstm_fwd_kernel(const float* __restrict
         __syncthreads();
         if (s < mylen) {
             const int t = dir ? mylen - 1 - s : s;
-            const float gi = sigmoidf_(gs[cb][cu]), gf = sigmoidf_(gs[cb][H + cu]), gg = tanhf(gs[cb][2 * H + cu]),
-                        go = sigmoidf_(gs[cb][3 * H + cu]);
+            const float gi = sigmoid_exact(gs[cb][cu]), gf = sigmoid_exact(gs[cb][H + cu]), gg = tanhf(gs[cb][2 * H + cu]),
+                        go = sigmoid_exact(gs[cb][3 * H + cu]);
             c = gf * c + gi * gg;
             h = go * tanhf(c);
             const size_t bt = (size_t)b * T + t;

@@ -328,16 +328,9 @@ __global__ __launch_bounds__(kThreads) void poly_final_kernel(const double* __re
     __shared__ double red[kThreads];
     double s = 0.0;
     for (int i = threadIdx.x; i < blocks; i += kThreads) s += partial[i];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = kThreads / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
+    block_tree_sum_d<kThreads>(s, red);
     if (threadIdx.x == 0) *out = red[0];
 }
-
-size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 bool rows_in_domain(int n, int D) { return n >= 1 && D >= 1 && D <= kMaxDim && (long long)n * D < (1ll << 31); }
 bool knn_in_domain(int n, int D, int k) { return k >= 1 && k <= kMaxK && n >= k + 1 && rows_in_domain(n, D); }
@@ -381,10 +374,7 @@ extern "C" int agan_knn_radius(const float* x, int n, int D, int k, float* rad2,
     AGAN_REQUIRE(x && rad2, "knn_radius: null pointer");
     const size_t need = agan_knn_radius_ws_bytes(n, D, k);
     AGAN_REQUIRE(ws, "knn_radius: no workspace (agan_knn_radius_ws_bytes: %zu bytes)", need);
-    if (ws_bytes < need) {
-        set_error("knn_radius: workspace of %zu bytes, %zu needed", ws_bytes, need);
-        return AGAN_EWORKSPACE;
-    }
+    if (int e = check_ws("knn_radius", need, ws, ws_bytes)) return e;
     hipStream_t st = as_stream(stream);
     const Split sp(n, n);
     float* norm = static_cast<float*>(ws);
@@ -411,10 +401,7 @@ extern "C" int agan_manifold_scan(const float* q, const float* ref, const float*
     AGAN_REQUIRE(q && ref && count && near_d2 && near_idx, "manifold_scan: null pointer");
     const size_t need = agan_manifold_scan_ws_bytes(m, n, D);
     AGAN_REQUIRE(ws, "manifold_scan: no workspace (agan_manifold_scan_ws_bytes: %zu bytes)", need);
-    if (ws_bytes < need) {
-        set_error("manifold_scan: workspace of %zu bytes, %zu needed", ws_bytes, need);
-        return AGAN_EWORKSPACE;
-    }
+    if (int e = check_ws("manifold_scan", need, ws, ws_bytes)) return e;
     hipStream_t st = as_stream(stream);
     const Split sp(m, n);
     const size_t part_bytes = up16((size_t)sp.splits * m * sizeof(float));
@@ -452,10 +439,7 @@ extern "C" int agan_poly_kernel_sum(const float* x, const float* y, int n, int m
     AGAN_REQUIRE(x && y && out, "poly_kernel_sum: null pointer");
     const size_t need = agan_poly_kernel_sum_ws_bytes(n, m, D);
     AGAN_REQUIRE(ws, "poly_kernel_sum: no workspace (agan_poly_kernel_sum_ws_bytes: %zu bytes)", need);
-    if (ws_bytes < need) {
-        set_error("poly_kernel_sum: workspace of %zu bytes, %zu needed", ws_bytes, need);
-        return AGAN_EWORKSPACE;
-    }
+    if (int e = check_ws("poly_kernel_sum", need, ws, ws_bytes)) return e;
     hipStream_t st = as_stream(stream);
     double* partial = static_cast<double*>(ws);
     const Split sp(n, m);

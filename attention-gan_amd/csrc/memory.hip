@@ -12,6 +12,7 @@
 // The backward keeps nothing but the attention map: o and g_r are recomputed.
 #include "agan_common.h"
 #include "dispatch.h"
+#include "mfma_tile.h"
 
 using namespace agan;
 
@@ -22,18 +23,6 @@ constexpr int kMaxT = 64;   // words
 constexpr int kCU = 4;      // channels whose loads are issued together in the backward's channel loops
 constexpr int kMemLd = 68;  // row stride (floats) of the per-wave transposition tiles of the backward (attention.hip: kAttLd)
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float sigmoid1(float z) { return 1.f / (1.f + __expf(-z)); }
-
-// LDS traffic between the lanes of ONE wave needs no s_barrier (a wave's LDS instructions execute in order); this only stops the
-// compiler from moving LDS accesses across the hand-over.
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // ---------------------------------------------------------------------------------------------------------------------- write
 __global__ __launch_bounds__(256) void mem_write_fwd_kernel(const float* __restrict__ U, const float* __restrict__ Q,
                                                             float* __restrict__ m, int T, int Md, int n) {
@@ -42,7 +31,7 @@ __global__ __launch_bounds__(256) void mem_write_fwd_kernel(const float* __restr
     const int d = i % Md, bt = i / Md, b = bt / T;
     const float* u = U + (size_t)bt * (Md + 1);
     const float* q = Q + (size_t)b * (Md + 1);
-    const float g = sigmoid1(u[Md] + q[Md]);
+    const float g = sigmoid_fast(u[Md] + q[Md]);
     m[i] = fmaxf(u[d], 0.f) * g + fmaxf(q[d], 0.f) * (1.f - g);
 }
 
@@ -59,7 +48,7 @@ __global__ __launch_bounds__(256) void mem_write_bwd_kernel(const float* __restr
         const float* u = U + bt * (Md + 1);
         const float* dr = dm + bt * Md;
         float* du = dU + bt * (Md + 1);
-        const float g = sigmoid1(u[Md] + q[Md]);
+        const float g = sigmoid_fast(u[Md] + q[Md]);
         float s = 0.f;
         for (int d = lane; d < Md; d += 64) {
             const float uv = u[d], qv = q[d], dv = dr[d];
@@ -161,7 +150,7 @@ __global__ __launch_bounds__(256) void mem_read_fwd_kernel(const float* __restri
         z += sc[t] * vw[t];
         if (t < T) ao[(size_t)t * HW] = sc[t];
     }
-    const float g = sigmoid1(z);
+    const float g = sigmoid_fast(z);
 #pragma unroll
     for (int c = 0; c < CMAX; ++c) {
         if (c < C) {
@@ -263,7 +252,7 @@ __global__ __launch_bounds__(256) void mem_read_bwd_kernel(const float* __restri
     }
 #pragma unroll
     for (int t = 0; t < TMAX; ++t) z += a[t] * vw[t];
-    const float g = sigmoid1(z);
+    const float g = sigmoid_fast(z);
     const float dz = dg * g * (1.f - g);                 // 0 in a lane past the map (dg = 0)
     float dot = 0.f;
 #pragma unroll
@@ -525,10 +514,7 @@ int agan_mem_read_bwd(const float* h, const float* kv, const int64_t* mask, cons
     AGAN_REQUIRE(B > 0 && C > 0 && T > 0 && HW > 0, "mem_read_bwd: non-positive dimension");
     AGAN_REQUIRE(C <= kMaxC && T <= kMaxT, "mem_read_bwd: nc_in %d / seq_len %d out of range", C, T);
     AGAN_REQUIRE(read_shape_ok(B, C, T, HW), "mem_read_bwd: B * 2 nc_in * HW and B * seq_len * HW must stay below 2^31, B below 65536");
-    if (ws_bytes < agan_mem_read_bwd_ws_bytes(B, C, T, HW)) {
-        set_error("mem_read_bwd: workspace too small (%zu bytes needed)", agan_mem_read_bwd_ws_bytes(B, C, T, HW));
-        return AGAN_EWORKSPACE;
-    }
+    if (int e = check_ws("mem_read_bwd", agan_mem_read_bwd_ws_bytes(B, C, T, HW), ws, ws_bytes)) return e;
     hipStream_t st = as_stream(stream);
     const int nblk = cdiv(HW, 256);
     float* part_kv = static_cast<float*>(ws);

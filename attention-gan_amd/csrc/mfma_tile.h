@@ -6,7 +6,9 @@
 
 namespace agan {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));        // accumulator of a 32 x 32 MFMA tile
+typedef float f32x4 __attribute__((ext_vector_type(4)));          // accumulator of a 16 x 16 MFMA tile; a 16-byte access
+__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
 constexpr int kTileThreads = 256;      // threads of a workgroup that uses TileRegs
 constexpr int kStep = 32;              // columns of D per LDS stage

@@ -40,15 +40,9 @@ constexpr size_t kLdsLimit = 65536;
 constexpr int kTargetGroups = 256;
 
 // ---- launch log: one integer per kernel launch of the last agan_self_attn_* / agan_scaled_residual_* call -------------------------
-constexpr int kLogCap = 8;
-thread_local int g_log[kLogCap];
-thread_local int g_log_n = 0;
+thread_local LaunchLog<8> g_log;
 enum { kLogFwd = 1, kLogDelta, kLogBwdKV, kLogBwdQ, kLogGateFwd, kLogGateBwd, kLogGateFinal };
-inline void log_reset() { g_log_n = 0; }
-inline void log_launch(int kind, int W, int dkt, int dvt) {
-    if (g_log_n < kLogCap) g_log[g_log_n] = kind * 100000 + (W * kT) * 100 + dkt * 10 + dvt;
-    ++g_log_n;
-}
+inline void log_launch(int kind, int W, int dkt, int dvt) { g_log.add(kind * 100000 + (W * kT) * 100 + dkt * 10 + dvt); }
 
 // img[rows][kLd] <- columns c0 .. c0 + 31 of the first `valid` rows of src (row stride n_cols); everything else reads 0
 // (the resident tiles, once per workgroup)
@@ -380,12 +374,7 @@ __global__ __launch_bounds__(kGateThreads) void gate_bwd_kernel(const float* __r
         dy[i] = mul_rn(gv, d);
         s += (double)d * (double)y[i];
     }
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = kGateThreads / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
+    block_tree_sum_d<kGateThreads>(s, red);
     if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
 }
 
@@ -393,19 +382,13 @@ __global__ __launch_bounds__(kGateThreads) void gate_final_kernel(const double* 
     __shared__ double red[kGateThreads];
     double s = 0.0;
     for (int i = threadIdx.x; i < blocks; i += kGateThreads) s += partial[i];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = kGateThreads / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
+    block_tree_sum_d<kGateThreads>(s, red);
     if (threadIdx.x == 0) dg[0] = (float)((accumulate ? (double)dg[0] : 0.0) + red[0]);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------------------
-size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
 int even(int d) { return (d + 1) & ~1; }
 int dk_tiles(int Dk) { return Dk <= kT ? 1 : 2; }
 int dv_tiles(int Dv) { return Dv <= kT ? 1 : Dv <= 2 * kT ? 2 : 4; }
@@ -448,15 +431,11 @@ int check_stride(const char* what, const char* name, long long bs, int rows, int
 
 extern "C" {
 
-int agan_self_attn_last_launch(int* codes, int capacity) {
-    const int n = std::min(std::min(g_log_n, kLogCap), capacity);
-    for (int i = 0; i < n; ++i) codes[i] = g_log[i];
-    return g_log_n;
-}
+int agan_self_attn_last_launch(int* codes, int capacity) { return g_log.copy_out(codes, capacity); }
 
 int agan_self_attn_fwd(const float* q, const float* k, const float* v, float* o, float* lse, int B, int N, int M, int Dk, int Dv, long long q_bs,
                        long long k_bs, long long v_bs, long long o_bs, float scale, void* stream) {
-    log_reset();
+    g_log.reset();
     if (int e = check_shape("self_attn_fwd", B, N, M, Dk, Dv, scale)) return e;
     if (int e = check_stride("self_attn_fwd", "q", q_bs, Dk, N)) return e;
     if (int e = check_stride("self_attn_fwd", "k", k_bs, Dk, M)) return e;
@@ -483,7 +462,7 @@ size_t agan_self_attn_bwd_ws_bytes(int B, int N, int M, int Dk, int Dv) {
 int agan_self_attn_bwd(const float* q, const float* k, const float* v, const float* o, const float* lse, const float* dout, float* dq, float* dk,
                        float* dv, int B, int N, int M, int Dk, int Dv, long long q_bs, long long k_bs, long long v_bs, long long o_bs,
                        long long do_bs, long long dq_bs, long long dk_bs, long long dv_bs, float scale, void* ws, size_t ws_bytes, void* stream) {
-    log_reset();
+    g_log.reset();
     const char* what = "self_attn_bwd";
     if (int e = check_shape(what, B, N, M, Dk, Dv, scale)) return e;
     if (int e = check_stride(what, "q", q_bs, Dk, N)) return e;
@@ -495,11 +474,7 @@ int agan_self_attn_bwd(const float* q, const float* k, const float* v, const flo
     if (int e = check_stride(what, "dk", dk_bs, Dk, M)) return e;
     if (int e = check_stride(what, "dv", dv_bs, Dv, M)) return e;
     AGAN_REQUIRE(q && k && v && o && lse && dout && dq && dk && dv && ws, "self_attn_bwd: null pointer");
-    const size_t need = agan_self_attn_bwd_ws_bytes(B, N, M, Dk, Dv);
-    if (ws_bytes < need) {
-        set_error("self_attn_bwd: workspace of %zu bytes, %zu needed", ws_bytes, need);
-        return AGAN_EWORKSPACE;
-    }
+    if (int e = check_ws(what, agan_self_attn_bwd_ws_bytes(B, N, M, Dk, Dv), ws, ws_bytes)) return e;
     hipStream_t st = as_stream(stream);
     float* delta = static_cast<float*>(ws);
     const int total = B * N;
@@ -534,7 +509,7 @@ int agan_self_attn_bwd(const float* q, const float* k, const float* v, const flo
 }
 
 int agan_scaled_residual_fwd(const float* x, const float* y, const float* g, float* out, size_t n, void* stream) {
-    log_reset();
+    g_log.reset();
     AGAN_REQUIRE(n >= 1, "scaled_residual_fwd: no elements");
     AGAN_REQUIRE(x && y && g && out, "scaled_residual_fwd: null pointer");
     hipLaunchKernelGGL(gate_fwd_kernel, dim3(gate_blocks(n)), dim3(kGateThreads), 0, as_stream(stream), x, y, g, out, n);
@@ -546,14 +521,10 @@ size_t agan_scaled_residual_bwd_ws_bytes(size_t n) { return n >= 1 ? up16((size_
 
 int agan_scaled_residual_bwd(const float* dout, const float* y, const float* g, float* dy, float* dg, size_t n, int accumulate, void* ws,
                              size_t ws_bytes, void* stream) {
-    log_reset();
+    g_log.reset();
     AGAN_REQUIRE(n >= 1, "scaled_residual_bwd: no elements");
     AGAN_REQUIRE(dout && y && g && dy && dg && ws, "scaled_residual_bwd: null pointer");
-    const size_t need = agan_scaled_residual_bwd_ws_bytes(n);
-    if (ws_bytes < need) {
-        set_error("scaled_residual_bwd: workspace of %zu bytes, %zu needed", ws_bytes, need);
-        return AGAN_EWORKSPACE;
-    }
+    if (int e = check_ws("scaled_residual_bwd", agan_scaled_residual_bwd_ws_bytes(n), ws, ws_bytes)) return e;
     hipStream_t st = as_stream(stream);
     double* partial = static_cast<double*>(ws);
     const int blocks = gate_blocks(n);

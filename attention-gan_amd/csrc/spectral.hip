@@ -421,11 +421,7 @@ int agan_spectral_fwd(const float* w0, const float* w1, const float* u, const fl
     AGAN_REQUIRE(iterate == 0 || iterate == 1, "spectral_fwd: iterate must be 0 or 1, got %d", iterate);
     AGAN_REQUIRE(w0 && u && sigma && wsn0 && (k1 == 0 || (w1 && wsn1)), "spectral_fwd: null pointer");
     AGAN_REQUIRE(iterate ? (u_out && v_out) : v != nullptr, "spectral_fwd: null pointer (u_out and v_out with iterate = 1, v with iterate = 0)");
-    const size_t need = agan_spectral_fwd_ws_bytes(cout, k0, k1);
-    if (ws_bytes < need || (need > 0 && !ws)) {
-        set_error("spectral_fwd: workspace too small (%zu bytes needed)", need);
-        return AGAN_EWORKSPACE;
-    }
+    if (int e = check_ws("spectral_fwd", agan_spectral_fwd_ws_bytes(cout, k0, k1), ws, ws_bytes)) return e;
     Mat m;
     m.w[0] = w0, m.w[1] = k1 > 0 ? w1 : w0, m.cout = cout, m.k[0] = k0, m.k[1] = k1;
     m.vec = (unsigned)(k0 % 4 == 0 && aligned16(w0)) | ((unsigned)(k1 > 0 && k1 % 4 == 0 && aligned16(w1)) << 1);
@@ -462,11 +458,7 @@ int agan_spectral_bwd(const float* dwsn0, const float* dwsn1, const float* wsn0,
                       size_t ws_bytes, void* stream) {
     SPECTRAL_SHAPE("spectral_bwd");
     AGAN_REQUIRE(dwsn0 && wsn0 && u && v && sigma && dw0 && (k1 == 0 || (dwsn1 && wsn1 && dw1)), "spectral_bwd: null pointer");
-    const size_t need = agan_spectral_bwd_ws_bytes(cout, k0, k1);
-    if (ws_bytes < need || (need > 0 && !ws)) {
-        set_error("spectral_bwd: workspace too small (%zu bytes needed)", need);
-        return AGAN_EWORKSPACE;
-    }
+    if (int e = check_ws("spectral_bwd", agan_spectral_bwd_ws_bytes(cout, k0, k1), ws, ws_bytes)) return e;
     Grad g;
     g.d[0] = dwsn0, g.wsn[0] = wsn0, g.out[0] = dw0, g.acc[0] = accumulate0 != 0;
     g.d[1] = dwsn1, g.wsn[1] = wsn1, g.out[1] = dw1, g.acc[1] = accumulate1 != 0;

@@ -22,6 +22,7 @@
 // the words is re-used for d(attention) and then d(scores); the last contraction reads its word operand from global memory (L2).
 #include "agan_common.h"
 #include "dispatch.h"
+#include "mfma_tile.h"
 
 using namespace agan;
 
@@ -32,9 +33,6 @@ constexpr int kNW = kNT / 64;
 constexpr int kMaxB = 128;
 constexpr int kMaxT = 32;
 constexpr int kSaveRows = 5;       // save[b][k][T]: k = 0 <ctx_l, w_l>, 1 |w_l|, 2 |ctx_l|, 3 r_l, 4 g_l
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
 // the shape of a pair as the kernels use it
 struct PairDims {
@@ -223,7 +221,6 @@ __device__ __forceinline__ int caption_len(const int64_t* __restrict__ lens, int
     const int64_t v = lens[c];
     return v < 0 ? 0 : (v > T ? T : (int)v);
 }
-__device__ __forceinline__ float sigmoidf(float x) { return 1.f / (1.f + expf(-x)); }
 
 template <int NLT>
 __global__ __launch_bounds__(kNT) void word_corr_fwd_kernel(const float* __restrict__ regions, const float* __restrict__ words,
@@ -269,7 +266,7 @@ __global__ __launch_bounds__(kNT) void word_corr_fwd_kernel(const float* __restr
         const float sum = wave_sum(e);
         const float gl = live ? e / sum : 0.f;
         const float rl = live ? sm.r[lane] : 0.f;
-        const float pv = wave_sum(live ? gl * sigmoidf(gamma2 * rl) : 0.f);
+        const float pv = wave_sum(live ? gl * sigmoid_exact(gamma2 * rl) : 0.f);
         if (lane < T) {
             r_out[(size_t)b * T + lane] = rl;
             g_out[(size_t)b * T + lane] = gl;
@@ -309,7 +306,7 @@ __global__ __launch_bounds__(kNT) void word_corr_bwd_kernel(const float* __restr
         if (tid < g.L) {
             const float* sv = save + (size_t)b * kSaveRows * T + tid;
             const float num = sv[0], n1 = sv[T], n2 = sv[2 * T], rl = sv[3 * T], gl = sv[4 * T];
-            const float sg = sigmoidf(gamma2 * rl);
+            const float sg = sigmoid_exact(gamma2 * rl);
             const float dr = dp[b] * gl * gamma2 * sg * (1.f - sg);
             const float nn = n1 * n2;
             if (nn > eps) {
